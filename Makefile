@@ -2,7 +2,7 @@
 #   make            -> engine + compat + harness + oracle restatement
 #   make engine     -> arm-spmv_amd/lib/libspmv_hip.so       (hipcc, gfx950 only)
 #   make oracle     -> oracle/_build/libspmv_oracle.so     (test infrastructure)
-#   make ref        -> oracle/_ref/libarmspmv_ref.so       (needs /root/reference; build container only)
+#   make ref        -> oracle/_ref/libarmspmv_ref.so + ref_main  (needs the reference's sources)
 HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
 PKG      := arm-spmv_amd
@@ -37,7 +37,7 @@ host: engine
 oracle:
 	$(MAKE) -C oracle
 
-ref:
+ref: host
 	$(MAKE) -C oracle ref
 
 clean:

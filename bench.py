@@ -175,6 +175,26 @@ def host_limits() -> dict:
     return out
 
 
+DUMP_ROWS = 2_000_000  # rows of y that --dump-outputs writes, over all ranks: value + row index, 8 bytes each: 32 MB
+
+
+def dump_outputs(out_dir: str, y, row_begin: int, rank: int, world: int) -> None:
+    """--dump-outputs: what the timed loop left in this rank's y (y += A*x, accumulated over the warm-up and timed steps) as
+    float64 .npy files: every row where they fit in DUMP_ROWS / world, else a fixed seeded sample of them, and next to it
+    the global indices of those rows (y_rows).  At N > 1 every rank writes its own slice (suffix _rank<r>)."""
+    import numpy as np
+    import torch
+
+    n = y.numel()
+    m = min(n, DUMP_ROWS // world)
+    rows = np.arange(n) if m == n else np.sort(np.random.default_rng(20240501).choice(n, m, replace=False))
+    vals = y.index_select(0, torch.from_numpy(rows).to(y.device)).cpu().numpy()
+    suffix = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"y{suffix}.npy"), vals.astype(np.float64))
+    np.save(os.path.join(out_dir, f"y_rows{suffix}.npy"), (rows + row_begin).astype(np.float64))
+
+
 def cpu_baseline_child(args) -> dict:
     """The CPU leg of the report, in a process of its own (no torch: its OpenMP runtime and thread pools would be in
     the way; OMP_PROC_BIND / OMP_PLACES have to be in the environment before libgomp starts).  Times, on the GPU box's
@@ -535,7 +555,12 @@ def main() -> None:
                          "(the reference's split, src/mat_vec.cpp:245-246), by stored entries (spmv_partition_rows_balanced), or both")
     ap.add_argument("--no-shared-plan", action="store_true", help="N > 1: every rank selects its kernel by itself (A/B against rank 0's plan broadcast)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the y they computed to DIR/y.npy (float64; a fixed seeded sample of its rows, "
+                         "listed in DIR/y_rows.npy, where y is larger than %d rows)" % DUMP_ROWS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_child:
         print(json.dumps(cpu_baseline_child(args)), flush=True)
         return
@@ -685,6 +710,8 @@ def main() -> None:
         barrier()
         wall_s = time.perf_counter() - t0
         kernel_ms = ev0.elapsed_time(ev1) / args.steps  # HIP events on the stream the kernel runs on
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, y, row_begin, rank, world)
 
         # secondary: the same loop with the x exchange charged to every step (solver-realistic)
         exch_s = None

@@ -6,7 +6,8 @@ The fixtures are DATA: inputs (or, for c1, the seed + a sha256 of the inputs) an
 reference's own compiled code produced for them — y after 1 and after 50 accumulating calls
 (NUM_TEST, main.cpp:16) of COOMatirxMatVector / CSRMatrixMatVector / ELLMatrixMatVector /
 CSCMatrixMatVector (+ DIAMatrixMatVector on the square tridiagonal), and the arrays built by the
-converting constructors CSRMatrix(COO), CSCMatrix(COO), ELLMatrix(COO), DIAMatrix(CSR).
+converting constructors CSRMatrix(COO), CSCMatrix(COO), ELLMatrix(COO), DIAMatrix(CSR).  Also live.npz (the
+reference's answers for cases.live_matrices()) and reader.npz (its COOMatrixRead on cases.odd_mtx_files()).
 OMP_NUM_THREADS=1 so that the `omp atomic` loops (COO, CSC) run in file order.
 """
 import os
@@ -15,6 +16,7 @@ os.environ["OMP_NUM_THREADS"] = "1"
 
 import ctypes as C
 import sys
+import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -94,14 +96,38 @@ def run_case(ref, c):
     return out
 
 
+def live_cases(ref):
+    """live.npz: the reference's answers for cases.live_matrices(), keys suffixed with the case's index"""
+    out = {}
+    for i, (nrow, ncol, row, col, val, x) in enumerate(cases.live_matrices()):
+        for key, v in ol.ref_live_outputs(ref, nrow, ncol, row, col, val, x).items():
+            out[f"{key}{i}"] = np.array(v)
+    return out
+
+
+def reader_cases():
+    """reader.npz: what the reference's COOMatrixRead returns for cases.odd_mtx_files(), per file (sorted by name) its
+    dimensions and a digest of row, col and the values' bits"""
+    with tempfile.TemporaryDirectory() as tmp:
+        files = cases.odd_mtx_files(Path(tmp))
+        names = sorted(files)
+        got = ol.read_mtx_files(ol.REF_SO, [files[n] for n in names], Path(tmp) / "ref.npz")
+        out = {"names": np.array(names)}
+        for i in range(len(names)):
+            out[f"dims{i}"] = got[f"dims{i}"]
+            out[f"sha{i}"] = np.array(cases.digest(got[f"row{i}"], got[f"col{i}"], got[f"val{i}"]))
+    return out
+
+
 def main():
     if not ol.ref_available():
         sys.exit("oracle/_ref/libarmspmv_ref.so missing: run `make ref` in the build container first")
     ref = ol.load_ref()
-    for make in cases.ALL_CASES:
-        c = make()
-        out = run_case(ref, c)
-        path = HERE / f"{c['name']}.npz"
+    fixtures = [(c["name"], lambda c=c: run_case(ref, c)) for c in (make() for make in cases.ALL_CASES)]
+    fixtures += [("live", lambda: live_cases(ref)), ("reader", reader_cases)]
+    for name, make in fixtures:
+        out = make()
+        path = HERE / f"{name}.npz"
         np.savez_compressed(path, **out)
         print(f"wrote {path.name}: {sorted(out)[:6]}... ({path.stat().st_size} bytes)")
 

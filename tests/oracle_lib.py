@@ -62,6 +62,46 @@ def load_ref() -> C.CDLL:
     return lib
 
 
+def ref_live_outputs(ref, nrow, ncol, row, col, val, x) -> dict:
+    """what the reference computes for one of cases.live_matrices(): its CSRMatrix(COO) (digest), ELLMatrix(COO)'s
+    width, one product of COO / CSR / ELL into a zero y, and dot(x, x) over min(nrow, ncol)"""
+    import cases
+
+    nnz = len(val)
+    rp, cc, cv = np.zeros(nrow + 1, np.int32), np.zeros(nnz, np.int32), np.zeros(nnz)
+    # one thread, whatever OMP_NUM_THREADS says: the reference's COO product adds with `omp atomic`, in file order only so
+    gomp = C.CDLL("libgomp.so.1")
+    threads = gomp.omp_get_max_threads()
+    gomp.omp_set_num_threads(1)
+    try:
+        ref.ref_coo_to_csr(nrow, ncol, nnz, _p(row), _p(col), _p(val), _p(rp), _p(cc), _p(cv))
+        k = ref.ref_coo_to_ell(nrow, ncol, nnz, _p(row), _p(col), _p(val), None, None)
+        ec, ev = np.zeros(nrow * k, np.int32), np.zeros(nrow * k)
+        ref.ref_coo_to_ell(nrow, ncol, nnz, _p(row), _p(col), _p(val), _p(ec), _p(ev))
+        out = {"sha_csr": cases.digest(rp, cc, cv), "ell_k": k}
+        for fmt, run in (("coo", lambda y: ref.ref_coo_spmv(nrow, ncol, nnz, _p(row), _p(col), _p(val), _p(x), _p(y))),
+                         ("csr", lambda y: ref.ref_csr_spmv(nrow, ncol, _p(rp), _p(cc), _p(cv), _p(x), _p(y))),
+                         ("ell", lambda y: ref.ref_ell_spmv(nrow, ncol, nnz, k, _p(ec), _p(ev), _p(x), _p(y)))):
+            y = np.zeros(nrow)
+            run(y)
+            out[f"y_{fmt}"] = y
+        n = min(nrow, ncol)
+        out["dot"] = ref.ref_dot(n, _p(x[:n].copy()), _p(x[:n].copy()))
+    finally:
+        gomp.omp_set_num_threads(threads)
+    return out
+
+
+def read_mtx_files(so, paths, out, env=None):
+    """COOMatrixRead of the library `so` (the compat shim or the compiled reference) over every file, in a child process
+    of its own (tests/reader_child.py: both export the same C++ names); returns the npz it wrote to `out`"""
+    child = Path(__file__).with_name("reader_child.py")
+    r = subprocess.run(["python3", str(child), str(so), str(out)] + [str(p) for p in paths],
+                       capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, (str(so), r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    return np.load(out)
+
+
 # ---------------------------------------------------------------- oracle wrappers (y updated in place)
 def _sfx(fma: bool) -> str:
     return "_fma" if fma else ""

@@ -63,3 +63,24 @@ def test_live_counter_rows_are_reduced_to_the_products_of_the_right_kernel():
     assert per == {"tp_expand_kernel": 5.0, "tp_reduce_kernel": 1.0} and shown == "tp_reduce_kernel"
     assert "fewer than 3" in bench.pmc_mean_of_products(rows[:10], 4)
     assert "no product kernel" in bench.pmc_mean_of_products(rows, 99)
+
+
+def test_dump_outputs_writes_y_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """--dump-outputs: float64 y and the global indices of its rows; every row where they fit, else the same seeded sample
+    in every run, within the 64 MB bound at the default size"""
+    import numpy as np
+    import torch
+
+    assert 16 * bench.DUMP_ROWS <= 64_000_000
+    y = torch.arange(1000, dtype=torch.float64) * 0.5
+    bench.dump_outputs(str(tmp_path / "all"), y, 0, 0, 1)
+    assert np.array_equal(np.load(tmp_path / "all" / "y.npy"), y.numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "y_rows.npy"), np.arange(1000.0))
+    monkeypatch.setattr(bench, "DUMP_ROWS", 200)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), y, 3000, 1, 2)
+    rows = np.load(tmp_path / "a" / "y_rows_rank1.npy")
+    vals = np.load(tmp_path / "a" / "y_rank1.npy")
+    assert rows.dtype == vals.dtype == np.float64 and len(rows) == 100 and len(np.unique(rows)) == 100
+    assert np.array_equal(vals, (rows - 3000) * 0.5)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "y_rows_rank1.npy"))

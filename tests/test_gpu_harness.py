@@ -137,9 +137,9 @@ def test_sharded_drivers_partition_by_rows_or_by_entries(tmp_path, pkg):
 
 
 def test_reference_main_cpp_runs_unchanged_on_the_engine(tmp_path, pkg):
-    exe = BIN / "ref_main"
+    exe = ROOT / "oracle" / "_ref" / "ref_main"
     if not exe.exists():
-        pytest.skip("ref_main is built only where the reference sources exist (build container)")
+        pytest.skip("oracle/_ref/ref_main is built only where the reference sources exist (make ref)")
     p = _mtx(tmp_path, pkg, 1500, 8, 23)
     r = subprocess.run([str(exe), str(p), "4"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr

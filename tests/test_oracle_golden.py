@@ -1,7 +1,7 @@
 """Pin the oracle: our C restatement (oracle/spmv_oracle.c) against the golden vectors produced by the REAL
 reference (tests/golden/*.npz, made by tests/golden/make_golden.py from oracle/_ref) — bit for bit — and,
-where the compiled reference is present (build container; the .so also travels to the GPU box), live against
-it on fresh random inputs.  CPU only."""
+on random inputs, against the reference's stored answers for them and, where the compiled reference is present,
+live against it.  CPU only."""
 import ctypes as C
 
 import numpy as np
@@ -114,39 +114,29 @@ def test_partition_is_the_numa_drivers(orc):
     assert np.array_equal(ol.csr_shard_row_ptr(orc, rp, 2, 5), [0, 3, 7, 7])
 
 
-@pytest.mark.skipif(not ol.ref_available(), reason="oracle/_ref not built (needs the reference sources)")
 def test_oracle_live_against_compiled_reference():
-    """fresh random matrices, oracle vs the reference's own compiled code, bit for bit"""
-    orc, ref = ol.load_oracle(), ol.load_ref()
-    p = ol._p
-    rng = np.random.RandomState(123)
-    for nrow, ncol, nnz in ((1, 1, 1), (17, 5, 60), (200, 300, 5000), (1000, 1000, 16000)):
-        row = rng.randint(0, nrow, size=nnz).astype(np.int32)
-        col = rng.randint(0, ncol, size=nnz).astype(np.int32)
-        val = rng.uniform(-1, 1, size=nnz)
-        x = rng.uniform(0, 1, size=ncol)
+    """random matrices (cases.live_matrices), oracle vs the reference's own compiled code, bit for bit: against its answers
+    stored in tests/golden/live.npz (make_golden.py) and, where oracle/_ref is built, against the library itself"""
+    orc = ol.load_oracle()
+    g = golden("live")
+    ref = ol.load_ref() if ol.ref_available() else None
+    for i, (nrow, ncol, row, col, val, x) in enumerate(cases.live_matrices()):
         rp, cc, cv = ol.coo_to_csr(orc, nrow, row, col, val)
-        rrp, rcc, rcv = np.zeros(nrow + 1, np.int32), np.zeros(nnz, np.int32), np.zeros(nnz)
-        ref.ref_coo_to_csr(nrow, ncol, nnz, p(row), p(col), p(val), p(rrp), p(rcc), p(rcv))
-        assert np.array_equal(rp, rrp) and np.array_equal(cc, rcc) and np.array_equal(cv, rcv)
         k, ec, ev = ol.coo_to_ell(orc, nrow, row, col, val)
-        assert k == ref.ref_coo_to_ell(nrow, ncol, nnz, p(row), p(col), p(val), None, None)
-        a, b = np.zeros(nrow), np.zeros(nrow)
-        ol.coo_spmv(orc, row, col, val, x, a)
-        ref.ref_coo_spmv(nrow, ncol, nnz, p(row), p(col), p(val), p(x), p(b))
-        assert np.array_equal(a, b)
-        a[:] = 0
-        b[:] = 0
-        ol.csr_spmv(orc, rp, cc, cv, x, a)
-        ref.ref_csr_spmv(nrow, ncol, p(rp), p(cc), p(cv), p(x), p(b))
-        assert np.array_equal(a, b)
-        a[:] = 0
-        b[:] = 0
-        ol.ell_spmv(orc, nrow, k, ec, ev, x, a)
-        ref.ref_ell_spmv(nrow, ncol, nnz, k, p(ec), p(ev), p(x), p(b))
-        assert np.array_equal(a, b)
+        ours = {"sha_csr": cases.digest(rp, cc, cv), "ell_k": k}
+        for fmt, run in (("coo", lambda y: ol.coo_spmv(orc, row, col, val, x, y)), ("csr", lambda y: ol.csr_spmv(orc, rp, cc, cv, x, y)),
+                         ("ell", lambda y: ol.ell_spmv(orc, nrow, k, ec, ev, x, y))):
+            y = np.zeros(nrow)
+            run(y)
+            ours[f"y_{fmt}"] = y
         n = min(nrow, ncol)
-        assert ol.dot(orc, x[:n], x[:n]) == ref.ref_dot(n, p(x[:n].copy()), p(x[:n].copy()))
+        ours["dot"] = ol.dot(orc, x[:n], x[:n])
+        theirs = {"golden": {key: g[f"{key}{i}"] for key in ours}}
+        if ref is not None:
+            theirs["live"] = ol.ref_live_outputs(ref, nrow, ncol, row, col, val, x)
+        for src, want in theirs.items():
+            for key, v in ours.items():
+                assert np.array_equal(v, want[key]), (src, (nrow, ncol, len(val)), key)
 
 
 def test_first_touch_copy_of_the_cpu_baseline_is_a_faithful_copy(orc):
