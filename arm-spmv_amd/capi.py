@@ -92,6 +92,8 @@ SIGNATURES = {
     "spmv_mat_device_ptrs": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "spmv_apply": (C.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_apply_timed": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _f64p]),
+    "spmv_apply_multi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32]),
+    "spmv_apply_multi_timed": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _f64p]),
     "spmv_dot": (C.c_int, [_vp, _vp, _vp, _f64p]),
     "spmv_axpby": (C.c_int, [_vp, C.c_double, _vp, C.c_double, _vp, _vp]),
     "spmv_apply_dot": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, _f64p]),
@@ -372,6 +374,18 @@ class Context:
     def apply_timed(self, A: "Matrix", x: "Vector", y: "Vector", reps: int) -> float:
         ms = C.c_double(0.0)
         _check(self._lib.spmv_apply_timed(self.h, A.h, x.h, y.h, reps, C.byref(ms)))
+        return ms.value
+
+    def apply_multi(self, A: "Matrix", X: "Vector", Y: "Vector", k: int, overwrite: bool = False) -> None:
+        """Y += A*X (Y = A*X with overwrite) for k vectors at once, asynchronous.  X and Y are row-major (ncol, k) and (nrow, k):
+        Vectors of ncol*k and nrow*k entries, e.g. wrap_vector of C-contiguous torch tensors.  CSR and ELL handles; column c of Y
+        is bit-identical to the oracle's fma flavour on column c of X"""
+        _check(self._lib.spmv_apply_multi(self.h, A.h, k, X.h, Y.h, 1 if overwrite else 0))
+
+    def apply_multi_timed(self, A: "Matrix", X: "Vector", Y: "Vector", k: int, reps: int, overwrite: bool = False) -> float:
+        """`reps` back-to-back apply_multi between two device events; mean milliseconds per product"""
+        ms = C.c_double(0.0)
+        _check(self._lib.spmv_apply_multi_timed(self.h, A.h, k, X.h, Y.h, 1 if overwrite else 0, reps, C.byref(ms)))
         return ms.value
 
     def dot(self, x: "Vector", y: "Vector") -> float:

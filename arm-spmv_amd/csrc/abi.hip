@@ -1289,6 +1289,50 @@ int spmv_apply_timed(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_v
     return SPMV_OK;
 }
 
+// ---- several vectors at once: Y += A*X, X and Y row-major (kernels_spmm.hip) --------------------------------
+// Every check is made before the device is touched, so that they hold (and are tested) on a machine without one.
+static int check_apply_multi_args(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* X, spmv_vec* Y)
+{
+    SPMV_REQUIRE(ctx && A && X && Y, "spmv_apply_multi: null argument");
+    SPMV_REQUIRE(k >= 1 && k <= 64, "spmv_apply_multi: k = %d, must be in [1, 64]", k);
+    SPMV_REQUIRE(X->n == (int64_t)A->ncol * k, "spmv_apply_multi: X has %lld entries, ncol * k = %d * %d", (long long)X->n,
+                 A->ncol, k);
+    SPMV_REQUIRE(Y->n == (int64_t)A->nrow * k, "spmv_apply_multi: Y has %lld entries, nrow * k = %d * %d", (long long)Y->n,
+                 A->nrow, k);
+    SPMV_REQUIRE(X->n == 0 || Y->n == 0 || X->d + X->n <= Y->d || Y->d + Y->n <= X->d,
+                 "spmv_apply_multi: X and Y must not overlap");
+    if (A->format != SPMV_FMT_CSR && A->format != SPMV_FMT_ELL)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_apply_multi: CSR and ELL handles only (format %d)", A->format);
+    // the product reads the handle's own arrays: a CSR handle that released them (panel_keep_csr = 0) is refused here, on the host
+    const int64_t entries = A->format == SPMV_FMT_CSR ? A->nnz : (int64_t)A->nrow * A->k;
+    SPMV_REQUIRE(entries == 0 || (A->b && A->v),
+                 "spmv_apply_multi: this handle gave up its CSR arrays (panel_keep_csr = 0)");
+    return SPMV_OK;
+}
+
+int spmv_apply_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* X, spmv_vec* Y, int32_t overwrite)
+{
+    SPMV_TRY(check_apply_multi_args(ctx, A, k, X, Y));
+    SPMV_TRY(use_device(ctx));
+    return spmm_apply(ctx, A, k, X->d, Y->d, overwrite != 0);
+}
+
+int spmv_apply_multi_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* X, spmv_vec* Y, int32_t overwrite,
+                           int32_t reps, double* ms_per_apply)
+{
+    SPMV_TRY(check_apply_multi_args(ctx, A, k, X, Y));
+    SPMV_REQUIRE(reps > 0 && ms_per_apply, "spmv_apply_multi_timed: reps=%d", reps);
+    SPMV_TRY(use_device(ctx));
+    SPMV_HIP(hipEventRecord(ctx->ev_begin, ctx->stream));
+    for (int32_t i = 0; i < reps; ++i) SPMV_TRY(spmm_apply(ctx, A, k, X->d, Y->d, overwrite != 0));
+    SPMV_HIP(hipEventRecord(ctx->ev_end, ctx->stream));
+    SPMV_HIP(hipEventSynchronize(ctx->ev_end));
+    float ms = 0.f;
+    SPMV_HIP(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+    *ms_per_apply = (double)ms / reps;
+    return SPMV_OK;
+}
+
 // ---- the reference's own call shape: host vectors in, host vector out ---------------------------------------------------------
 // CSRMatrixMatVector(A, x, y) and its siblings take HOST vectors on every call (include/mat_vec.h:7-11; main.cpp:56-59 calls
 // them 50 times).  Behind that signature a product costs two hand-overs whatever the kernel does; for small matrices they ARE the

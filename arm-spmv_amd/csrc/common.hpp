@@ -447,6 +447,8 @@ void csr_split_free(spmv_mat* m);
 int  csr_split_threshold(const spmv_mat* m);
 int  csr_split_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int  csr_split_long_rows_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
+// kernels_spmm.hip: Y += A*X (Y = A*X) for k row-major vectors, CSR and ELL handles, over the handle's own arrays
+int spmm_apply(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* X, double* Y, bool overwrite);
 // kernels_misc.hip (CSC, DIA, BLAS-1, fill)
 int csc_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int csc_analyse(spmv_mat* m);

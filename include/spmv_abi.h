@@ -405,6 +405,36 @@ int spmv_apply(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y)
 int spmv_apply_timed(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y, int32_t reps,
                      double* ms_per_apply);
 
+/* ---- several vectors at once: Y += A*X  (not in the reference's API) ----------------------------------------------------------
+ * Y += A*X (overwrite != 0: Y = A*X) for k vectors at once.  X holds ncol*k entries, Y nrow*k (the shard's rows), both ROW-MAJOR:
+ * entry (j, c) of X at X[(int64)j*k + c] - a C-contiguous torch (ncol, k) tensor wrapped with spmv_vec_wrap_device is this layout.
+ * 1 <= k <= 64.  CSR handles (uploaded, wrapped, shards) and ELL handles; COO / CSC / DIA: SPMV_ERR_UNSUPPORTED.  Asynchronous.
+ * Every argument is checked before the device is touched: a null pointer, k out of range, X with other than ncol*k or Y with other
+ * than nrow*k entries, X and Y overlapping, a CSR handle without its arrays (panel_keep_csr = 0): SPMV_ERR_INVALID.  Index arithmetic on X and Y is 64-bit (ncol*k passes 2^31 at 34M
+ * columns and k = 64).
+ * Order of the additions (the contract): column c of Y is BIT-IDENTICAL to the oracle's fma flavour on column c of X -
+ *   CSR  a row's sum runs left to right from 0.0 with fma, then y += sum (y = sum with overwrite): the SCALAR kernel's order;
+ *   ELL  the accumulator starts at y (0.0 with overwrite) and goes slot after slot; padding slots contribute 0.0 * X[pad col, c]
+ *        (column 0 in the reference's layout) as spmv_apply on a true ELL handle does.
+ *   So the product is deterministic, and k = 1 gives the bits of SPMV_CSR_SCALAR, which may differ in the last bits from what
+ *   AUTO picked for spmv_apply on the same handle.
+ * The product reads only the handle's own arrays (row_ptr / col_ind / values; ELL col_ind / values).  It deliberately ignores the
+ * kernel AUTO or spmv_mat_set_kernel chose, the copies and layouts made for it (ELL copy, split, panel layout, row-grouped copy)
+ * and the plan, and changes none of them: a handle's plan stays canonical whether or not it was used here.
+ * Kernel (kernels_spmm.hip): a group of lanes owns one row and lane t one column of a tile of T = the next power of two >= k, at
+ * most 16, columns; a larger k runs ceil(k / 16) column tiles, each re-reading the matrix (from the caches where it can).
+ * SPMV_SPMM_LANES=32 or 64 (environment, read once per process at the first call; an A/B switch; other values are ignored) lets
+ * one group cover up to that many columns instead.
+ * A CSR handle that released its arrays (spmv_mat_set_param "panel_keep_csr" 0) has nothing this product can read: SPMV_ERR_INVALID.
+ * Limitation: a row's entries form ONE chain of fmas per column, so a very long row runs on one lane group, in series: the arrow
+ * matrix of 1M rows (one row of 1M entries) takes 90-98 ms per product at k = 1-32, against 0.02-0.66 ms for k spmv_apply calls
+ * (DESIGN.md 9).  Splitting long rows would break the bit-identity. */
+int spmv_apply_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* X, spmv_vec* Y, int32_t overwrite);
+/* `reps` back-to-back spmv_apply_multi between two HIP events on the context's stream; the mean milliseconds per product.
+ * Synchronous. */
+int spmv_apply_multi_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* X, spmv_vec* Y, int32_t overwrite,
+                           int32_t reps, double* ms_per_apply);
+
 /* y_host += A * x_host with the caller's HOST vectors, synchronous - the reference's own call shape (include/mat_vec.h:7-11:
  * every CSRMatrixMatVector(A, x, y) hands over host arrays; main.cpp:56-59 does it 50 times), as ONE entry point so that the
  * hand-over can be done the cheapest way for its size.  Vectors of up to 1 MB together: x by CPU stores straight into device
