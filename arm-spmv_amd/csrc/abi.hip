@@ -93,7 +93,7 @@ void mat_free(spmv_mat* m)
     csr_split_free(m);
     csr_ell_copy_free(m);
     symgs_free(m);
-    if (m->coo_csr) mat_free(m->coo_csr);
+    if (m->rowgrouped) mat_free(m->rowgrouped);
     coo_free_bins(m);
     delete m;
 }
@@ -176,15 +176,15 @@ bool adds_into_y_with_atomics(const spmv_mat* A)
     {
         case SPMV_FMT_COO:
         case SPMV_FMT_CSC:
-            return A->coo_csr && A->kernel == SPMV_CSR_PANEL ? adds_into_y_with_atomics(A->coo_csr) : true;
-        case SPMV_FMT_ELL: return A->coo_csr && A->kernel == SPMV_CSR_PANEL ? adds_into_y_with_atomics(A->coo_csr) : false;
+            return runs_from_rowgrouped(A) ? adds_into_y_with_atomics(A->rowgrouped) : true;
+        case SPMV_FMT_ELL: return runs_from_rowgrouped(A) ? adds_into_y_with_atomics(A->rowgrouped) : false;
         case SPMV_FMT_CSR:
             switch (A->kernel)
             {
                 case SPMV_CSR_SEGSCAN: return true;
                 case SPMV_CSR_SPLIT:
                     // the short rows' copy picks a kernel of its own; long rows: chunks add atomically, virtual rows do not
-                    return adds_into_y_with_atomics(A->coo_csr) || (!A->split_long && A->split_nchunks > 0);
+                    return adds_into_y_with_atomics(A->split_short) || (!A->split_long && A->split_nchunks > 0);
                 case SPMV_CSR_ELL: return adds_into_y_with_atomics(A->ell_copy);
                 default: return false;
             }
@@ -743,6 +743,18 @@ int spmv_mat_get_info(const spmv_mat* m, spmv_mat_info* info)
     return SPMV_OK;
 }
 
+// a CSR handle holds the layout of its own that `kernel` multiplies from (kernel_reads_own_layout: the others have none)
+static bool own_layout_built(const spmv_mat* m, int32_t kernel)
+{
+    switch (kernel)
+    {
+        case SPMV_CSR_PANEL: return m->pb_val;
+        case SPMV_CSR_TWOPHASE: return m->tp_val;
+        case SPMV_CSR_ELL: return m->ell_copy;
+        default: return false;
+    }
+}
+
 int spmv_mat_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes_per_row)
 {
     SPMV_REQUIRE(m, "null matrix");
@@ -751,86 +763,10 @@ int spmv_mat_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes_per_row)
                                         (lanes_per_row & (lanes_per_row - 1)) == 0),
                  "lanes_per_row must be 0 or a power of two in 1..64, got %d", lanes_per_row);
     if (lanes_per_row > 0) m->lanes_per_row = lanes_per_row;
-    if (m->format == SPMV_FMT_COO)
-    {
-        // COO: AUTO = panel layout when it pays, VECTOR = the segmented scan, PANEL = build the panel layout now
-        SPMV_REQUIRE(kernel == SPMV_CSR_AUTO || kernel == SPMV_CSR_VECTOR || kernel == SPMV_CSR_PANEL,
-                     "COO handles take kernel AUTO (0), VECTOR (1: segmented scan) or PANEL (4), got %d", kernel);
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        m->kernel_forced = kernel != SPMV_CSR_AUTO;
-        if (kernel == SPMV_CSR_VECTOR)
-        {
-            // the scan runs over a copy of the entries in column bins when x is beyond an XCD's L2 ("coo_column_bins" = 0 drops it)
-            m->kernel = SPMV_CSR_VECTOR;
-            if (!m->cb_bins)
-            {
-                const int rc = coo_build_bins(m, 0, /*only_if_worth=*/true);
-                if (rc != SPMV_OK && rc != SPMV_ERR_ALLOC) return rc;  // (no room for the copy: the scan runs over the handle's own arrays)
-                (void)hipGetLastError();
-            }
-        }
-        else
-        {
-            if (kernel == SPMV_CSR_AUTO)
-                SPMV_TRY(coo_select_kernel(m));  // the scan or the row-grouped copy, timed (select.hip)
-            else
-                SPMV_TRY(coo_build_panel(m, /*only_if_worth=*/false));
-            m->kernel = m->coo_csr ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
-            if (m->kernel == SPMV_CSR_PANEL)
-            {
-                SPMV_HIP(hipStreamSynchronize(m->ctx->stream));
-                coo_free_bins(m);
-            }
-        }
-        return SPMV_OK;
-    }
-    if (m->format == SPMV_FMT_CSC)
-    {
-        // CSC: AUTO = the scatter or the row-grouped copy, timed; VECTOR = the scatter over the columns; PANEL = regroup now, panel layout
-        SPMV_REQUIRE(kernel == SPMV_CSR_AUTO || kernel == SPMV_CSR_VECTOR || kernel == SPMV_CSR_PANEL,
-                     "CSC handles take kernel AUTO (0), VECTOR (1: scatter over the columns) or PANEL (4), got %d", kernel);
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        m->kernel_forced = kernel != SPMV_CSR_AUTO;
-        if (kernel == SPMV_CSR_VECTOR)
-            m->kernel = SPMV_CSR_VECTOR;
-        else if (kernel == SPMV_CSR_AUTO)
-            SPMV_TRY(csc_select_kernel(m));
-        else
-        {
-            SPMV_TRY(csc_build_rowgrouped(m, SPMV_CSR_PANEL));
-            m->kernel = m->coo_csr ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
-        }
-        return SPMV_OK;
-    }
-    if (m->format == SPMV_FMT_ELL)
-    {
-        // ELL: AUTO = panel layout when the columns are scattered, VECTOR = one lane per row, PANEL = build it now
-        SPMV_REQUIRE(kernel == SPMV_CSR_AUTO || kernel == SPMV_CSR_VECTOR || kernel == SPMV_CSR_PANEL,
-                     "ELL handles take kernel AUTO (0), VECTOR (1: one lane per row) or PANEL (4), got %d", kernel);
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        m->kernel_forced = kernel != SPMV_CSR_AUTO;
-        if (kernel == SPMV_CSR_VECTOR)
-        {
-            m->kernel      = SPMV_CSR_VECTOR;
-            m->ell_variant = 0;  // lanes_per_row (below) picks the variant of the format's own kernel
-            if (m->ell_dia_order_req < 0 && m->ell_rval)
-            {
-                SPMV_HIP(hipStreamSynchronize(m->ctx->stream));
-                ell_free_dia_order(m);  // (a DIA-order copy the trial had kept: 8 bytes per slot nobody multiplies from now)
-            }
-        }
-        else if (kernel == SPMV_CSR_AUTO)
-            SPMV_TRY(ell_select_kernel(m));  // the format's own kernels and, where it is a candidate, the row-grouped copy: timed
-        else
-        {
-            SPMV_TRY(ell_build_panel(m, /*only_if_worth=*/false));
-            m->kernel = m->coo_csr ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
-        }
-        return SPMV_OK;
-    }
+    // COO, CSC, ELL: the format's own kernel or the row-grouped copy (rowgrouped.hip)
+    if (m->format == SPMV_FMT_COO || m->format == SPMV_FMT_CSC || m->format == SPMV_FMT_ELL) return rowgrouped_set_kernel(m, kernel);
     if (m->format == SPMV_FMT_CSR && m->nnz > 0 && (!m->b || !m->v))
-        SPMV_REQUIRE((kernel == SPMV_CSR_PANEL && m->pb_val) || (kernel == SPMV_CSR_TWOPHASE && m->tp_val) || (kernel == SPMV_CSR_ELL && m->ell_copy) ||
-                         (kernel == SPMV_CSR_AUTO && (m->kernel == SPMV_CSR_PANEL || m->kernel == SPMV_CSR_TWOPHASE || m->kernel == SPMV_CSR_ELL)),
+        SPMV_REQUIRE(own_layout_built(m, kernel) || (kernel == SPMV_CSR_AUTO && kernel_reads_own_layout(m->kernel)),
                      "this handle gave up its CSR arrays (panel_keep_csr = 0): only the product it was built for is left");
     if (kernel == SPMV_CSR_AUTO)
     {
@@ -924,9 +860,7 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
         SPMV_REQUIRE(value == 0 || (m->b && m->v) || m->nnz == 0, "panel_keep_csr: the arrays are gone already");
         if (value == 0 && m->b && m->v)
         {
-            SPMV_REQUIRE(m->format == SPMV_FMT_CSR && m->owned &&
-                             ((m->kernel == SPMV_CSR_PANEL && m->pb_val) || (m->kernel == SPMV_CSR_TWOPHASE && m->tp_val) ||
-                              (m->kernel == SPMV_CSR_ELL && m->ell_copy)),
+            SPMV_REQUIRE(m->format == SPMV_FMT_CSR && m->owned && own_layout_built(m, m->kernel),
                          "panel_keep_csr = 0 needs an owned CSR handle whose panel or two-phase layout or ELL copy is built");
             SPMV_HIP(hipSetDevice(m->ctx->device));
             SPMV_HIP(hipStreamSynchronize(m->ctx->stream));
@@ -964,7 +898,7 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
         if (value == 1)
         {
             SPMV_TRY(ell_build_dia_order(m, /*only_if_worth=*/false));
-            if (m->coo_csr && m->kernel == SPMV_CSR_PANEL) m->kernel = SPMV_CSR_VECTOR;  // (the format's own kernel runs: this variant of it)
+            if (runs_from_rowgrouped(m)) m->kernel = SPMV_CSR_VECTOR;  // (the format's own kernel runs: this variant of it)
             m->ell_variant = 3;
         }
         else
@@ -1165,7 +1099,7 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         *value = (int64_t)(m->sel_us[slot] + 0.5f);
     }
     else if (!strcmp(name, "rowgrouped_kernel"))
-        *value = m->coo_csr && m->kernel == SPMV_CSR_PANEL ? m->coo_csr->kernel : 0;
+        *value = runs_from_rowgrouped(m) ? m->rowgrouped->kernel : 0;
     else if (!strcmp(name, "ell_variant"))
         *value = m->ell_variant;
     else if (!strcmp(name, "panel_rounds"))
@@ -1197,7 +1131,7 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
     else if (!strcmp(name, "adds_into_y_with_atomics"))  // 1: the product adds into y with device atomics (spmv_apply_host stages y in device memory)
         *value = adds_into_y_with_atomics(m) ? 1 : 0;
     else if (!strcmp(name, "split_inner_kernel"))
-        *value = m->format == SPMV_FMT_CSR && m->kernel == SPMV_CSR_SPLIT && m->coo_csr ? m->coo_csr->kernel : 0;
+        *value = m->format == SPMV_FMT_CSR && m->kernel == SPMV_CSR_SPLIT && m->split_short ? m->split_short->kernel : 0;
     else
         SPMV_FAIL(SPMV_ERR_INVALID, "unknown parameter '%s'", name);
     return SPMV_OK;
@@ -1441,7 +1375,7 @@ int spmv_apply_host(spmv_ctx* ctx, const spmv_mat* A, const double* x_host, doub
         //     bit for bit what the kernel would have stored, one memcpy and one crossing of the host link less.  Kernels whose
         //     accumulator starts AT y_i (ELL, DIA, scalar CSR: the reference's order y0 + p0 + p1 + ...) keep y in place.
         const spmv_mat* K = A;  // the handle whose kernel runs
-        while (K->format != SPMV_FMT_CSR && K->coo_csr && K->kernel == SPMV_CSR_PANEL) K = K->coo_csr;
+        while (runs_from_rowgrouped(K)) K = K->rowgrouped;
         const bool sum_then_add = y_in_place && !kForceInPlace && K->format == SPMV_FMT_CSR && K->nnz > 0 &&
                                   (K->kernel == SPMV_CSR_VECTOR || K->kernel == SPMV_CSR_AUTO || K->kernel == SPMV_CSR_PANEL || K->kernel == SPMV_CSR_TWOPHASE);
         if (nx && !ctx->large_bar) memcpy(hx, x_host, sizeof(double) * nx);

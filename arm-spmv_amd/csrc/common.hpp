@@ -287,7 +287,7 @@ struct spmv_mat
     bool      sel_no_ell = false;  // the handle is itself somebody's copy whose source is an ELL handle
     bool      sel_no_rowgrouped = false;  // ELL: the handle is the ELL copy of a CSR handle (no row-grouped copy of the copy)
 
-    // CSR long-row split (kernels_csr_split.hip): the long rows in chunks over the handle's own arrays, the others in `coo_csr`
+    // CSR long-row split (kernels_csr_split.hip): the long rows in chunks over the handle's own arrays, the others in `split_short`
     int32_t* split_chunks = nullptr;      // [3 * nchunks] row | first entry | end, per chunk of a long row
     int32_t  split_nchunks = 0;
     int32_t  split_threshold = 0;         // rows of this many entries and more are long (0: max(4096, longest / 16))
@@ -300,6 +300,7 @@ struct spmv_mat
     int32_t  split_built_mode = 0;         // the mode in effect (1 or 2)
     int32_t  split_built_for_mode = 0;     // the "split_mode" request the split in memory was built under
     spmv_mat* split_long = nullptr;       // mode 2: the virtual rows (a CSR handle with a kernel of its own); owned
+    spmv_mat* split_short = nullptr;      // the copy without the long rows (a CSR handle with a kernel of its own); owned
     double*  split_yl = nullptr;          // mode 2: [split_vrows] the virtual rows' sums of one product
     int32_t* split_rows = nullptr;        // mode 2: [4 * long rows] row | first entry | virtual rows V | first virtual row
     int32_t  split_vrows = 0;
@@ -325,9 +326,8 @@ struct spmv_mat
     int32_t             ell_dia_order_req = -1;  // "ell_dia_order": -1 a candidate of the trial, 0 never, 1 built and used
     bool                ell_pad_marked = false;  // the ELL COPY of a CSR handle: padding slots carry a negative column and take no part in the sums (kernels_ell.hip: MASKED)
 
-    // COO / CSC / ELL: internal row-grouped copy in the panel layout (coo_build_panel, csc_analyse, ell_build_panel); owned.
-    // CSR with kernel SPLIT: the copy without the long rows
-    spmv_mat* coo_csr = nullptr;
+    // COO / CSC / ELL: the entries grouped by row, an internal CSR handle with a kernel of its own (rowgrouped.hip); owned
+    spmv_mat* rowgrouped = nullptr;
 
     // COO: copy of the entries in column bins, one run of bins per XCD, for the segmented scan (kernels_coo.hip:
     // coo_build_bins); bins start on workgroup chunks, the padding carries row INT32_MAX
@@ -353,6 +353,10 @@ namespace spmv
 {
 // a launch holds fewer than 2^32 work-items: beyond that the grid wraps around without an error
 inline bool launch_fits(int64_t items, int lanes_per_item) { return items * lanes_per_item < ((int64_t)1 << 32) - 4096; }
+// a COO, CSC or ELL handle whose product runs from its row-grouped copy (reported as kernel PANEL)
+inline bool runs_from_rowgrouped(const spmv_mat* m) { return m->format != SPMV_FMT_CSR && m->rowgrouped && m->kernel == SPMV_CSR_PANEL; }
+// a CSR kernel that reads row_ptr and a layout of its own only, not col_ind / values (the panel and two-phase layouts, the ELL copy)
+inline bool kernel_reads_own_layout(int32_t kernel) { return kernel == SPMV_CSR_PANEL || kernel == SPMV_CSR_TWOPHASE || kernel == SPMV_CSR_ELL; }
 int ensure_scratch(spmv_ctx* ctx, size_t bytes);
 
 // kernels_csr.hip
@@ -421,8 +425,8 @@ int csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 // kernels_ell.hip
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int ell_analyse(spmv_mat* m);
-int ell_build_panel(spmv_mat* m, bool only_if_worth);  // the row-grouped copy with the PANEL kernel forced on it
 int ell_select_kernel(spmv_mat* m);                    // AUTO: the format's own variants and (where a candidate) the row-grouped copy, timed
+int ell_rowgrouped_copy(spmv_mat* m, int32_t force_kernel, spmv_mat** out);  // the row-grouped copy's CSR handle (rowgrouped_build)
 int  csr_ell_copy_build(spmv_mat* m);  // SPMV_CSR_ELL: the ELL copy of a CSR handle with (nearly) equal rows
 void csr_ell_copy_free(spmv_mat* m);
 bool csr_ell_copy_worth(const spmv_mat* m);
@@ -432,9 +436,7 @@ void ell_free_tiles(spmv_mat* m);
 int  ell_build_dia_order(spmv_mat* m, bool only_if_worth);  // the DIA-order copy of the values (ell_variant 3)
 void ell_free_dia_order(spmv_mat* m);
 int coo_analyse(spmv_mat* m);
-int coo_build_panel(spmv_mat* m, bool only_if_worth);  // the row-grouped copy with the PANEL kernel forced on it
 int coo_select_kernel(spmv_mat* m);                    // AUTO: the segmented scan or the row-grouped copy (which picks its own kernel), timed
-void coo_drop_rowgrouped(spmv_mat* m);
 int  coo_build_bins(spmv_mat* m, int bins_per_xcd, bool only_if_worth);  // bins_per_xcd 0: as many as keep a slice of x inside an XCD's L2
 void coo_free_bins(spmv_mat* m);
 int coo_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
@@ -453,8 +455,7 @@ int spmm_apply(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* X, dou
 int csc_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int csc_analyse(spmv_mat* m);
 int csc_select_kernel(spmv_mat* m);                       // AUTO: the scatter or the row-grouped copy (which picks its own kernel), timed
-int csc_build_rowgrouped(spmv_mat* m, int32_t force_kernel);
-void csc_drop_rowgrouped(spmv_mat* m);
+int csc_rowgrouped_copy(spmv_mat* m, int32_t force_kernel, spmv_mat** out);  // the row-grouped copy's CSR handle (rowgrouped_build)
 int dia_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int dia_rows_apply(spmv_ctx* ctx, int nrow, int jmax, int k, const int32_t* offsets, const double* values, const double* x, double* y, bool off_known,
                    int off_min, int off_max, uint32_t flags, const unsigned long long* skip_rows, int stride);
@@ -505,13 +506,21 @@ inline void plan_hand_down(const spmv_mat* parent, spmv_mat* child, plan_child w
     child->plan_base = at >= 0 ? parent->plan_base : nullptr;
     child->plan_at   = at;
 }
-bool plan_take_armed(spmv_mat* m);   // a handle under analysis takes the context's armed plan (if its format is the plan's); true: it did
+// a handle under analysis applies its plan: the node handed down to it, else the context's armed plan (if its format is the
+// plan's).  true: the plan decided, *rc says how; false: no plan, or a context's plan that does not fit this matrix (the handle selects)
+bool plan_analyse(spmv_mat* m, int* rc);
 void plan_clear(spmv_mat* m);
 int  csr_apply_plan(spmv_mat* m);    // select.hip
 void plan_reset_requests(spmv_mat* m);  // the parameters a plan sets explicitly, back to "choose" (a plan that did not fit)
 int  ell_apply_plan(spmv_mat* m);    // kernels_ell.hip
 int  coo_apply_plan(spmv_mat* m);    // kernels_coo.hip
 int  csc_apply_plan(spmv_mat* m);    // kernels_misc.hip
+// rowgrouped.hip: the row-grouped copy of a COO, CSC or ELL handle
+void rowgrouped_drop(spmv_mat* m);
+void release_unread_csr_arrays(spmv_mat* csr);  // a CSR handle whose kernel reads only its own layout gives col_ind / values back
+int  rowgrouped_build(spmv_mat* m, int32_t force_kernel);  // reuse, size limit, drop, produce, release, adopt
+int  rowgrouped_select(spmv_mat* m, int (*trial)(spmv_mat* m, const select_scratch& sv, bool model_copy, float* t_copy, float* t_own));  // COO, CSC AUTO
+int  rowgrouped_set_kernel(spmv_mat* m, int32_t kernel);  // spmv_mat_set_kernel on a COO, CSC or ELL handle
 // abi.hip helpers used by the other units
 int  mat_alloc(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t nnz, int32_t k,
                size_t a_count, size_t b_count, size_t v_count, spmv_mat** out);

@@ -290,96 +290,37 @@ int coo_analyse(spmv_mat* m)
     SPMV_HIP(hipStreamSynchronize(ctx->stream));
     m->sorted_rows = unsorted ? 0 : 1;
     m->kernel      = SPMV_CSR_VECTOR;  // reported for COO as "segmented scan"
-    const bool from_ctx = plan_take_armed(m);
-    if (plan_of(m))
-    {
-        const int rc = coo_apply_plan(m);
-        plan_clear(m);
-        if (rc == SPMV_OK || !from_ctx) return rc;
-        (void)hipGetLastError();  // (a context's plan that does not fit this matrix: the handle selects by itself)
-    }
+    int rc;
+    if (plan_analyse(m, &rc)) return rc;
     if (!m->kernel_forced) SPMV_TRY(coo_select_kernel(m));
     return SPMV_OK;
 }
 
-void coo_drop_rowgrouped(spmv_mat* m)
-{
-    if (!m->coo_csr) return;
-    (void)hipStreamSynchronize(m->ctx->stream);
-    m->device_bytes -= m->coo_csr->device_bytes;
-    mat_free(m->coo_csr);
-    m->coo_csr = nullptr;
-    if (m->kernel == SPMV_CSR_PANEL) m->kernel = SPMV_CSR_VECTOR;
-}
-
 namespace
 {
-// adopts a CSR handle as the row-grouped copy; the layouts that do not read col_ind / values give them back
-void adopt_rowgrouped(spmv_mat* m, spmv_mat* csr)
-{
-    if ((csr->kernel == SPMV_CSR_PANEL || csr->kernel == SPMV_CSR_TWOPHASE || csr->kernel == SPMV_CSR_ELL) && csr->b && csr->v && csr->owned)
-    {
-        (void)hipFree(const_cast<int32_t*>(csr->b));
-        (void)hipFree(const_cast<double*>(csr->v));
-        csr->device_bytes -= (int64_t)csr->nnz * 12;
-        csr->b = nullptr;
-        csr->v = nullptr;
-    }
-    m->coo_csr = csr;
-    m->kernel  = SPMV_CSR_PANEL;  // reported for COO as "runs from the row-grouped copy" (whichever CSR kernel that copy picked)
-    m->device_bytes += csr->device_bytes;
-}
 int coo_scan_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
-}  // namespace
 
-// AUTO for a COO handle: the segmented scan over the entries as they are, or a copy grouped by row (spmv_coo_to_csr: duplicates
-// and the order inside a row kept) which picks ITS kernel like any CSR handle - row-parallel, LDS window, panel, two-phase
-// (select.hip).  Model: the copy from 1.5M entries on (C4: 0.28 ms against 1.81 for the scan in place).  From 64K entries on
-// both are timed (tools/sweep_structures.py: below 2M entries the copy won 2x on every family but one - an R-MAT graph
-// with a hub row, where the scan won 1.7x; above, the scan won 6-15 % on dense blocks and wide rectangles).
-int coo_select_kernel(spmv_mat* m)
+// the trial of coo_select_kernel (rowgrouped_select: the row-grouped copy, if any, is built): the scan and the copy timed in rounds -
+// the model's pick first - until their minima stand still, then the scan over column bins where it may beat both
+int coo_trial(spmv_mat* m, const select_scratch& sv, bool model_copy, float* t_copy_out, float* t_own_out)
 {
-    spmv_ctx* ctx = m->ctx;
-    select_reset(m);
-    coo_drop_rowgrouped(m);
-    (void)hipStreamSynchronize(ctx->stream);
-    coo_free_bins(m);
-    m->kernel = SPMV_CSR_VECTOR;
-    if (m->nnz == 0 || m->nrow <= 0 || m->nnz > (int64_t)INT32_MAX - 65536) return SPMV_OK;
-    const bool model_copy = m->nnz >= ((int64_t)3 << 19);
-    auto       build_copy = [&]() -> int {
-        spmv_mat* csr = nullptr;
-        const int rc  = coo_to_csr(ctx, m, &csr, kCsrAutoNoSegscan);  // (csr_analyse inside selects the copy's kernel)
-        if (rc == SPMV_OK) adopt_rowgrouped(m, csr);
-        return rc;
-    };
-    if (!select_trials_enabled(m) || m->nnz < kSelectMinNnz) return model_copy ? build_copy() : SPMV_OK;
-    select_scratch sv;
-    if (sv.alloc(ctx, m->ncol, m->nrow) != SPMV_OK) return model_copy ? build_copy() : SPMV_OK;
-    // the copy is built first, then the two are timed in rounds - the model's pick first - until their minima stand still
-    // (select.hip: no allocation between two timings)
-    int rc = build_copy();
-    if (rc == SPMV_ERR_ALLOC && !model_copy)
-    {
-        (void)hipGetLastError();
-        rc = SPMV_OK;  // no memory for the copy: the scan runs
-    }
-    if (rc != SPMV_OK) return rc;
-    float t_scan = 1e30f, t_copy = 1e30f;
+    spmv_ctx* ctx    = m->ctx;
+    float     t_scan = 1e30f, t_copy = 1e30f;
+    int       rc;
     {
         // candidate 0 is the model's pick; without a copy the scan is timed alone (its figure is reported)
-        const bool copy_first = model_copy && m->coo_csr;
+        const bool copy_first = model_copy && m->rowgrouped;
         float      t[2]       = {-1.f, -1.f};
-        const int  n          = m->coo_csr ? 2 : 1;
+        const int  n          = m->rowgrouped ? 2 : 1;
         rc = select_rounds(ctx, n,
                            [&](int j) {
-                               const bool copy = m->coo_csr && ((j == 0) == copy_first);
-                               return copy ? csr_apply(ctx, m->coo_csr, sv.x, sv.y) : coo_scan_apply(ctx, m, sv.x, sv.y);
+                               const bool copy = m->rowgrouped && ((j == 0) == copy_first);
+                               return copy ? csr_apply(ctx, m->rowgrouped, sv.x, sv.y) : coo_scan_apply(ctx, m, sv.x, sv.y);
                            },
                            t, &m->sel_rounds);
         (void)hipStreamSynchronize(ctx->stream);
         if (rc != SPMV_OK) return rc;
-        if (m->coo_csr)
+        if (m->rowgrouped)
         {
             t_copy = copy_first ? t[0] : t[1];
             t_scan = copy_first ? t[1] : t[0];
@@ -400,14 +341,14 @@ int coo_select_kernel(spmv_mat* m)
         {
             // the scan over the bins and (again, as a minimum to improve on) the copy, in rounds: the bins' first timing follows
             // their build - allocations and frees a moment ago - the later ones do not
-            float     t[2] = {-1.f, m->coo_csr && t_copy < 1e29f ? t_copy : -1.f};
-            const int n    = m->coo_csr ? 2 : 1;
-            rc = select_rounds(ctx, n, [&](int j) { return j == 0 ? coo_scan_apply(ctx, m, sv.x, sv.y) : csr_apply(ctx, m->coo_csr, sv.x, sv.y); }, t, nullptr);
+            float     t[2] = {-1.f, m->rowgrouped && t_copy < 1e29f ? t_copy : -1.f};
+            const int n    = m->rowgrouped ? 2 : 1;
+            rc = select_rounds(ctx, n, [&](int j) { return j == 0 ? coo_scan_apply(ctx, m, sv.x, sv.y) : csr_apply(ctx, m->rowgrouped, sv.x, sv.y); }, t, nullptr);
             if (rc == SPMV_OK)
             {
                 t_bins = t[0] >= 0.f ? t[0] : 1e30f;
                 if (t[0] >= 0.f) select_note(m, 6, t_bins);  // "select_us_variant1"
-                if (m->coo_csr && t[1] >= 0.f)
+                if (m->rowgrouped && t[1] >= 0.f)
                 {
                     t_copy                    = t[1];
                     m->sel_us[SPMV_CSR_PANEL] = t_copy * 1000.f;
@@ -423,13 +364,27 @@ int coo_select_kernel(spmv_mat* m)
         if (rc != SPMV_OK) return rc;
         if (!(t_bins < 0.98f * std::min(t_scan, t_copy))) coo_free_bins(m);
     }
-    const float t_own     = std::min(t_scan, m->cb_bins ? t_bins : 1e30f);
-    const bool  keep_copy = m->coo_csr && (model_copy ? t_copy <= t_own * 1.02f : t_copy < t_own * 0.98f);  // the second one has to win by 2 %
-    if (!keep_copy)
-        coo_drop_rowgrouped(m);
-    else
-        coo_free_bins(m);
-    m->kernel = m->coo_csr ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
+    *t_copy_out = t_copy;
+    *t_own_out  = std::min(t_scan, m->cb_bins ? t_bins : 1e30f);
+    return SPMV_OK;
+}
+}  // namespace
+
+// AUTO for a COO handle: the segmented scan over the entries as they are, or a copy grouped by row (spmv_coo_to_csr: duplicates
+// and the order inside a row kept) which picks ITS kernel like any CSR handle - row-parallel, LDS window, panel, two-phase
+// (select.hip).  Model: the copy from 1.5M entries on (C4: 0.28 ms against 1.81 for the scan in place).  From 64K entries on
+// both are timed (tools/sweep_structures.py: below 2M entries the copy won 2x on every family but one - an R-MAT graph
+// with a hub row, where the scan won 1.7x; above, the scan won 6-15 % on dense blocks and wide rectangles).
+int coo_select_kernel(spmv_mat* m)
+{
+    select_reset(m);
+    rowgrouped_drop(m);
+    (void)hipStreamSynchronize(m->ctx->stream);
+    coo_free_bins(m);
+    m->kernel = SPMV_CSR_VECTOR;
+    if (m->nnz == 0 || m->nrow <= 0 || m->nnz > (int64_t)INT32_MAX - 65536) return SPMV_OK;
+    SPMV_TRY(rowgrouped_select(m, coo_trial));
+    if (m->rowgrouped) coo_free_bins(m);  // (the copy runs: the bins' copy of the entries goes)
     return SPMV_OK;
 }
 
@@ -440,7 +395,7 @@ int coo_apply_plan(spmv_mat* m)
     const plan_node& p = *plan_of(m);
     spmv_ctx*        ctx = m->ctx;
     select_reset(m);
-    coo_drop_rowgrouped(m);
+    rowgrouped_drop(m);
     (void)hipStreamSynchronize(ctx->stream);
     coo_free_bins(m);
     m->kernel = SPMV_CSR_VECTOR;
@@ -448,9 +403,7 @@ int coo_apply_plan(spmv_mat* m)
     if (p.kernel == SPMV_CSR_PANEL)
     {
         SPMV_REQUIRE(m->nnz <= (int64_t)INT32_MAX - 65536, "plan: a row-grouped copy of %lld COO entries does not fit int32 offsets", (long long)m->nnz);
-        spmv_mat* csr = nullptr;
-        SPMV_TRY(coo_to_csr(ctx, m, &csr, kCsrAutoNoSegscan));  // (hands the copy's node down)
-        adopt_rowgrouped(m, csr);
+        SPMV_TRY(rowgrouped_build(m, SPMV_CSR_AUTO));  // (coo_to_csr hands the copy's node down)
     }
     else if (p.coo_bins_per_xcd > 0)
     {
@@ -458,27 +411,6 @@ int coo_apply_plan(spmv_mat* m)
         if (rc != SPMV_OK && rc != SPMV_ERR_ALLOC) return rc;  // (no room for the copy: the scan runs over the handle's own arrays)
         (void)hipGetLastError();
     }
-    return SPMV_OK;
-}
-
-// The row-grouped copy with the PANEL kernel forced on it (spmv_mat_set_kernel(coo, SPMV_CSR_PANEL), and the CSC handles'
-// regrouping, kernels_misc.hip).  Large COO with an x beyond L2 is gather-bound in entry order exactly like CSR (C4: 13 % of
-// roofline with the segmented scan in place); the entries are grouped by row on the device (spmv_coo_to_csr, duplicates and
-// file order inside a row kept) and re-ordered as in kernels_csr_panel.hip.  Only row_ptr and the panel arrays are kept.
-int coo_build_panel(spmv_mat* m, bool only_if_worth)
-{
-    if (m->coo_csr && m->coo_csr->kernel == SPMV_CSR_PANEL)
-    {
-        m->kernel = SPMV_CSR_PANEL;
-        return SPMV_OK;
-    }
-    const bool worth = m->nnz >= ((int64_t)3 << 19) && m->nrow > 0;
-    if (only_if_worth && !worth) return SPMV_OK;
-    if (m->nnz == 0 || m->nnz > (int64_t)INT32_MAX - 65536) return SPMV_OK;
-    coo_drop_rowgrouped(m);  // (a copy AUTO made with another kernel)
-    spmv_mat* csr = nullptr;
-    SPMV_TRY(coo_to_csr(m->ctx, m, &csr, SPMV_CSR_PANEL));
-    adopt_rowgrouped(m, csr);
     return SPMV_OK;
 }
 
@@ -703,7 +635,7 @@ int csr_segscan_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double*
 int coo_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
 {
     if (A->nnz == 0) return SPMV_OK;
-    if (A->coo_csr && A->kernel == SPMV_CSR_PANEL) return csr_apply(ctx, A->coo_csr, x, y);
+    if (runs_from_rowgrouped(A)) return csr_apply(ctx, A->rowgrouped, x, y);
     return coo_scan_apply(ctx, A, x, y);
 }
 

@@ -128,11 +128,11 @@ void csr_split_free(spmv_mat* m)
         m->device_bytes -= (int64_t)sizeof(int32_t) * 3 * m->split_nchunks;
         m->split_chunks = nullptr;
     }
-    if (m->coo_csr)
+    if (m->split_short)
     {
-        m->device_bytes -= m->coo_csr->device_bytes;
-        mat_free(m->coo_csr);
-        m->coo_csr = nullptr;
+        m->device_bytes -= m->split_short->device_bytes;
+        mat_free(m->split_short);
+        m->split_short = nullptr;
     }
     if (m->split_long)
     {
@@ -173,7 +173,7 @@ int csr_split_build(spmv_mat* m)
 {
     SPMV_REQUIRE(m->format == SPMV_FMT_CSR && m->a && m->b && m->v, "the long-row split is built from a CSR handle's own arrays");
     const int T = csr_split_threshold(m);
-    if (m->coo_csr && m->split_built_threshold == T && m->split_mode == m->split_built_for_mode) return SPMV_OK;  // (the request it was built for)
+    if (m->split_short && m->split_built_threshold == T && m->split_mode == m->split_built_for_mode) return SPMV_OK;  // (the request it was built for)
     (void)hipStreamSynchronize(m->ctx->stream);
     csr_split_free(m);
     spmv_ctx*   ctx = m->ctx;
@@ -303,15 +303,7 @@ int csr_split_build(spmv_mat* m)
             part->sel_no_segscan = true;  // what the scan is for went out with the long rows
             plan_hand_down(m, part, part == rest ? kPlanChildRowgrouped : kPlanChildLong);
             rc                   = csr_analyse(part);  // picks the part's kernel and builds its layout
-            // the panel and two-phase layouts read row_ptr and their own arrays only
-            if (rc == SPMV_OK && (part->kernel == SPMV_CSR_PANEL || part->kernel == SPMV_CSR_TWOPHASE || part->kernel == SPMV_CSR_ELL) && part->b && part->v && part->nnz > 0)
-            {
-                (void)hipFree(const_cast<int32_t*>(part->b));
-                (void)hipFree(const_cast<double*>(part->v));
-                part->device_bytes -= part->nnz * 12;
-                part->b = nullptr;
-                part->v = nullptr;
-            }
+            if (rc == SPMV_OK) release_unread_csr_arrays(part);
         }
     if (rc != SPMV_OK)
     {
@@ -322,7 +314,7 @@ int csr_split_build(spmv_mat* m)
         if (rc == SPMV_ERR_ALLOC) set_error("no device memory for the long-row split of %lld entries", (long long)m->nnz);
         return rc;
     }
-    m->coo_csr = rest;
+    m->split_short = rest;
     m->device_bytes += rest->device_bytes;
     if (lng)
     {
@@ -365,8 +357,8 @@ int csr_split_long_rows_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x,
 
 int csr_split_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
 {
-    if (!A->coo_csr) SPMV_FAIL(SPMV_ERR_INVALID, "long-row split selected but never built");
-    SPMV_TRY(csr_apply(ctx, A->coo_csr, x, y));
+    if (!A->split_short) SPMV_FAIL(SPMV_ERR_INVALID, "long-row split selected but never built");
+    SPMV_TRY(csr_apply(ctx, A->split_short, x, y));
     return csr_split_long_rows_apply(ctx, A, x, y);
 }
 }  // namespace spmv

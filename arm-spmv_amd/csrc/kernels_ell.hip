@@ -387,23 +387,27 @@ double ell_mean_block_span(spmv_mat* m)
     return (double)h_sum / nblk;
 }
 
-void ell_drop_rowgrouped(spmv_mat* m)
+int ell_own_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
+
+// the model's gate for the row-grouped copy (no trial; no launches but the window scan): >= 2M slots whose row blocks span more
+// than 1 MiB of an x beyond L2 get the copy with the PANEL kernel forced on it
+int ell_model_copy(spmv_mat* m)
 {
-    if (!m->coo_csr) return;
-    (void)hipStreamSynchronize(m->ctx->stream);
-    m->device_bytes -= m->coo_csr->device_bytes;
-    mat_free(m->coo_csr);
-    m->coo_csr = nullptr;
-    if (m->kernel == SPMV_CSR_PANEL) m->kernel = SPMV_CSR_VECTOR;
+    const int64_t slots = (int64_t)m->nrow * m->k;
+    if (slots < ((int64_t)2 << 20) || slots > (int64_t)INT32_MAX - 65536 || m->k < 2 || (double)m->ncol * 8.0 <= 4.0 * 1048576.0) return SPMV_OK;
+    const double span = ell_mean_block_span(m);  // how far apart are the columns of 256 consecutive rows, on average?
+    if (span < 0.0) SPMV_FAIL(SPMV_ERR_HIP, "ELL window scan failed: %s", hipGetErrorString(hipGetLastError()));
+    if (span <= 131072.0) return SPMV_OK;  // a row block's x window is at most 1 MiB: stays in L2
+    return rowgrouped_build(m, SPMV_CSR_PANEL);
 }
+}  // namespace
 
 // every slot that says something - the padding's `0.0 * x[0]` of the reference (src/mat_vec.cpp:108-117) once per row, see
-// ell_to_csr_kernel - copied row by row into a CSR handle; force_kernel AUTO: the copy picks its kernel like any CSR handle
-int ell_make_rowgrouped(spmv_mat* m, int32_t force_kernel)
+// ell_to_csr_kernel - copied row by row into a CSR handle; force_kernel AUTO: the copy picks its kernel like any CSR handle.
+// For rowgrouped_build.
+int ell_rowgrouped_copy(spmv_mat* m, int32_t force_kernel, spmv_mat** out)
 {
-    spmv_ctx*     ctx   = m->ctx;
-    SPMV_REQUIRE((int64_t)m->nrow * m->k <= (int64_t)INT32_MAX - 65536, "the row-grouped copy of an ELL handle of %d rows x %d slots: shard it (int32 offsets)",
-                 m->nrow, m->k);
+    spmv_ctx*      ctx   = m->ctx;
     spmv_mat*      csr   = nullptr;
     int32_t *      cnt = nullptr, *rp = nullptr;
     const unsigned grid = (unsigned)ceil_div((int64_t)m->nrow + 1, kBlock);
@@ -438,7 +442,6 @@ int ell_make_rowgrouped(spmv_mat* m, int32_t force_kernel)
         if (rc0 == SPMV_ERR_ALLOC) SPMV_FAIL(rc0, "no device memory for the row-grouped copy of an ELL handle (%lld slots)", (long long)((int64_t)m->nrow * m->k));
         SPMV_FAIL(rc0, "building the row-grouped copy of an ELL handle failed");
     }
-    const int64_t slots = total;  // entries of the copy (below: what its col_ind / values hold)
     int rc = hipGetLastError() == hipSuccess ? SPMV_OK : SPMV_ERR_HIP;
     if (rc == SPMV_OK)
     {
@@ -458,43 +461,8 @@ int ell_make_rowgrouped(spmv_mat* m, int32_t force_kernel)
         if (rc == SPMV_ERR_HIP) set_error("building the row-grouped copy of an ELL handle failed");
         return rc;
     }
-    // the panel and two-phase kernels read row_ptr and their own arrays only
-    if ((csr->kernel == SPMV_CSR_PANEL || csr->kernel == SPMV_CSR_TWOPHASE || csr->kernel == SPMV_CSR_ELL) && csr->b && csr->v)
-    {
-        (void)hipFree(const_cast<int32_t*>(csr->b));
-        (void)hipFree(const_cast<double*>(csr->v));
-        csr->device_bytes -= slots * 12;
-        csr->b = nullptr;
-        csr->v = nullptr;
-    }
-    m->coo_csr = csr;
-    m->kernel  = SPMV_CSR_PANEL;  // reported for ELL as "runs from the row-grouped copy"
-    m->device_bytes += csr->device_bytes;
+    *out = csr;
     return SPMV_OK;
-}
-int ell_own_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
-}  // namespace
-
-// the row-grouped copy with the PANEL kernel forced on it (spmv_mat_set_kernel(ell, SPMV_CSR_PANEL)); only_if_worth: the
-// model's gate (no launches): >= 2M slots whose row blocks span more than 1 MiB of an x beyond L2
-int ell_build_panel(spmv_mat* m, bool only_if_worth)
-{
-    if (m->coo_csr && m->coo_csr->kernel == SPMV_CSR_PANEL)
-    {
-        m->kernel = SPMV_CSR_PANEL;
-        return SPMV_OK;
-    }
-    const int64_t slots = (int64_t)m->nrow * m->k;
-    if (slots == 0 || slots > (int64_t)INT32_MAX - 65536) return SPMV_OK;
-    if (only_if_worth)
-    {
-        if (slots < ((int64_t)2 << 20) || m->k < 2 || (double)m->ncol * 8.0 <= 4.0 * 1048576.0) return SPMV_OK;
-        const double span = ell_mean_block_span(m);  // how far apart are the columns of 256 consecutive rows, on average?
-        if (span < 0.0) SPMV_FAIL(SPMV_ERR_HIP, "ELL window scan failed: %s", hipGetErrorString(hipGetLastError()));
-        if (span <= 131072.0) return SPMV_OK;  // a row block's x window is at most 1 MiB: stays in L2
-    }
-    ell_drop_rowgrouped(m);
-    return ell_make_rowgrouped(m, SPMV_CSR_PANEL);
 }
 
 // AUTO for an ELL handle (select.hip; tools/sweep_structures.py).  The format's own kernels: two rows per lane (with the
@@ -508,15 +476,14 @@ int ell_select_kernel(spmv_mat* m)
 {
     spmv_ctx* ctx = m->ctx;
     select_reset(m);
-    ell_drop_rowgrouped(m);
+    rowgrouped_drop(m);
     m->kernel      = SPMV_CSR_VECTOR;
     m->ell_variant = 0;
     const int64_t slots = (int64_t)m->nrow * m->k;
     if (slots == 0 || m->nrow <= 0) return SPMV_OK;
-    if (!select_trials_enabled(m) || slots < kSelectMinNnz)
-        return (m->ell_diag || m->sel_no_rowgrouped) ? SPMV_OK : ell_build_panel(m, /*only_if_worth=*/true);
     select_scratch sv;
-    if (sv.alloc(ctx, m->ncol, m->nrow) != SPMV_OK) return (m->ell_diag || m->sel_no_rowgrouped) ? SPMV_OK : ell_build_panel(m, true);
+    if (!select_trials_enabled(m) || slots < kSelectMinNnz || sv.alloc(ctx, m->ncol, m->nrow) != SPMV_OK)
+        return (m->ell_diag || m->sel_no_rowgrouped) ? SPMV_OK : ell_model_copy(m);
     // is the row-grouped copy a candidate?  (decided from the matrix, not from a timing: it is built BEFORE anything is timed, so
     // that no allocation falls between two timings - select.hip)
     bool candidate = !m->sel_no_rowgrouped && slots <= (int64_t)INT32_MAX - 65536;  // (the ELL copy of a CSR handle: that handle IS the row-grouped form)
@@ -541,7 +508,7 @@ int ell_select_kernel(spmv_mat* m)
     int rc = SPMV_OK;
     if (candidate)
     {
-        rc = ell_make_rowgrouped(m, SPMV_CSR_AUTO);
+        rc = rowgrouped_build(m, SPMV_CSR_AUTO);
         if (rc == SPMV_ERR_ALLOC)
         {
             (void)hipGetLastError();
@@ -559,11 +526,11 @@ int ell_select_kernel(spmv_mat* m)
     ids[n++] = 1;
     if (has_v2) ids[n++] = 2;
     if (m->ell_rval) ids[n++] = 4;
-    if (m->coo_csr) ids[n++] = 3;
+    if (m->rowgrouped) ids[n++] = 3;
     float t[5] = {-1.f, -1.f, -1.f, -1.f, -1.f};
     rc = select_rounds(ctx, n,
                        [&](int j) {
-                           if (ids[j] == 3) return csr_apply(ctx, m->coo_csr, sv.x, sv.y);
+                           if (ids[j] == 3) return csr_apply(ctx, m->rowgrouped, sv.x, sv.y);
                            m->ell_variant = ids[j] == 4 ? 3 : ids[j];
                            return ell_own_apply(ctx, m, sv.x, sv.y);
                        },
@@ -587,13 +554,13 @@ int ell_select_kernel(spmv_mat* m)
     }
     m->ell_variant = best_v;
     if (best_v != 3 && m->ell_dia_order_req < 0) ell_free_dia_order(m);  // (a copy that was asked for stays, used or not)
-    if (m->coo_csr)
+    if (m->rowgrouped)
     {
         const float t_copy = t[n - 1];
         if (t_copy >= 0.f) select_note(m, SPMV_CSR_PANEL, t_copy);
-        if (!(t_copy >= 0.f && t_copy < best_ms * 0.98f)) ell_drop_rowgrouped(m);
+        if (!(t_copy >= 0.f && t_copy < best_ms * 0.98f)) rowgrouped_drop(m);
     }
-    m->kernel = m->coo_csr ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
+    m->kernel = m->rowgrouped ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
     return SPMV_OK;
 }
 
@@ -963,14 +930,8 @@ int ell_analyse(spmv_mat* m)
 {
     m->kernel = SPMV_CSR_VECTOR;  // reported for ELL as "one lane per row"
     SPMV_TRY(ell_detect_diagonals(m));
-    const bool from_ctx = plan_take_armed(m);
-    if (plan_of(m))
-    {
-        const int rc = ell_apply_plan(m);
-        plan_clear(m);
-        if (rc == SPMV_OK || !from_ctx) return rc;
-        (void)hipGetLastError();  // (a context's plan that does not fit this matrix: the handle selects by itself)
-    }
+    int rc;
+    if (plan_analyse(m, &rc)) return rc;
     if (!m->kernel_forced) SPMV_TRY(ell_select_kernel(m));
     return SPMV_OK;
 }
@@ -982,7 +943,7 @@ int ell_apply_plan(spmv_mat* m)
 {
     const plan_node& p = *plan_of(m);
     select_reset(m);
-    ell_drop_rowgrouped(m);
+    rowgrouped_drop(m);
     m->kernel        = SPMV_CSR_VECTOR;
     m->ell_variant   = p.ell_variant >= 0 && p.ell_variant <= 3 ? p.ell_variant : 0;
     if (m->ell_variant == 3)
@@ -1000,8 +961,10 @@ int ell_apply_plan(spmv_mat* m)
     if ((int64_t)m->nrow * m->k == 0) return SPMV_OK;
     if (p.kernel == SPMV_CSR_PANEL)
     {
-        SPMV_TRY(ell_make_rowgrouped(m, SPMV_CSR_AUTO));  // (hands the copy's node down)
-        m->kernel = m->coo_csr ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
+        SPMV_REQUIRE((int64_t)m->nrow * m->k <= (int64_t)INT32_MAX - 65536, "the row-grouped copy of an ELL handle of %d rows x %d slots: shard it (int32 offsets)",
+                     m->nrow, m->k);
+        SPMV_TRY(rowgrouped_build(m, SPMV_CSR_AUTO));  // (hands the copy's node down)
+        m->kernel = m->rowgrouped ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
     }
     if (p.ell_tiled)
         SPMV_TRY(ell_build_tiles(m, /*only_if_worth=*/false));
@@ -1016,7 +979,7 @@ int ell_apply_plan(spmv_mat* m)
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
 {
     if (A->nrow == 0) return SPMV_OK;
-    if (A->coo_csr && A->kernel == SPMV_CSR_PANEL) return csr_apply(ctx, A->coo_csr, x, y);
+    if (runs_from_rowgrouped(A)) return csr_apply(ctx, A->rowgrouped, x, y);
     return ell_own_apply(ctx, A, x, y);
 }
 

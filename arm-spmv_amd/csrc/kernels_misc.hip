@@ -341,28 +341,12 @@ int csc_scatter_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double*
 }
 }  // namespace
 
-void csc_drop_rowgrouped(spmv_mat* m)
-{
-    if (!m->coo_csr) return;
-    (void)hipStreamSynchronize(m->ctx->stream);
-    m->device_bytes -= m->coo_csr->device_bytes;
-    mat_free(m->coo_csr);
-    m->coo_csr = nullptr;
-    if (m->kernel == SPMV_CSR_PANEL) m->kernel = SPMV_CSR_VECTOR;
-}
-
 // The entries of a CSC handle grouped by row on the device (column expansion + spmv_coo_to_csr through a borrowed COO view of
 // the same arrays: duplicates and the column-major order inside a row kept) as an internal CSR handle; force_kernel AUTO: that
-// copy picks its kernel like any CSR handle (select.hip), PANEL: the panel layout (spmv_mat_set_kernel(csc, SPMV_CSR_PANEL)).
-int csc_build_rowgrouped(spmv_mat* m, int32_t force_kernel)
+// copy picks its kernel like any CSR handle (select.hip: the segmented scan included), PANEL: the panel layout
+// (spmv_mat_set_kernel(csc, SPMV_CSR_PANEL)).  For rowgrouped_build.
+int csc_rowgrouped_copy(spmv_mat* m, int32_t force_kernel, spmv_mat** out)
 {
-    if (m->coo_csr && (force_kernel == SPMV_CSR_AUTO || m->coo_csr->kernel == force_kernel))
-    {
-        m->kernel = SPMV_CSR_PANEL;
-        return SPMV_OK;
-    }
-    if (m->nnz == 0 || m->nnz > (int64_t)INT32_MAX - 65536 || !launch_fits(m->ncol, 8)) return SPMV_OK;
-    csc_drop_rowgrouped(m);
     spmv_ctx* ctx  = m->ctx;
     int32_t*  cols = nullptr;
     if (hipMalloc(&cols, sizeof(int32_t) * (size_t)m->nnz) != hipSuccess)
@@ -389,79 +373,52 @@ int csc_build_rowgrouped(spmv_mat* m, int32_t force_kernel)
     int       rc  = coo_analyse(&view);  // sortedness of the row indices
     view.plan_base = m->plan_base;  // (a CSC handle built from a plan: spmv_coo_to_csr hands the copy's node down from the view -
     view.plan_at   = m->plan_at;    // set only now: the view itself is nobody's handle and must not act on the plan)
-    spmv_mat* csr = nullptr;
-    if (rc == SPMV_OK) rc = coo_to_csr(ctx, &view, &csr, force_kernel);
+    if (rc == SPMV_OK) rc = coo_to_csr(ctx, &view, out, force_kernel);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(cols);
-    if (rc != SPMV_OK) return rc;
-    // the panel and two-phase layouts read row_ptr and their own arrays only
-    if ((csr->kernel == SPMV_CSR_PANEL || csr->kernel == SPMV_CSR_TWOPHASE || csr->kernel == SPMV_CSR_ELL) && csr->b && csr->v)
+    return rc;
+}
+
+namespace
+{
+// the trial of csc_select_kernel (rowgrouped_select): the copy, if it is built, and the scatter timed in rounds until their minima
+// stand still (select.hip)
+int csc_trial(spmv_mat* m, const select_scratch& sv, bool /*model_copy*/, float* t_copy, float* t_own)
+{
+    if (!m->rowgrouped) return SPMV_OK;
+    spmv_ctx* ctx  = m->ctx;
+    float     t[2] = {-1.f, -1.f};
+    const int rc   = select_rounds(ctx, 2, [&](int j) { return j == 0 ? csr_apply(ctx, m->rowgrouped, sv.x, sv.y) : csc_scatter_apply(ctx, m, sv.x, sv.y); }, t,
+                                   &m->sel_rounds);
+    if (rc == SPMV_OK)
     {
-        (void)hipFree(const_cast<int32_t*>(csr->b));
-        (void)hipFree(const_cast<double*>(csr->v));
-        csr->device_bytes -= (int64_t)csr->nnz * 12;
-        csr->b = nullptr;
-        csr->v = nullptr;
+        *t_copy = t[0] >= 0.f ? t[0] : 1e30f;
+        *t_own  = t[1] >= 0.f ? t[1] : 1e30f;
     }
-    m->coo_csr = csr;
-    m->kernel  = SPMV_CSR_PANEL;  // reported for CSC as "runs from the row-grouped copy"
-    m->device_bytes += csr->device_bytes;
+    (void)hipStreamSynchronize(ctx->stream);
+    if (rc != SPMV_OK) return rc;
+    select_note(m, SPMV_CSR_PANEL, *t_copy);
+    select_note(m, SPMV_CSR_VECTOR, *t_own);
     return SPMV_OK;
 }
+}  // namespace
 
 // AUTO for a CSC handle (round 5, select.hip): the scatter over the columns (one fp64 atomic on y per entry) or the copy grouped
 // by row.  Model: the copy from 1.5M entries on; from 64K entries on both are timed.
 int csc_select_kernel(spmv_mat* m)
 {
-    spmv_ctx* ctx = m->ctx;
     select_reset(m);
-    csc_drop_rowgrouped(m);
+    rowgrouped_drop(m);
     m->kernel = SPMV_CSR_VECTOR;
     if (m->nnz == 0 || m->nrow <= 0 || m->ncol <= 0) return SPMV_OK;
-    const bool model_copy = m->nnz >= ((int64_t)3 << 19);
-    if (!select_trials_enabled(m) || m->nnz < kSelectMinNnz) return model_copy ? csc_build_rowgrouped(m, SPMV_CSR_AUTO) : SPMV_OK;
-    select_scratch sv;
-    if (sv.alloc(ctx, m->ncol, m->nrow) != SPMV_OK) return model_copy ? csc_build_rowgrouped(m, SPMV_CSR_AUTO) : SPMV_OK;
-    float t_own = 1e30f, t_copy = 1e30f;
-    int   rc    = csc_build_rowgrouped(m, SPMV_CSR_AUTO);
-    if (rc == SPMV_ERR_ALLOC)
-    {
-        (void)hipGetLastError();
-        return SPMV_OK;  // no memory for the copy: the scatter runs
-    }
-    if (rc != SPMV_OK) return rc;
-    if (!m->coo_csr) return SPMV_OK;
-    {
-        // the copy is built; the two are timed in rounds until their minima stand still (select.hip)
-        float t[2] = {-1.f, -1.f};
-        rc = select_rounds(ctx, 2, [&](int j) { return j == 0 ? csr_apply(ctx, m->coo_csr, sv.x, sv.y) : csc_scatter_apply(ctx, m, sv.x, sv.y); }, t, &m->sel_rounds);
-        if (rc == SPMV_OK)
-        {
-            t_copy = t[0] >= 0.f ? t[0] : 1e30f;
-            t_own  = t[1] >= 0.f ? t[1] : 1e30f;
-        }
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    if (rc != SPMV_OK) return rc;
-    select_note(m, SPMV_CSR_PANEL, t_copy);
-    select_note(m, SPMV_CSR_VECTOR, t_own);
-    const bool keep_copy = model_copy ? t_copy <= t_own * 1.02f : t_copy < t_own * 0.98f;
-    if (!keep_copy) csc_drop_rowgrouped(m);
-    m->kernel = m->coo_csr ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
-    return SPMV_OK;
+    return rowgrouped_select(m, csc_trial);
 }
 
 int csc_analyse(spmv_mat* m)
 {
     m->kernel = SPMV_CSR_VECTOR;  // reported for CSC as "scatter over the columns"
-    const bool from_ctx = plan_take_armed(m);
-    if (plan_of(m))
-    {
-        const int rc = csc_apply_plan(m);
-        plan_clear(m);
-        if (rc == SPMV_OK || !from_ctx) return rc;
-        (void)hipGetLastError();  // (a context's plan that does not fit this matrix: the handle selects by itself)
-    }
+    int rc;
+    if (plan_analyse(m, &rc)) return rc;
     if (m->kernel_forced) return SPMV_OK;
     return csc_select_kernel(m);
 }
@@ -471,18 +428,18 @@ int csc_apply_plan(spmv_mat* m)
 {
     const plan_node& p = *plan_of(m);
     select_reset(m);
-    csc_drop_rowgrouped(m);
+    rowgrouped_drop(m);
     m->kernel = SPMV_CSR_VECTOR;
     if (m->nnz == 0 || m->nrow <= 0 || m->ncol <= 0 || p.kernel != SPMV_CSR_PANEL) return SPMV_OK;
-    SPMV_TRY(csc_build_rowgrouped(m, SPMV_CSR_AUTO));
-    m->kernel = m->coo_csr ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
+    SPMV_TRY(rowgrouped_build(m, SPMV_CSR_AUTO));
+    m->kernel = m->rowgrouped ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
     return SPMV_OK;
 }
 
 int csc_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
 {
     if (A->ncol == 0 || A->nnz == 0) return SPMV_OK;
-    if (A->coo_csr && A->kernel == SPMV_CSR_PANEL) return csr_apply(ctx, A->coo_csr, x, y);
+    if (runs_from_rowgrouped(A)) return csr_apply(ctx, A->rowgrouped, x, y);
     return csc_scatter_apply(ctx, A, x, y);
 }
 

@@ -69,16 +69,16 @@ int collect(const spmv_mat* m, std::vector<plan_node>& out)
     if (csr && m->kernel != SPMV_CSR_VECTOR && m->kernel != SPMV_CSR_AUTO) n.flags = 0;  // (the tuning bits of the row-parallel kernel)
     if (m->format == SPMV_FMT_ELL)
     {
-        const bool own   = !(m->coo_csr && m->kernel == SPMV_CSR_PANEL);  // the format's own kernels run (else: the row-grouped copy)
+        const bool own   = !runs_from_rowgrouped(m);  // the format's own kernels run (else: the row-grouped copy)
         n.ell_variant    = own ? m->ell_variant : 0;
         n.ell_tiled      = own && m->ell_tval ? 1 : 0;
         if (!own) n.lanes_per_row = 0;
     }
     if (m->format == SPMV_FMT_COO) n.coo_bins_per_xcd = m->kernel == SPMV_CSR_PANEL ? 0 : m->cb_bins / 8;
     if (m->format == SPMV_FMT_COO || m->format == SPMV_FMT_CSC || m->format == SPMV_FMT_DIA) n.lanes_per_row = 0, n.flags = m->format == SPMV_FMT_DIA ? m->flags : 0;
-    const bool from_copy = m->format != SPMV_FMT_CSR && m->coo_csr && m->kernel == SPMV_CSR_PANEL;
-    const bool split     = m->format == SPMV_FMT_CSR && m->kernel == SPMV_CSR_SPLIT;
-    if ((from_copy || split) && m->coo_csr) n.child_rowgrouped = collect(m->coo_csr, out);
+    if (runs_from_rowgrouped(m)) n.child_rowgrouped = collect(m->rowgrouped, out);
+    const bool split = m->format == SPMV_FMT_CSR && m->kernel == SPMV_CSR_SPLIT;
+    if (split && m->split_short) n.child_rowgrouped = collect(m->split_short, out);  // (the plan blob: the short rows' node in the same field)
     if (split && m->split_long) n.child_long = collect(m->split_long, out);
     if (m->format == SPMV_FMT_CSR && m->kernel == SPMV_CSR_ELL && m->ell_copy) n.child_ell = collect(m->ell_copy, out);
     out[(size_t)at] = n;
@@ -125,6 +125,8 @@ void plan_clear(spmv_mat* m)
     m->plan_at   = -1;
 }
 
+namespace
+{
 bool plan_take_armed(spmv_mat* m)
 {
     spmv_ctx* ctx = m->ctx;
@@ -136,6 +138,31 @@ bool plan_take_armed(spmv_mat* m)
     m->plan_base = n;
     m->plan_at   = 0;
     return true;
+}
+
+int plan_apply(spmv_mat* m)
+{
+    switch (m->format)
+    {
+        case SPMV_FMT_CSR: return csr_apply_plan(m);
+        case SPMV_FMT_COO: return coo_apply_plan(m);
+        case SPMV_FMT_CSC: return csc_apply_plan(m);
+        case SPMV_FMT_ELL: return ell_apply_plan(m);
+        default: return SPMV_OK;  // DIA: one kernel, nothing to plan
+    }
+}
+}  // namespace
+
+bool plan_analyse(spmv_mat* m, int* rc)
+{
+    const bool from_ctx = plan_take_armed(m);
+    if (!plan_of(m)) return false;
+    *rc = plan_apply(m);
+    plan_clear(m);
+    if (*rc == SPMV_OK || !from_ctx) return true;
+    (void)hipGetLastError();  // a context's plan that does not fit THIS matrix is no reason to refuse the handle: it selects by itself
+    if (m->format == SPMV_FMT_CSR) plan_reset_requests(m);
+    return false;
 }
 }  // namespace spmv
 
@@ -171,15 +198,7 @@ int spmv_mat_set_plan(spmv_mat* m, const void* buf, int64_t len)
     SPMV_HIP(hipSetDevice(m->ctx->device));
     m->plan_base = own.data();
     m->plan_at   = 0;
-    int rc       = SPMV_OK;
-    switch (m->format)
-    {
-        case SPMV_FMT_CSR: rc = csr_apply_plan(m); break;
-        case SPMV_FMT_COO: rc = coo_apply_plan(m); break;
-        case SPMV_FMT_CSC: rc = csc_apply_plan(m); break;
-        case SPMV_FMT_ELL: rc = ell_apply_plan(m); break;
-        default: break;  // DIA: one kernel, nothing to plan
-    }
+    const int rc = plan_apply(m);
     plan_clear(m);
     if (hipStreamSynchronize(m->ctx->stream) != hipSuccess && rc == SPMV_OK) SPMV_FAIL(SPMV_ERR_HIP, "spmv_mat_set_plan: %s", hipGetErrorString(hipGetLastError()));
     if (rc != SPMV_OK)
