@@ -16,6 +16,11 @@ The x replica is assembled from the ranks' own slices by an RCCL all-gather over
            --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds
+everything else the line can carry: the live counter passes (N = 1), the set-up re-timed without trials and under the
+plan, the check that every rank holds rank 0's plan, the x all-gather charged to every step and the y gather (N > 1),
+the other configurations under "extra" and the CPU baseline (N = 1).
 """
 from __future__ import annotations
 
@@ -533,6 +538,9 @@ def main() -> None:
     ap.add_argument("--kernel", type=int, default=0, help="spmv_csr_kernel id (0 = auto)")
     ap.add_argument("--lanes", type=int, default=0, help="lanes per row for the vector kernel (0 = auto)")
     ap.add_argument("--flags", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: live counters, set-up re-timings, the plan check, the per-step x all-gather "
+                         "and y gather, the extra configurations and the CPU baseline (the --no-* options below skip parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-rows", type=int, default=0,
                     help="rows of the headline matrix the CPU baseline's OpenMP mode runs on; 0 = all of them (BASELINE.md section 4: the same matrix)")
@@ -569,7 +577,7 @@ def main() -> None:
         return
     # N = 1: the counter passes run first, while this process has not touched the GPU (one GPU process at a time)
     live = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_live_counters:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_live_counters:
         live = live_counters(args)
 
     import torch
@@ -655,8 +663,8 @@ def main() -> None:
         setup_no_trial_s = None
         setup_with_plan_s = None
         my_plan = A.get_plan()
-        plans_equal = shard.plans_equal(my_plan, dev) if grouped else None
-        if world == 1 and int(info.kernel) == 4 and not args.no_extra:
+        plans_equal = shard.plans_equal(my_plan, dev) if grouped and args.full else None
+        if args.full and world == 1 and int(info.kernel) == 4 and not args.no_extra:
             os.environ["SPMV_PANEL_TRIAL"] = "0"
             t1 = time.perf_counter()
             B = ctx.gen_csr_uniform(row_begin, row_end, ncol, k, band=args.band, seed=args.seed)
@@ -715,7 +723,7 @@ def main() -> None:
 
         # secondary: the same loop with the x exchange charged to every step (solver-realistic)
         exch_s = None
-        if grouped:
+        if grouped and args.full:
             barrier()
             t1 = time.perf_counter()
             for _ in range(args.steps):
@@ -734,7 +742,7 @@ def main() -> None:
         # the optional last step of the sharded product: every rank's y slice gathered into the full y on every rank
         # (the reference does it for DIA only, src/mat_vec.cpp:474-477); timed by itself, never part of `value`
         y_concat_ms = None
-        if grouped:
+        if grouped and args.full:
             y_full = shard.concatenate_y(y, ncol)  # warm-up (allocates the result)
             barrier()
             t1 = time.perf_counter()
@@ -787,7 +795,7 @@ def main() -> None:
         # at N = 1, the shard shape of C5.  5 warm-up + 50 applications between HIP events on the engine's stream.
         # Reported in "extra"; they never enter "value".
         extra = []
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             def one(name, fmt, make, tkey=None, x_vec=None, sharded=False, flags=0):
                 t = time.perf_counter()
                 M = make()
@@ -1058,7 +1066,7 @@ def main() -> None:
                    if l2 and l2["l2_frac"] > 0.75 else {}),
             },
         }
-        if grouped:
+        if exch_s is not None:
             out["with_x_allgather_each_step"] = {
                 "value": round(2.0 * nnz_total * args.steps / exch_max / 1e9, 3),
                 "unit": "GFLOP/s",
@@ -1068,7 +1076,7 @@ def main() -> None:
             out["y_concatenate_ms"] = round(y_concat_ms, 4) if y_concat_ms is not None else None
         if extra:
             out["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
 

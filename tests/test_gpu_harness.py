@@ -158,7 +158,7 @@ def test_reference_main_cpp_runs_unchanged_on_the_engine(tmp_path, pkg):
 
 
 def test_bench_contract_one_rank_and_two_rank_rehearsal(tmp_path):
-    """bench.py end to end on small shards: the single-rank line carries roofline + cpu_baseline; the two-rank run
+    """bench.py --full end to end on small shards: the single-rank line carries roofline + cpu_baseline; the two-rank run
     (both ranks on this one GPU, gloo standing in for RCCL: SPMV_BENCH_BACKEND=gloo) exercises sharding, the x
     all-gather and the max-over-ranks timing of the N > 1 path.  Parity of the shards themselves is covered by
     test_row_shards_concatenate_to_unsharded_result."""
@@ -172,7 +172,7 @@ def test_bench_contract_one_rank_and_two_rank_rehearsal(tmp_path):
     # the caller having exported it
     env = dict(os.environ)
     env.pop("HSA_ENABLE_IPC_MODE_LEGACY", None)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--rows", "400000", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--rows", "400000", "--steps", "4", "--warmup", "1",
                         "--cpu-sample-rows", "100000", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -205,7 +205,7 @@ def test_bench_contract_one_rank_and_two_rank_rehearsal(tmp_path):
         port = s.getsockname()[1]
     env["SPMV_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--rows", "400000",
+                        "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--full", "--gpus", "2", "--rows", "400000",
                         "--steps", "4", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -227,6 +227,69 @@ def test_bench_contract_one_rank_and_two_rank_rehearsal(tmp_path):
     assert skew["rows"]["entries_per_shard_max_over_mean"] > 1.5 and skew["entries"]["entries_per_shard_max_over_mean"] <= 1.02
     band = [e for e in line["extra"] if "band of 65536" in e["name"]]  # the band-random variant is reported at every world size
     assert len(band) == 1 and band[0]["n_gpus"] == 2 and band[0]["nnz"] == 2 * 400000 * 32 and 0 < band[0]["roofline"]["frac"] <= 1.0
+
+
+def _check_dumped_y(pkg, orc, out_dir, suffix, n, ncol, k, products):
+    """y of a --dump-outputs run (every row of a small shard) against `products` oracle products on the same rows"""
+    import oracle_lib as ol
+
+    rows = np.load(out_dir / f"y_rows{suffix}.npy").astype(np.int64)
+    y = np.load(out_dir / f"y{suffix}.npy")
+    assert len(rows) == len(y) == n and np.array_equal(np.diff(rows), np.ones(n - 1))
+    rp, col, val = pkg.synth.csr_uniform(int(rows[0]), int(rows[0]) + n, ncol, k, seed=1)
+    x = pkg.synth.vec_uniform(ncol, seed=1)
+    ref, scale = np.zeros(n), np.zeros(n)
+    ol.csr_spmv(orc, rp, col, val, x, ref, fma=True)
+    ol.csr_abs_row_sums(orc, rp, col, val, x, scale)
+    err = float(np.max(np.abs(y - products * ref) / np.maximum(products * scale, 1e-300)))
+    assert err <= 1e-10, err
+
+
+def test_plain_bench_run_carries_the_headline_only(tmp_path, pkg, orc):
+    """bench.py without --full, one rank and two (gloo on this one GPU): set-up, warm-up, the timed steps, the dump and the
+    line - no counter passes, extra configurations, CPU baseline, plan check or per-step all-gather.  The dumped y is the
+    warm-up and timed products of the headline matrix, row for row against the oracle."""
+    import json
+    import os
+    import socket
+    import sys
+
+    env = dict(os.environ)
+    env.pop("SPMV_BENCH_BACKEND", None)
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--rows", "400000", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "one")], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 1 and line["steps"] == 4 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "GFLOP/s" and line["higher_is_better"] is True and line["dtype"] == "f64" and line["metric"].startswith("SpMV GFLOP/s")
+    assert abs(line["value"] - 2.0 * 400000 * 32 / line["ms_per_step"] / 1e6) <= 1e-3 * line["value"]
+    assert 0 < line["roofline"]["frac"] < 1.0 and line["roofline"]["traffic_live"] is None
+    for key in ("extra", "cpu_baseline", "with_x_allgather_each_step", "y_concatenate_ms"):
+        assert key not in line, key
+    cfg = line["config"]
+    assert cfg["setup_seconds"] > 0 and cfg["setup_seconds_without_trials"] is None and cfg["setup_seconds_with_plan"] is None
+    _check_dumped_y(pkg, orc, tmp_path / "one", "", 400000, 400000, 32, 5)
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env["SPMV_BENCH_BACKEND"] = "gloo"
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
+                        "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--rows", "400000",
+                        "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / "two")], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, "rank 0 prints exactly one JSON line"
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["config"]["nnz_total"] == 2 * 400000 * 32 and line["value"] > 0
+    for key in ("extra", "cpu_baseline", "with_x_allgather_each_step", "y_concatenate_ms"):
+        assert key not in line, key
+    plan = line["config"]["plan"]
+    assert plan["shared_from_rank_0"] is True and plan["plans_equal"] is None and len(line["config"]["per_rank"]) == 2
+    for rank in (0, 1):
+        _check_dumped_y(pkg, orc, tmp_path / "two", f"_rank{rank}", 400000, 800000, 32, 5)
 
 
 def _check_sharded_rows(pkg, orc, path, n, parts, k, band, seed):
@@ -311,7 +374,7 @@ def test_native_sharded_harness_at_the_full_shard_shape_of_config_5(tmp_path, pk
 
 
 def test_bench_under_torchrun_with_one_rank_runs_the_rccl_collectives(tmp_path):
-    """`torch.distributed.run --nproc-per-node 1 bench.py --gpus 1`: the launcher starts before anything touches the GPU,
+    """`torch.distributed.run --nproc-per-node 1 bench.py --full --gpus 1`: the launcher starts before anything touches the GPU,
     the process group is backend nccl (= RCCL) with world size 1, and the run makes the same collective calls as the
     8-GPU job - all_gather_into_tensor of the x slices, barriers, the all-reduce of the times."""
     import json
@@ -326,7 +389,7 @@ def test_bench_under_torchrun_with_one_rank_runs_the_rccl_collectives(tmp_path):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-                        "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "1", "--rows", "400000",
+                        "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--full", "--gpus", "1", "--rows", "400000",
                         "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -8,13 +8,13 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 cd "$R" || exit 1
-timeout -k 10 600 python3 bench.py > "$O/bench_c2_uniform.json" 2> "$O/bench_c2_uniform.err" || exit 1
+timeout -k 10 600 python3 bench.py --full > "$O/bench_c2_uniform.json" 2> "$O/bench_c2_uniform.err" || exit 1
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 "$R/bench.py" --steps 50 --warmup 5 --no-cpu-baseline --no-live-counters > "$O/rocprof_stats.log" 2>&1 || exit 1
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch" -- python3 "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-live-counters > "$O/pmc_fetch.log" 2>&1 || exit 1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/pmc_write" -- python3 "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-live-counters > "$O/pmc_write.log" 2>&1 || exit 1
-timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --output-format csv -d "$O/pmc_tcc" -- python3 "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-live-counters > "$O/pmc_tcc.log" 2>&1 || exit 1
-timeout -k 10 300 rocprofv3 --pmc TCP_TCC_READ_REQ_sum TCC_REQ_sum TCC_BUSY_sum --output-format csv -d "$O/pmc_req" -- python3 "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-live-counters > "$O/pmc_req.log" 2>&1 || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 "$R/bench.py" --full --steps 50 --warmup 5 --no-cpu-baseline --no-live-counters > "$O/rocprof_stats.log" 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch" -- python3 "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-live-counters > "$O/pmc_fetch.log" 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/pmc_write" -- python3 "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-live-counters > "$O/pmc_write.log" 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --output-format csv -d "$O/pmc_tcc" -- python3 "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-live-counters > "$O/pmc_tcc.log" 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --pmc TCP_TCC_READ_REQ_sum TCC_REQ_sum TCC_BUSY_sum --output-format csv -d "$O/pmc_req" -- python3 "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-live-counters > "$O/pmc_req.log" 2>&1 || exit 1
 cd "$R" || exit 1
 python3 - "$O" <<'PY'
 import csv, glob, re, statistics, sys
