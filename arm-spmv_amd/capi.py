@@ -94,6 +94,9 @@ SIGNATURES = {
     "spmv_apply_timed": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _f64p]),
     "spmv_apply_multi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32]),
     "spmv_apply_multi_timed": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _f64p]),
+    "spmv_apply_transpose": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_apply_transpose_timed": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _f64p]),
+    "spmv_mat_transpose_setup": (C.c_int, [_vp]),
     "spmv_dot": (C.c_int, [_vp, _vp, _vp, _f64p]),
     "spmv_axpby": (C.c_int, [_vp, C.c_double, _vp, C.c_double, _vp, _vp]),
     "spmv_apply_dot": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, _f64p]),
@@ -388,6 +391,17 @@ class Context:
         _check(self._lib.spmv_apply_multi_timed(self.h, A.h, k, X.h, Y.h, 1 if overwrite else 0, reps, C.byref(ms)))
         return ms.value
 
+    def apply_transpose(self, A: "Matrix", x: "Vector", y: "Vector") -> None:
+        """y += A^T x, asynchronous: x has nrow entries (a shard: its rows), y ncol.  The first call builds the handle's transposed
+        state (Matrix.transpose_setup); the forward state, its kernel and its plan stay as they were"""
+        _check(self._lib.spmv_apply_transpose(self.h, A.h, x.h, y.h))
+
+    def apply_transpose_timed(self, A: "Matrix", x: "Vector", y: "Vector", reps: int) -> float:
+        """`reps` back-to-back apply_transpose between two device events (set-up, if due, before them); mean milliseconds"""
+        ms = C.c_double(0.0)
+        _check(self._lib.spmv_apply_transpose_timed(self.h, A.h, x.h, y.h, reps, C.byref(ms)))
+        return ms.value
+
     def dot(self, x: "Vector", y: "Vector") -> float:
         r = C.c_double(0.0)
         _check(self._lib.spmv_dot(self.h, x.h, y.h, C.byref(r)))
@@ -552,6 +566,10 @@ class Matrix:
         v = C.c_int64(0)
         _check(self.ctx._lib.spmv_mat_get_param(self.h, name.encode(), C.byref(v)))
         return v.value
+
+    def transpose_setup(self) -> None:
+        """build the handle's transposed state now (spmv_mat_transpose_setup): synchronous, idempotent"""
+        _check(self.ctx._lib.spmv_mat_transpose_setup(self.h))
 
     def get_plan(self) -> bytes:
         """the handle's set-up decisions (kernel, layout, tuned parameters; its copies' too) as a POD blob (spmv_mat_get_plan)"""

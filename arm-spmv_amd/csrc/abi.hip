@@ -75,6 +75,7 @@ int mat_alloc(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t
 void mat_free(spmv_mat* m)
 {
     if (!m) return;
+    transpose_free(m);  // (the companion borrows the arrays freed below)
     if (m->owned)
     {
         if (m->a) (void)hipFree(const_cast<int32_t*>(m->a));
@@ -864,6 +865,7 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
                          "panel_keep_csr = 0 needs an owned CSR handle whose panel or two-phase layout or ELL copy is built");
             SPMV_HIP(hipSetDevice(m->ctx->device));
             SPMV_HIP(hipStreamSynchronize(m->ctx->stream));
+            transpose_free(m);  // (its companion reads the arrays released here)
             // a two-phase handle first offers the gigabytes it is about to release to its product stream's piece search
             // (kernels_csr_twophase.hip: memory of another moment of the allocator's history, at no transient cost)
             bool keep_b = false, keep_v = false;
@@ -921,6 +923,8 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
         SPMV_REQUIRE(m->format == SPMV_FMT_DIA && value >= 0 && value <= m->ncol, "dia_col_bound: a DIA handle and 0 <= bound <= ncol");
         m->dia_col_bound = (int32_t)value;
     }
+    else if (!strcmp(name, "transpose_kernel"))  // the companion's kernel (transpose.hip); takes effect at the next set-up
+        SPMV_TRY(transpose_set_kernel(m, value));
     else if (!strcmp(name, "panel_sync"))
         m->pb_sync = (int32_t)value;
     else if (!strcmp(name, "twophase_offer_csr_copy"))
@@ -1021,6 +1025,7 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         SPMV_REQUIRE(symgs_info(m, name, value) == SPMV_OK, "unknown parameter '%s'", name);
         return SPMV_OK;
     }
+    if (transpose_get_param(m, name, value)) return SPMV_OK;  // "transpose_ready", "transpose_bytes", "transpose_kernel", ...
     if (!strcmp(name, "panel_keep_csr"))
         *value = (m->b && m->v) || m->nnz == 0 ? 1 : 0;
     else if (!strcmp(name, "device_bytes"))

@@ -137,6 +137,7 @@ struct spmv_ctx
 namespace spmv
 {
 struct symgs_plan;
+struct transpose_state;
 // ---- plans (plan.hip): the decisions a handle's set-up made - by model or by timing - as plain data ------------------------------
 // One node per handle, children by index (the row-grouped copy of a COO / CSC / ELL handle or the short-row copy of a split,
 // the long rows' matrix of a split in virtual-row mode, the ELL copy of a CSR handle).  32 four-byte fields, no pointers:
@@ -347,6 +348,11 @@ struct spmv_mat
     // symmetric Gauss-Seidel (symgs.hip): L / D / U copies, rows by level, launch schedule; built by symgs_setup
     struct spmv::symgs_plan* gs = nullptr;
     int32_t                  gs_order = 1;  // sweep order: 1 multicolour (default), 0 the matrix's own row order
+
+    // the transposed product (transpose.hip): a companion handle of A^T over A's arrays, or the DIA transposed kernel's set-up;
+    // built by spmv_mat_transpose_setup, no part of the forward state (kernel, copies, device_bytes, plan)
+    struct spmv::transpose_state* tr            = nullptr;
+    int32_t                       tr_kernel_req = SPMV_CSR_AUTO;  // "transpose_kernel": handed to spmv_mat_set_kernel on the companion
 };
 
 namespace spmv
@@ -521,6 +527,10 @@ void release_unread_csr_arrays(spmv_mat* csr);  // a CSR handle whose kernel rea
 int  rowgrouped_build(spmv_mat* m, int32_t force_kernel);  // reuse, size limit, drop, produce, release, adopt
 int  rowgrouped_select(spmv_mat* m, int (*trial)(spmv_mat* m, const select_scratch& sv, bool model_copy, float* t_copy, float* t_own));  // COO, CSC AUTO
 int  rowgrouped_set_kernel(spmv_mat* m, int32_t kernel);  // spmv_mat_set_kernel on a COO, CSC or ELL handle
+// transpose.hip: the transposed product's state
+void transpose_free(spmv_mat* A);                                        // drops it (A's arrays are only borrowed)
+int  transpose_set_kernel(spmv_mat* A, int64_t kernel);                  // "transpose_kernel"
+bool transpose_get_param(const spmv_mat* A, const char* name, int64_t* value);  // "transpose_*"; false: not one of them
 // abi.hip helpers used by the other units
 int  mat_alloc(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t nnz, int32_t k,
                size_t a_count, size_t b_count, size_t v_count, spmv_mat** out);

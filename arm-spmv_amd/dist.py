@@ -6,7 +6,9 @@ Mirrors the reference's NUMA driver (src/mat_vec.cpp:230-297): rank r plays thre
   * every rank holds a FULL replica of x (:257,266); here the replica is assembled from the ranks' own slices
     (rank r owns x[rows of r], the natural layout when y of one product feeds x of the next) by an all-gather
   * y stays sharded; concatenate_y() is the optional gather the reference only performs for DIA (:474-477)
-The only exchange step is the x all-gather; there is no reduction (rows are independent).
+The only exchange step of the forward product is the x all-gather; there is no reduction (rows are independent).  The
+transposed product y = A^T x is the other way round: every rank's shard contributes to ALL columns, and reduce_transposed
+sends every rank the pieces of its own columns (one all-to-all) and adds them up in rank order.
 
 Compute is NOT in this module: callers apply their shard with the HIP engine (capi.Context.apply).  That keeps
 the collective logic testable on CPU with gloo, where the tests plug the oracle in as the per-shard product.
@@ -82,6 +84,38 @@ def concatenate_y(y_own: torch.Tensor, nrow: int, group=None, bounds=None) -> to
     return y_full
 
 
+def reduce_transposed(partial_full: torch.Tensor, y_own: torch.Tensor, ncol: int, bounds=None, group=None) -> None:
+    """y_own += sum over the ranks p of partial_p[own columns], added in rank order 0 .. P-1.
+
+    Each rank holds partial_full = A_p^T x_p over all `ncol` columns (its shard's contribution: spmv_apply_transpose on a row
+    shard, HipShardOps.product_transpose).  One all_to_all_single, split by the column bounds, hands every rank the slices of
+    its own columns; the rank then adds them into y_own one after the other, so the result is deterministic and does not depend
+    on the backend's reduction order.  bounds: the ranks' column ranges (default: all_bounds(ncol, world))."""
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    equal = bounds is None
+    bounds = all_bounds(ncol, world) if bounds is None else [(int(b), int(e)) for b, e in bounds]
+    if len(bounds) != world or bounds[0][0] != 0 or bounds[-1][1] != ncol or any(bounds[r][1] != bounds[r + 1][0] for r in range(world - 1)):
+        raise ValueError(f"bounds {bounds} do not tile [0, {ncol}) over {world} ranks")
+    b, e = bounds[rank]
+    if partial_full.numel() != ncol:
+        raise ValueError(f"partial_full has {partial_full.numel()} entries, expected {ncol}")
+    if y_own.numel() != e - b:
+        raise ValueError(f"rank {rank} owns columns [{b},{e}) but passed a slice of {y_own.numel()} entries")
+    if partial_full.is_cuda and dist.get_backend(group) == "gloo":
+        # rehearsal only (several ranks sharing one GPU, where RCCL refuses to run): stage through the host
+        host = y_own.cpu()
+        reduce_transposed(partial_full.cpu(), host, ncol, None if equal else bounds, group)
+        y_own.copy_(host)
+        return
+    own = e - b
+    pieces = torch.empty(world * own, dtype=partial_full.dtype, device=partial_full.device)
+    dist.all_to_all_single(pieces, partial_full.contiguous(), output_split_sizes=[own] * world,
+                           input_split_sizes=[re - rb for rb, re in bounds], group=group)
+    for p in range(world):
+        y_own += pieces[p * own:(p + 1) * own]
+
+
 def max_over_ranks(value: float, device, group=None) -> float:
     t = torch.tensor([value], dtype=torch.float64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
@@ -143,6 +177,9 @@ class HipShardOps:
 
     def product_dot(self, p_full, w_own, q_own) -> float:  # q = A_shard p ; returns w_own . q
         return self.ctx.apply_dot(self.A, self._v(p_full), self._v(q_own), self._v(w_own), overwrite=True)
+
+    def product_transpose(self, x_own, partial_full) -> None:  # partial_full = A_shard^T x_own (all columns; reduce_transposed sums them)
+        self.ctx.apply_transpose(self.A, self._v(x_own), self._fill0(partial_full))
 
     # ---- the same product in two halves, for overlapping the exchange (enable_overlap) -------------------------
     def enable_overlap(self, col_begin: int, col_end: int) -> None:

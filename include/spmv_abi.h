@@ -435,6 +435,23 @@ int spmv_apply_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec
 int spmv_apply_multi_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* X, spmv_vec* Y, int32_t overwrite,
                            int32_t reps, double* ms_per_apply);
 
+/* y += A^T x.  x has nrow entries (the shard's rows), y has ncol entries.  Asynchronous.  Every format: CSR (uploaded, wrapped,
+ * shard), CSC and COO run on an internal companion handle that borrows A's arrays read the other way round (CSR -> CSC, CSC ->
+ * CSR, COO -> COO with rows and columns swapped) and picks its own kernel; ELL runs as a COO companion that borrows col_ind and
+ * values and owns one array of slot rows (padding slots take part, as in the forward product); DIA has a kernel of its own over
+ * A's row-major values (outputs j < the forward product's column bound, diagonals in slot order from y_j).  A CSR row shard
+ * gives its own contribution y[0..ncol) += A_p^T x_p (the caller sums over the shards).  Refused on the host, before any device
+ * use: null arguments, wrong lengths, overlapping x and y, a CSR handle that released its arrays (panel_keep_csr = 0).
+ * The transposed state never changes the handle's forward state: kernel, copies, device_bytes and plan stay as they were.
+ * Parameters: "transpose_kernel" (set before the set-up; handed to spmv_mat_set_kernel on the companion; reads back the
+ * companion's kernel), "transpose_bytes", "transpose_ready" and "transpose_rowgrouped_kernel" (read-only).  DESIGN.md 10. */
+int spmv_apply_transpose(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y);
+/* `reps` back-to-back spmv_apply_transpose between two HIP events; the set-up, if still due, runs before the first event.
+ * Synchronous. */
+int spmv_apply_transpose_timed(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y, int32_t reps, double* ms_per_apply);
+/* Build the handle's transposed state now.  Synchronous and idempotent.  The first spmv_apply_transpose also runs it. */
+int spmv_mat_transpose_setup(spmv_mat* A);
+
 /* y_host += A * x_host with the caller's HOST vectors, synchronous - the reference's own call shape (include/mat_vec.h:7-11:
  * every CSRMatrixMatVector(A, x, y) hands over host arrays; main.cpp:56-59 does it 50 times), as ONE entry point so that the
  * hand-over can be done the cheapest way for its size.  Vectors of up to 1 MB together: x by CPU stores straight into device
