@@ -37,8 +37,9 @@ int ensure_scratch(spmv_ctx* ctx, size_t bytes)
     return SPMV_OK;
 }
 
-int mat_alloc(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t nnz, int32_t k, size_t a_count,
-              size_t b_count, size_t v_count, spmv_mat** out)
+// a handle over arrays that are not its own (spmv_*_wrap_device; mat_alloc goes on from here)
+static int wrap(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t nnz, int32_t k, const int32_t* a,
+                const int32_t* b, const double* v, spmv_mat** out)
 {
     spmv_mat* m = new (std::nothrow) spmv_mat();
     if (!m) SPMV_FAIL(SPMV_ERR_ALLOC, "out of host memory");
@@ -48,7 +49,19 @@ int mat_alloc(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t
     m->ncol   = ncol;
     m->nnz    = nnz;
     m->k      = k;
-    m->owned  = true;
+    m->a      = a;
+    m->b      = b;
+    m->v      = v;
+    m->owned  = false;
+    *out      = m;
+    return SPMV_OK;
+}
+
+int mat_alloc(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t nnz, int32_t k, size_t a_count,
+              size_t b_count, size_t v_count, spmv_mat** out)
+{
+    spmv_mat* m = nullptr;
+    SPMV_TRY(wrap(ctx, format, nrow, ncol, nnz, k, nullptr, nullptr, nullptr, &m));
     void *a = nullptr, *b = nullptr, *v = nullptr;
     hipError_t e = hipSuccess;
     // a zero-length array still gets a valid (tiny) allocation so that kernels never see nullptr
@@ -67,6 +80,7 @@ int mat_alloc(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t
     m->a            = (const int32_t*)a;
     m->b            = (const int32_t*)b;
     m->v            = (const double*)v;
+    m->owned        = true;
     m->device_bytes = (int64_t)((a_count + b_count) * sizeof(int32_t) + v_count * sizeof(double));
     *out            = m;
     return SPMV_OK;
@@ -88,11 +102,7 @@ void mat_free(spmv_mat* m)
     if (m->ell_diag_mask) (void)hipFree(m->ell_diag_mask);
     ell_free_tiles(m);
     ell_free_dia_order(m);
-    csr_panel_free(m);
-    csr_twophase_free(m);
-    csr_segscan_free(m);
-    csr_split_free(m);
-    csr_ell_copy_free(m);
+    csr_layouts_free(m, kCsrAllLayouts);
     symgs_free(m);
     if (m->rowgrouped) mat_free(m->rowgrouped);
     coo_free_bins(m);
@@ -113,23 +123,14 @@ static int upload(void* dst, const void* src, size_t bytes, spmv_ctx* ctx)
     return SPMV_OK;
 }
 
-static int wrap(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t nnz, int32_t k, const int32_t* a,
-                const int32_t* b, const double* v, spmv_mat** out)
+// the host arrays of a new handle into its a / b / v (a count of 0 skips one); the handle is freed on failure
+static int upload_arrays(spmv_mat* m, const int32_t* a, size_t a_count, const int32_t* b, size_t b_count, const double* v, size_t v_count)
 {
-    spmv_mat* m = new (std::nothrow) spmv_mat();
-    if (!m) SPMV_FAIL(SPMV_ERR_ALLOC, "out of host memory");
-    m->ctx    = ctx;
-    m->format = format;
-    m->nrow   = nrow;
-    m->ncol   = ncol;
-    m->nnz    = nnz;
-    m->k      = k;
-    m->a      = a;
-    m->b      = b;
-    m->v      = v;
-    m->owned  = false;
-    *out      = m;
-    return SPMV_OK;
+    int rc = upload(const_cast<int32_t*>(m->a), a, sizeof(int32_t) * a_count, m->ctx);
+    if (rc == SPMV_OK) rc = upload(const_cast<int32_t*>(m->b), b, sizeof(int32_t) * b_count, m->ctx);
+    if (rc == SPMV_OK) rc = upload(const_cast<double*>(m->v), v, sizeof(double) * v_count, m->ctx);
+    if (rc != SPMV_OK) mat_free(m);
+    return rc;
 }
 
 // spmv_ctx_set_plan: the handle a public entry point is about to create takes the context's plan (plan.hip: plan_take_armed, at
@@ -164,35 +165,6 @@ static int finish(spmv_mat* m, spmv_mat** out)
     *out = m;
     return SPMV_OK;
 }
-// Does a product of this handle add into y with device atomics (global_atomic_add_f64)?  Decided by the kernel that RUNS,
-// followed through the copies a handle may run from: the COO scan (in place or over column bins) and the CSC scatter; CSR
-// handles under SPMV_CSR_SEGSCAN (the same scan over a row index per entry) and SPMV_CSR_SPLIT in chunk mode (one atomic add
-// per chunk of a long row; the virtual-row mode adds its partial sums up in a scratch vector of its own and onto y with a plain
-// read and store); and any handle whose row-grouped copy, short-row copy or ELL copy runs one of those.  Everything else
-// touches every y_i once with a plain read and a plain store.  spmv_apply_host decides from this where y may live.
-bool adds_into_y_with_atomics(const spmv_mat* A)
-{
-    if (!A) return false;
-    switch (A->format)
-    {
-        case SPMV_FMT_COO:
-        case SPMV_FMT_CSC:
-            return runs_from_rowgrouped(A) ? adds_into_y_with_atomics(A->rowgrouped) : true;
-        case SPMV_FMT_ELL: return runs_from_rowgrouped(A) ? adds_into_y_with_atomics(A->rowgrouped) : false;
-        case SPMV_FMT_CSR:
-            switch (A->kernel)
-            {
-                case SPMV_CSR_SEGSCAN: return true;
-                case SPMV_CSR_SPLIT:
-                    // the short rows' copy picks a kernel of its own; long rows: chunks add atomically, virtual rows do not
-                    return adds_into_y_with_atomics(A->split_short) || (!A->split_long && A->split_nchunks > 0);
-                case SPMV_CSR_ELL: return adds_into_y_with_atomics(A->ell_copy);
-                default: return false;
-            }
-        default: return false;  // DIA
-    }
-}
-
 }  // namespace spmv
 
 using namespace spmv;
@@ -545,14 +517,7 @@ int spmv_csr_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, const int32_t* ro
     plan_arm arm(ctx);
     spmv_mat* m = nullptr;
     SPMV_TRY(mat_alloc(ctx, SPMV_FMT_CSR, nrow, ncol, nnz, 0, (size_t)nrow + 1, (size_t)nnz, (size_t)nnz, &m));
-    int rc = upload(const_cast<int32_t*>(m->a), row_ptr, sizeof(int32_t) * ((size_t)nrow + 1), ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<int32_t*>(m->b), col_ind, sizeof(int32_t) * (size_t)nnz, ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<double*>(m->v), values, sizeof(double) * (size_t)nnz, ctx);
-    if (rc != SPMV_OK)
-    {
-        mat_free(m);
-        return rc;
-    }
+    SPMV_TRY(upload_arrays(m, row_ptr, (size_t)nrow + 1, col_ind, (size_t)nnz, values, (size_t)nnz));
     return finish(m, out);
 }
 
@@ -589,14 +554,7 @@ int spmv_csr_upload_shard(spmv_ctx* ctx, int64_t row_begin, int64_t row_end, int
     for (int32_t j = 0; j <= nrow; ++j) sub[j] = (int32_t)(row_ptr64[row_begin + j] - base);
     spmv_mat* m = nullptr;
     SPMV_TRY(mat_alloc(ctx, SPMV_FMT_CSR, nrow, ncol, nnz, 0, (size_t)nrow + 1, (size_t)nnz, (size_t)nnz, &m));
-    int rc = upload(const_cast<int32_t*>(m->a), sub.data(), sizeof(int32_t) * sub.size(), ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<int32_t*>(m->b), col_ind + base, sizeof(int32_t) * (size_t)nnz, ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<double*>(m->v), values + base, sizeof(double) * (size_t)nnz, ctx);
-    if (rc != SPMV_OK)
-    {
-        mat_free(m);
-        return rc;
-    }
+    SPMV_TRY(upload_arrays(m, sub.data(), sub.size(), col_ind + base, (size_t)nnz, values + base, (size_t)nnz));
     m->row_begin = row_begin;
     return finish(m, out);
 }
@@ -610,14 +568,7 @@ int spmv_coo_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int64_t nnz, cons
     plan_arm arm(ctx);
     spmv_mat* m = nullptr;
     SPMV_TRY(mat_alloc(ctx, SPMV_FMT_COO, nrow, ncol, nnz, 0, (size_t)nnz, (size_t)nnz, (size_t)nnz, &m));
-    int rc = upload(const_cast<int32_t*>(m->a), row_ind, sizeof(int32_t) * (size_t)nnz, ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<int32_t*>(m->b), col_ind, sizeof(int32_t) * (size_t)nnz, ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<double*>(m->v), values, sizeof(double) * (size_t)nnz, ctx);
-    if (rc != SPMV_OK)
-    {
-        mat_free(m);
-        return rc;
-    }
+    SPMV_TRY(upload_arrays(m, row_ind, (size_t)nnz, col_ind, (size_t)nnz, values, (size_t)nnz));
     return finish(m, out);
 }
 
@@ -642,13 +593,7 @@ int spmv_ell_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int32_t k, int64_
     plan_arm arm(ctx);
     spmv_mat* m = nullptr;
     SPMV_TRY(mat_alloc(ctx, SPMV_FMT_ELL, nrow, ncol, nnz, k, 0, total, total, &m));
-    int rc = upload(const_cast<int32_t*>(m->b), col_ind, sizeof(int32_t) * total, ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<double*>(m->v), values, sizeof(double) * total, ctx);
-    if (rc != SPMV_OK)
-    {
-        mat_free(m);
-        return rc;
-    }
+    SPMV_TRY(upload_arrays(m, nullptr, 0, col_ind, total, values, total));
     m->max_row_nnz = k;
     return finish(m, out);
 }
@@ -674,14 +619,7 @@ int spmv_csc_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, const int32_t* co
     plan_arm arm(ctx);
     spmv_mat* m = nullptr;
     SPMV_TRY(mat_alloc(ctx, SPMV_FMT_CSC, nrow, ncol, nnz, 0, (size_t)ncol + 1, (size_t)nnz, (size_t)nnz, &m));
-    int rc = upload(const_cast<int32_t*>(m->a), col_ptr, sizeof(int32_t) * ((size_t)ncol + 1), ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<int32_t*>(m->b), row_ind, sizeof(int32_t) * (size_t)nnz, ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<double*>(m->v), values, sizeof(double) * (size_t)nnz, ctx);
-    if (rc != SPMV_OK)
-    {
-        mat_free(m);
-        return rc;
-    }
+    SPMV_TRY(upload_arrays(m, col_ptr, (size_t)ncol + 1, row_ind, (size_t)nnz, values, (size_t)nnz));
     return finish(m, out);
 }
 
@@ -701,13 +639,7 @@ int spmv_dia_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int32_t ndiags, c
         m->dia_off_min   = *std::min_element(offsets, offsets + ndiags);
         m->dia_off_max   = *std::max_element(offsets, offsets + ndiags);
     }
-    int rc = upload(const_cast<int32_t*>(m->a), offsets, sizeof(int32_t) * (size_t)ndiags, ctx);
-    if (rc == SPMV_OK) rc = upload(const_cast<double*>(m->v), values, sizeof(double) * total, ctx);
-    if (rc != SPMV_OK)
-    {
-        mat_free(m);
-        return rc;
-    }
+    SPMV_TRY(upload_arrays(m, offsets, (size_t)ndiags, nullptr, 0, values, total));
     return finish(m, out);
 }
 
@@ -744,18 +676,6 @@ int spmv_mat_get_info(const spmv_mat* m, spmv_mat_info* info)
     return SPMV_OK;
 }
 
-// a CSR handle holds the layout of its own that `kernel` multiplies from (kernel_reads_own_layout: the others have none)
-static bool own_layout_built(const spmv_mat* m, int32_t kernel)
-{
-    switch (kernel)
-    {
-        case SPMV_CSR_PANEL: return m->pb_val;
-        case SPMV_CSR_TWOPHASE: return m->tp_val;
-        case SPMV_CSR_ELL: return m->ell_copy;
-        default: return false;
-    }
-}
-
 int spmv_mat_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes_per_row)
 {
     SPMV_REQUIRE(m, "null matrix");
@@ -767,7 +687,7 @@ int spmv_mat_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes_per_row)
     // COO, CSC, ELL: the format's own kernel or the row-grouped copy (rowgrouped.hip)
     if (m->format == SPMV_FMT_COO || m->format == SPMV_FMT_CSC || m->format == SPMV_FMT_ELL) return rowgrouped_set_kernel(m, kernel);
     if (m->format == SPMV_FMT_CSR && m->nnz > 0 && (!m->b || !m->v))
-        SPMV_REQUIRE(own_layout_built(m, kernel) || (kernel == SPMV_CSR_AUTO && kernel_reads_own_layout(m->kernel)),
+        SPMV_REQUIRE(csr_layout_built(m, kernel) || (kernel == SPMV_CSR_AUTO && kernel_reads_own_layout(m->kernel)),
                      "this handle gave up its CSR arrays (panel_keep_csr = 0): only the product it was built for is left");
     if (kernel == SPMV_CSR_AUTO)
     {
@@ -784,38 +704,17 @@ int spmv_mat_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes_per_row)
         m->kernel_forced  = true;
         m->split_auto_low = false;  // (a forced SPLIT takes "split_row_threshold" or its default, not what AUTO found)
     }
-    if (m->kernel != SPMV_CSR_SEGSCAN) csr_segscan_free(m);
-    if (m->format == SPMV_FMT_CSR && m->kernel != SPMV_CSR_SPLIT) csr_split_free(m);
-    if (m->kernel != SPMV_CSR_ELL) csr_ell_copy_free(m);
-    if (m->format == SPMV_FMT_CSR && m->kernel == SPMV_CSR_PANEL)
+    if (m->format != SPMV_FMT_CSR)  // a DIA handle: it has one kernel, and no layout of a CSR kernel to free or build
     {
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        SPMV_TRY(csr_panel_build(m));  // (re)build with the current parameters
+        SPMV_REQUIRE(m->kernel != SPMV_CSR_SEGSCAN, "kernel SEGSCAN (6) is a CSR kernel (a COO handle's VECTOR is the same scan)");
+        SPMV_REQUIRE(m->kernel != SPMV_CSR_SPLIT, "kernel SPLIT (7) is a CSR kernel");
+        SPMV_REQUIRE(m->kernel != SPMV_CSR_ELL, "kernel ELL (8) is a CSR kernel: the ELL copy of a CSR handle");
+        return SPMV_OK;
     }
-    if (m->format == SPMV_FMT_CSR && m->kernel == SPMV_CSR_TWOPHASE)
-    {
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        SPMV_TRY(csr_twophase_build(m));
-    }
-    if (m->kernel == SPMV_CSR_SEGSCAN)
-    {
-        SPMV_REQUIRE(m->format == SPMV_FMT_CSR, "kernel SEGSCAN (6) is a CSR kernel (a COO handle's VECTOR is the same scan)");
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        SPMV_TRY(csr_segscan_build(m));
-    }
-    if (m->kernel == SPMV_CSR_SPLIT)
-    {
-        SPMV_REQUIRE(m->format == SPMV_FMT_CSR, "kernel SPLIT (7) is a CSR kernel");
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        SPMV_TRY(csr_split_build(m));
-    }
-    if (m->kernel == SPMV_CSR_ELL)
-    {
-        SPMV_REQUIRE(m->format == SPMV_FMT_CSR, "kernel ELL (8) is a CSR kernel: the ELL copy of a CSR handle");
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        SPMV_TRY(csr_ell_copy_build(m));
-    }
-    return SPMV_OK;
+    // a built panel or two-phase layout is KEPT under another kernel (device_bytes and panel_bytes go on counting it); the other three go
+    csr_layouts_free(m, ((1u << SPMV_CSR_SEGSCAN) | (1u << SPMV_CSR_SPLIT) | (1u << SPMV_CSR_ELL)) & ~(1u << m->kernel));
+    SPMV_HIP(hipSetDevice(m->ctx->device));
+    return csr_layout_build(m, m->kernel);  // (re)build with the current parameters
 }
 
 int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
@@ -861,7 +760,7 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
         SPMV_REQUIRE(value == 0 || (m->b && m->v) || m->nnz == 0, "panel_keep_csr: the arrays are gone already");
         if (value == 0 && m->b && m->v)
         {
-            SPMV_REQUIRE(m->format == SPMV_FMT_CSR && m->owned && own_layout_built(m, m->kernel),
+            SPMV_REQUIRE(m->format == SPMV_FMT_CSR && m->owned && csr_layout_built(m, m->kernel),
                          "panel_keep_csr = 0 needs an owned CSR handle whose panel or two-phase layout or ELL copy is built");
             SPMV_HIP(hipSetDevice(m->ctx->device));
             SPMV_HIP(hipStreamSynchronize(m->ctx->stream));
@@ -1048,6 +947,7 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         *value = m->pb_built_sort;
     else if (!strcmp(name, "panel_groups"))
         *value = m->pb_ngroups;
+    // (panel_unroll / panel_pipe / panel_sync echo a REQUEST, aliases applied; a launch runs panel_effective, equal on every documented value)
     else if (!strcmp(name, "panel_unroll"))
         *value = std::min(8, m->pb_unroll > 0 ? m->pb_unroll : (m->pb_unroll_tuned > 0 ? m->pb_unroll_tuned : 8));  // (16 runs 8 since round 4)
     else if (!strcmp(name, "panel_bytes"))
@@ -1091,15 +991,13 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         *value = m->sel_rounds;
     else if (!strncmp(name, "select_us_", 10))
     {
-        static const char* const kNames[] = {"", "vector", "ldswin", "scalar", "panel", "twophase", "variant1", "variant2"};
         int slot = -1;
-        for (int i = 1; i < 8; ++i)
-            if (!strcmp(name + 10, kNames[i])) slot = i;
-        if (!strcmp(name + 10, "segscan")) slot = SPMV_CSR_SEGSCAN;  // (CSR handles; the slots are an ELL handle's "variant1" / "variant2")
-        if (!strcmp(name + 10, "split")) slot = SPMV_CSR_SPLIT;
-        if (!strcmp(name + 10, "split_low")) slot = 0;
+        for (int i = SPMV_CSR_VECTOR; i <= SPMV_CSR_ELL; ++i)  // the slot of a CSR kernel is its id
+            if (!strcmp(name + 10, csr_kernel_name(i))) slot = i;
+        if (!strcmp(name + 10, "variant1")) slot = 6;  // ELL / COO handles: the slots that are "segscan" / "split" on a CSR handle
+        if (!strcmp(name + 10, "variant2")) slot = 7;
+        if (!strcmp(name + 10, "split_low")) slot = 0;  // kernel SPLIT with rows of 256 entries and more split off (timed from 8M entries on)
         if (!strcmp(name + 10, "dia_order")) slot = 9;  // ELL handles: the DIA-order copy of the values
-        if (!strcmp(name + 10, "ell")) slot = SPMV_CSR_ELL;  // CSR handles: the ELL copy of (nearly) equal rows  // kernel SPLIT with rows of 256 entries and more split off (timed from 8M entries on)
         SPMV_REQUIRE(slot >= 0, "unknown parameter '%s'", name);
         *value = (int64_t)(m->sel_us[slot] + 0.5f);
     }
@@ -1182,19 +1080,6 @@ int spmv_mat_device_ptrs(const spmv_mat* m, const int32_t** a, const int32_t** b
 }
 
 // ---- the hot path -----------------------------------------------------------------------------------------
-static int apply_checked(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y)
-{
-    switch (A->format)
-    {
-        case SPMV_FMT_CSR: return csr_apply(ctx, A, x->d, y->d);
-        case SPMV_FMT_ELL: return ell_apply(ctx, A, x->d, y->d);
-        case SPMV_FMT_COO: return coo_apply(ctx, A, x->d, y->d);
-        case SPMV_FMT_CSC: return csc_apply(ctx, A, x->d, y->d);
-        case SPMV_FMT_DIA: return dia_apply(ctx, A, x->d, y->d);
-        default: SPMV_FAIL(SPMV_ERR_INVALID, "unknown format %d", A->format);
-    }
-}
-
 static int check_apply_args(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y)
 {
     SPMV_REQUIRE(ctx && A && x && y, "spmv_apply: null argument");
@@ -1209,7 +1094,7 @@ int spmv_apply(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y)
 {
     SPMV_TRY(check_apply_args(ctx, A, x, y));
     SPMV_TRY(use_device(ctx));
-    return apply_checked(ctx, A, x, y);
+    return mat_apply_ex(ctx, A, x->d, y->d);
 }
 
 int spmv_apply_timed(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y, int32_t reps,
@@ -1218,13 +1103,9 @@ int spmv_apply_timed(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_v
     SPMV_TRY(check_apply_args(ctx, A, x, y));
     SPMV_REQUIRE(reps > 0 && ms_per_apply, "spmv_apply_timed: reps=%d", reps);
     SPMV_TRY(use_device(ctx));
-    SPMV_HIP(hipEventRecord(ctx->ev_begin, ctx->stream));
-    for (int32_t i = 0; i < reps; ++i) SPMV_TRY(apply_checked(ctx, A, x, y));
-    SPMV_HIP(hipEventRecord(ctx->ev_end, ctx->stream));
-    SPMV_HIP(hipEventSynchronize(ctx->ev_end));
     float ms = 0.f;
-    SPMV_HIP(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
-    *ms_per_apply = (double)ms / reps;
+    SPMV_TRY(time_launches(ctx, reps, [&] { return mat_apply_ex(ctx, A, x->d, y->d); }, &ms));
+    *ms_per_apply = ms;
     return SPMV_OK;
 }
 
@@ -1262,13 +1143,9 @@ int spmv_apply_multi_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const sp
     SPMV_TRY(check_apply_multi_args(ctx, A, k, X, Y));
     SPMV_REQUIRE(reps > 0 && ms_per_apply, "spmv_apply_multi_timed: reps=%d", reps);
     SPMV_TRY(use_device(ctx));
-    SPMV_HIP(hipEventRecord(ctx->ev_begin, ctx->stream));
-    for (int32_t i = 0; i < reps; ++i) SPMV_TRY(spmm_apply(ctx, A, k, X->d, Y->d, overwrite != 0));
-    SPMV_HIP(hipEventRecord(ctx->ev_end, ctx->stream));
-    SPMV_HIP(hipEventSynchronize(ctx->ev_end));
     float ms = 0.f;
-    SPMV_HIP(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
-    *ms_per_apply = (double)ms / reps;
+    SPMV_TRY(time_launches(ctx, reps, [&] { return spmm_apply(ctx, A, k, X->d, Y->d, overwrite != 0); }, &ms));
+    *ms_per_apply = ms;
     return SPMV_OK;
 }
 
@@ -1325,12 +1202,8 @@ int spmv_apply_host(spmv_ctx* ctx, const spmv_mat* A, const double* x_host, doub
     if (ctx->stage_x_n < std::max<size_t>(nx, 1) || ctx->stage_y_n < ny) SPMV_HIP(hipStreamSynchronize(ctx->stream));
     SPMV_TRY(grow(&ctx->stage_x, &ctx->stage_x_n, std::max<size_t>(nx, 1)));
     SPMV_TRY(grow(&ctx->stage_y, &ctx->stage_y_n, ny));
-    spmv_vec vx, vy;
-    vx.ctx = vy.ctx = ctx;
-    vx.n            = (int64_t)nx;
-    vx.d            = ctx->stage_x;
-    vy.n            = (int64_t)ny;
-    vy.d            = ctx->stage_y;
+    const double* dx = ctx->stage_x;
+    double*       dy = ctx->stage_y;
     // (SPMV_HOST_STAGED_MB: the limit in megabytes, for tools/probe_apply_host_sizes.py; read per call, this is not a product's path
     // that anything is measured on)
     static const size_t kStagedLimit = [] {
@@ -1381,8 +1254,7 @@ int spmv_apply_host(spmv_ctx* ctx, const spmv_mat* A, const double* x_host, doub
         //     accumulator starts AT y_i (ELL, DIA, scalar CSR: the reference's order y0 + p0 + p1 + ...) keep y in place.
         const spmv_mat* K = A;  // the handle whose kernel runs
         while (runs_from_rowgrouped(K)) K = K->rowgrouped;
-        const bool sum_then_add = y_in_place && !kForceInPlace && K->format == SPMV_FMT_CSR && K->nnz > 0 &&
-                                  (K->kernel == SPMV_CSR_VECTOR || K->kernel == SPMV_CSR_AUTO || K->kernel == SPMV_CSR_PANEL || K->kernel == SPMV_CSR_TWOPHASE);
+        const bool sum_then_add = y_in_place && !kForceInPlace && K->format == SPMV_FMT_CSR && K->nnz > 0 && writes_row_sums_in_one_launch(K);
         if (nx && !ctx->large_bar) memcpy(hx, x_host, sizeof(double) * nx);
         if (!sum_then_add) memcpy(hy, y_host, sizeof(double) * ny);
         // x: where the CPU can store into device memory (large BAR) it writes x into the device buffer itself - 80 KB in 2 us,
@@ -1398,21 +1270,16 @@ int spmv_apply_host(spmv_ctx* ctx, const spmv_mat* A, const double* x_host, doub
         }
         if (y_in_place)
         {
-            vy.d = ctx->stage_pinned_dev + nx;
+            dy = ctx->stage_pinned_dev + nx;
             if (!direct) SPMV_TRY(vec_copy2(ctx, ctx->stage_x, ctx->stage_pinned_dev, (int64_t)nx, nullptr, nullptr, 0));
-            if (sum_then_add)
-            {
-                apply_extra ex;
-                ex.overwrite = true;
-                SPMV_TRY(mat_apply_ex(ctx, A, vx.d, vy.d, ex));
-            }
-            else
-                SPMV_TRY(apply_checked(ctx, A, &vx, &vy));
+            apply_extra ex;
+            ex.overwrite = sum_then_add;
+            SPMV_TRY(mat_apply_ex(ctx, A, dx, dy, ex));
         }
         else
         {
             SPMV_TRY(vec_copy2(ctx, ctx->stage_x, ctx->stage_pinned_dev, direct ? 0 : (int64_t)nx, ctx->stage_y, ctx->stage_pinned_dev + nx, (int64_t)ny));
-            SPMV_TRY(apply_checked(ctx, A, &vx, &vy));
+            SPMV_TRY(mat_apply_ex(ctx, A, dx, dy));
             SPMV_TRY(vec_copy2(ctx, ctx->stage_pinned_dev + nx, ctx->stage_y, (int64_t)ny, nullptr, nullptr, 0));
         }
         SPMV_TRY(host_wait(ctx));
@@ -1424,7 +1291,7 @@ int spmv_apply_host(spmv_ctx* ctx, const spmv_mat* A, const double* x_host, doub
     }
     if (nx) SPMV_HIP(hipMemcpyAsync(ctx->stage_x, x_host, sizeof(double) * nx, hipMemcpyHostToDevice, ctx->stream));
     SPMV_HIP(hipMemcpyAsync(ctx->stage_y, y_host, sizeof(double) * ny, hipMemcpyHostToDevice, ctx->stream));
-    SPMV_TRY(apply_checked(ctx, A, &vx, &vy));
+    SPMV_TRY(mat_apply_ex(ctx, A, dx, dy));
     SPMV_HIP(hipMemcpyAsync(y_host, ctx->stage_y, sizeof(double) * ny, hipMemcpyDeviceToHost, ctx->stream));
     SPMV_HIP(hipStreamSynchronize(ctx->stream));
     return SPMV_OK;

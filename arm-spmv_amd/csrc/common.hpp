@@ -367,10 +367,18 @@ int ensure_scratch(spmv_ctx* ctx, size_t bytes);
 
 // kernels_csr.hip
 int csr_analyse(spmv_mat* m);
+// the layouts of their own that five of the CSR kernels multiply from (panel, two-phase, segmented scan, long-row split, ELL copy)
+int  csr_layout_build(spmv_mat* m, int32_t kernel);       // (re)builds `kernel`'s with the current parameters; VECTOR, LDSWIN, SCALAR: nothing
+void csr_layouts_free(spmv_mat* m, uint32_t kernels);     // frees those of the kernels whose bit 1u << id is set
+bool csr_layout_built(const spmv_mat* m, int32_t kernel);  // kernel_reads_own_layout(kernel) and that layout is in memory
+constexpr uint32_t kCsrAllLayouts = ~0u;
+const char* csr_kernel_name(int32_t kernel);  // "vector" .. "ell" for VECTOR .. ELL ("select_us_<kernel>")
 void csr_choose_kernel(spmv_mat* m);  // the model's pick (no launches)
 int  csr_ldswin_capacity();           // columns of x the LDS-window kernel's tile holds
 // select.hip: AUTO by measurement
 bool select_trials_enabled(const spmv_mat* m);
+// ms per launch of n launches between the context's two events (ev_begin / ev_end); a launch that fails ends it with that code
+int  time_launches(spmv_ctx* ctx, int n, const std::function<int()>& launch, float* ms_per_launch);
 int  csr_select_kernel(spmv_mat* m);
 // zeroed x (ncol) and y (nrow) for timing launches; freed with the object
 struct select_scratch
@@ -420,14 +428,16 @@ struct apply_extra
 };
 int  csr_panel_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex);
 int  csr_twophase_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex);
-bool csr_vector_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex, int* rc);
+// kernels_csr.hip: the product dispatch.  mat_apply_ex is the one function that decides which kernel a forward product of a
+// handle (any format) runs; csr_apply is its CSR half (the trials time candidates through it)
+int  mat_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex = apply_extra{});
+int  csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex = apply_extra{});
+bool writes_row_sums_in_one_launch(const spmv_mat* A);  // the product can store sum_i instead of y_i + sum_i at no extra launch
+bool adds_into_y_with_atomics(const spmv_mat* A);       // global_atomic_add_f64 on y, by the kernel (of the handle or its copies) that runs
 // solver.hip
-int mat_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
-int mat_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex);
 int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
              int precond, int* iters, double* rel_resid);
 int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t n, double* device_out);
-int csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 // kernels_ell.hip
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int ell_analyse(spmv_mat* m);
@@ -453,7 +463,6 @@ int  csr_segscan_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double
 int  csr_split_build(spmv_mat* m);
 void csr_split_free(spmv_mat* m);
 int  csr_split_threshold(const spmv_mat* m);
-int  csr_split_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int  csr_split_long_rows_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 // kernels_spmm.hip: Y += A*X (Y = A*X) for k row-major vectors, CSR and ELL handles, over the handle's own arrays
 int spmm_apply(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* X, double* Y, bool overwrite);
@@ -535,5 +544,4 @@ bool transpose_get_param(const spmv_mat* A, const char* name, int64_t* value);  
 int  mat_alloc(spmv_ctx* ctx, int32_t format, int32_t nrow, int32_t ncol, int64_t nnz, int32_t k,
                size_t a_count, size_t b_count, size_t v_count, spmv_mat** out);
 void mat_free(spmv_mat* m);
-bool adds_into_y_with_atomics(const spmv_mat* A);  // global_atomic_add_f64 on y, by the kernel (of the handle or its copies) that runs
 }  // namespace spmv

@@ -635,7 +635,6 @@ int csr_segscan_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double*
 int coo_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
 {
     if (A->nnz == 0) return SPMV_OK;
-    if (runs_from_rowgrouped(A)) return csr_apply(ctx, A->rowgrouped, x, y);
     return coo_scan_apply(ctx, A, x, y);
 }
 

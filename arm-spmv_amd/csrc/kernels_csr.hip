@@ -442,32 +442,102 @@ int csr_analyse(spmv_mat* m)
     int rc;
     if (plan_analyse(m, &rc)) return rc;  // the plan's kernel and layout, no timing launch (select.hip)
     if (!m->kernel_forced) return csr_select_kernel(m);  // the model, and where it pays a trial of the candidates (select.hip)
-    if (m->kernel == SPMV_CSR_PANEL) SPMV_TRY(csr_panel_build(m));
-    if (m->kernel == SPMV_CSR_TWOPHASE) SPMV_TRY(csr_twophase_build(m));
-    if (m->kernel == SPMV_CSR_SEGSCAN) SPMV_TRY(csr_segscan_build(m));
-    if (m->kernel == SPMV_CSR_SPLIT) SPMV_TRY(csr_split_build(m));
-    if (m->kernel == SPMV_CSR_ELL) SPMV_TRY(csr_ell_copy_build(m));
-    return SPMV_OK;
+    return csr_layout_build(m, m->kernel);
 }
 
-// the row-parallel kernel with the solver's extras fused into its write-back; false if another kernel is selected
-bool csr_vector_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex, int* rc)
+// ---- the layouts of their own that CSR kernels multiply from ---------------------------------------------------------------
+const char* csr_kernel_name(int32_t kernel)
 {
-    if (A->nrow == 0 || (A->kernel != SPMV_CSR_VECTOR && A->kernel != SPMV_CSR_AUTO)) return false;
-    const int  lanes = A->lanes_per_row > 0 ? A->lanes_per_row : 8;
-    const bool dpp = A->flags & SPMV_FLAG_DPP_REDUCE, remap = A->flags & SPMV_FLAG_XCD_REMAP;
-    if (dpp && remap)
-        *rc = launch_vector<true, true>(ctx, A, x, y, lanes, ex);
-    else if (dpp)
-        *rc = launch_vector<true, false>(ctx, A, x, y, lanes, ex);
-    else if (remap)
-        *rc = launch_vector<false, true>(ctx, A, x, y, lanes, ex);
-    else
-        *rc = launch_vector<false, false>(ctx, A, x, y, lanes, ex);
-    return true;
+    // (inside a host function: a constant array at namespace scope of a .hip file is emitted into the device code object too)
+    static const char* const kNames[SPMV_CSR_ELL + 1] = {"", "vector", "ldswin", "scalar", "panel", "twophase", "segscan", "split", "ell"};
+    return kNames[kernel];
 }
 
-int csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
+int csr_layout_build(spmv_mat* m, int32_t kernel)
+{
+    switch (kernel)
+    {
+        case SPMV_CSR_PANEL: return csr_panel_build(m);
+        case SPMV_CSR_TWOPHASE: return csr_twophase_build(m);
+        case SPMV_CSR_SEGSCAN: return csr_segscan_build(m);
+        case SPMV_CSR_SPLIT: return csr_split_build(m);
+        case SPMV_CSR_ELL: return csr_ell_copy_build(m);
+        default: return SPMV_OK;  // VECTOR, LDSWIN, SCALAR: the CSR arrays as they are
+    }
+}
+
+void csr_layouts_free(spmv_mat* m, uint32_t kernels)
+{
+    if (kernels & (1u << SPMV_CSR_PANEL)) csr_panel_free(m);
+    if (kernels & (1u << SPMV_CSR_TWOPHASE)) csr_twophase_free(m);
+    if (kernels & (1u << SPMV_CSR_SEGSCAN)) csr_segscan_free(m);
+    if (kernels & (1u << SPMV_CSR_SPLIT)) csr_split_free(m);
+    if (kernels & (1u << SPMV_CSR_ELL)) csr_ell_copy_free(m);
+}
+
+bool csr_layout_built(const spmv_mat* m, int32_t kernel)
+{
+    switch (kernel)
+    {
+        case SPMV_CSR_PANEL: return m->pb_val;
+        case SPMV_CSR_TWOPHASE: return m->tp_val;
+        case SPMV_CSR_ELL: return m->ell_copy;
+        default: return false;
+    }
+}
+
+// ---- the product dispatch ---------------------------------------------------------------------------------------------------
+// The CSR kernels that form a row's sum and store it in one step take apply_extra (y = A x, the dot product w . y) into their
+// write-back: the row-parallel kernel (also what AUTO runs before a kernel is selected), panel and two-phase in ONE launch;
+// the long-row split in the kernel of its short rows, the long rows added on top and the dot product over the finished y.
+// Whoever adds a branch to csr_apply that fuses the extras adds it to the predicate its launch count belongs to.
+static bool csr_kernel_fuses_in_one_launch(int32_t kernel)
+{
+    return kernel == SPMV_CSR_VECTOR || kernel == SPMV_CSR_AUTO || kernel == SPMV_CSR_PANEL || kernel == SPMV_CSR_TWOPHASE;
+}
+bool writes_row_sums_in_one_launch(const spmv_mat* A)
+{
+    while (runs_from_rowgrouped(A)) A = A->rowgrouped;
+    return A->format == SPMV_FMT_CSR && csr_kernel_fuses_in_one_launch(A->kernel);
+}
+static bool fuses_extras(const spmv_mat* A)
+{
+    if (A->format != SPMV_FMT_CSR || A->nrow == 0) return false;
+    if (A->kernel == SPMV_CSR_SPLIT) return A->split_short;
+    return csr_kernel_fuses_in_one_launch(A->kernel) && (A->kernel != SPMV_CSR_PANEL || A->nnz > 0);
+}
+
+// Does a product of this handle add into y with device atomics (global_atomic_add_f64)?  Decided by the kernel that RUNS,
+// followed through the copies a handle may run from: the COO scan (in place or over column bins) and the CSC scatter; CSR
+// handles under SPMV_CSR_SEGSCAN (the same scan over a row index per entry) and SPMV_CSR_SPLIT in chunk mode (one atomic add
+// per chunk of a long row; the virtual-row mode adds its partial sums up in a scratch vector of its own and onto y with a plain
+// read and store); and any handle whose row-grouped copy, short-row copy or ELL copy runs one of those.  Everything else
+// touches every y_i once with a plain read and a plain store.  spmv_apply_host decides from this where y may live.
+bool adds_into_y_with_atomics(const spmv_mat* A)
+{
+    if (!A) return false;
+    switch (A->format)
+    {
+        case SPMV_FMT_COO:
+        case SPMV_FMT_CSC:
+            return runs_from_rowgrouped(A) ? adds_into_y_with_atomics(A->rowgrouped) : true;
+        case SPMV_FMT_ELL: return runs_from_rowgrouped(A) ? adds_into_y_with_atomics(A->rowgrouped) : false;
+        case SPMV_FMT_CSR:
+            switch (A->kernel)
+            {
+                case SPMV_CSR_SEGSCAN: return true;
+                case SPMV_CSR_SPLIT:
+                    // the short rows' copy picks a kernel of its own; long rows: chunks add atomically, virtual rows do not
+                    return adds_into_y_with_atomics(A->split_short) || (!A->split_long && A->split_nchunks > 0);
+                case SPMV_CSR_ELL: return adds_into_y_with_atomics(A->ell_copy);
+                default: return false;
+            }
+        default: return false;  // DIA
+    }
+}
+
+// The product of a CSR handle.  `ex` asks for something only where fuses_extras(A) (mat_apply_ex sees to that).
+int csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex)
 {
     if (A->nrow == 0) return SPMV_OK;
     const int lanes = A->lanes_per_row > 0 ? A->lanes_per_row : 8;
@@ -483,10 +553,20 @@ int csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
                 SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "LDS-window kernel: widest block window is %d columns, tile holds %d",
                           A->win_max_span, kWinDoubles);
             return launch_ldswin(ctx, A, x, y, lanes);
-        case SPMV_CSR_PANEL: return csr_panel_apply(ctx, A, x, y);
-        case SPMV_CSR_TWOPHASE: return csr_twophase_apply_ex(ctx, A, x, y, apply_extra{});
+        case SPMV_CSR_PANEL: return csr_panel_apply_ex(ctx, A, x, y, ex);
+        case SPMV_CSR_TWOPHASE: return csr_twophase_apply_ex(ctx, A, x, y, ex);
         case SPMV_CSR_SEGSCAN: return csr_segscan_apply(ctx, A, x, y);
-        case SPMV_CSR_SPLIT: return csr_split_apply(ctx, A, x, y);
+        case SPMV_CSR_SPLIT:
+        {
+            if (!A->split_short) SPMV_FAIL(SPMV_ERR_INVALID, "long-row split selected but never built");
+            // the short rows with the overwrite fused into their kernel, the long rows added on top, the dot product over the finished y
+            apply_extra first;
+            first.overwrite = ex.overwrite;
+            SPMV_TRY(mat_apply_ex(ctx, A->split_short, x, y, first));
+            SPMV_TRY(csr_split_long_rows_apply(ctx, A, x, y));
+            if (ex.dot_w) SPMV_TRY(vec_dot_accumulate(ctx, ex.dot_w, y, A->nrow, ex.dot_out));
+            return SPMV_OK;
+        }
         case SPMV_CSR_ELL:
             if (!A->ell_copy) SPMV_FAIL(SPMV_ERR_INVALID, "ELL copy selected but never built");
             return ell_apply(ctx, A->ell_copy, x, y);
@@ -495,11 +575,37 @@ int csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
         default:
         {
             const bool dpp = A->flags & SPMV_FLAG_DPP_REDUCE, remap = A->flags & SPMV_FLAG_XCD_REMAP;
-            if (dpp && remap) return launch_vector<true, true>(ctx, A, x, y, lanes);
-            if (dpp) return launch_vector<true, false>(ctx, A, x, y, lanes);
-            if (remap) return launch_vector<false, true>(ctx, A, x, y, lanes);
-            return launch_vector<false, false>(ctx, A, x, y, lanes);
+            if (dpp && remap) return launch_vector<true, true>(ctx, A, x, y, lanes, ex);
+            if (dpp) return launch_vector<true, false>(ctx, A, x, y, lanes, ex);
+            if (remap) return launch_vector<false, true>(ctx, A, x, y, lanes, ex);
+            return launch_vector<false, false>(ctx, A, x, y, lanes, ex);
         }
+    }
+}
+
+int mat_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex)
+{
+    const bool extras = ex.overwrite || ex.dot_w;
+    // COO / CSC / ELL handles that run from their row-grouped copy: that copy is a CSR handle with a kernel of its own.  (Such a
+    // handle has entries, rows and columns - rowgrouped_build - so none of its format's early returns below is skipped.  An ELL
+    // handle states its entry count itself: extras go to the copy only if that count says there is something to fuse them into.)
+    if (runs_from_rowgrouped(A) && (!extras || (A->nnz > 0 && A->nrow > 0 && A->ncol > 0))) return mat_apply_ex(ctx, A->rowgrouped, x, y, ex);
+    if (extras && !fuses_extras(A))
+    {
+        // every other kernel: y zeroed first, the plain product, the dot product over the finished y
+        if (ex.overwrite) SPMV_TRY(vec_fill(ctx, y, A->nrow, 0.0));
+        SPMV_TRY(mat_apply_ex(ctx, A, x, y));
+        if (ex.dot_w) SPMV_TRY(vec_dot_accumulate(ctx, ex.dot_w, y, A->nrow, ex.dot_out));
+        return SPMV_OK;
+    }
+    switch (A->format)
+    {
+        case SPMV_FMT_CSR: return csr_apply(ctx, A, x, y, ex);
+        case SPMV_FMT_ELL: return ell_apply(ctx, A, x, y);
+        case SPMV_FMT_COO: return coo_apply(ctx, A, x, y);
+        case SPMV_FMT_CSC: return csc_apply(ctx, A, x, y);
+        case SPMV_FMT_DIA: return dia_apply(ctx, A, x, y);
+        default: SPMV_FAIL(SPMV_ERR_INVALID, "unknown format %d", A->format);
     }
 }
 }  // namespace spmv

@@ -43,6 +43,7 @@
 
 #include "common.hpp"
 #include "panel_groups.hpp"
+#include "panel_settings.hpp"
 #include "wave.hpp"
 
 namespace spmv
@@ -822,17 +823,10 @@ int panel_choose_pace(spmv_mat* m)
     if (sv.alloc(ctx, m->ncol, m->nrow) != SPMV_OK) return SPMV_OK;  // no room to try: defaults
     double *x = sv.x, *y = sv.y;
     int  rc    = SPMV_OK;
-    auto timed = [&](int launches, float* ms) -> int {
-        int r = panel_launch(ctx, m, x, y, true, apply_extra{});  // warm
-        if (r != SPMV_OK) return r;
-        (void)hipEventRecord(ctx->ev_begin, ctx->stream);
-        for (int i = 0; i < launches && r == SPMV_OK; ++i) r = panel_launch(ctx, m, x, y, true, apply_extra{});
-        (void)hipEventRecord(ctx->ev_end, ctx->stream);
-        if (r == SPMV_OK && (hipEventSynchronize(ctx->ev_end) != hipSuccess ||
-                             hipEventElapsedTime(ms, ctx->ev_begin, ctx->ev_end) != hipSuccess))
-            r = SPMV_ERR_HIP;
-        *ms /= (float)launches;
-        return r;
+    auto launch = [&] { return panel_launch(ctx, m, x, y, true, apply_extra{}); };
+    auto timed  = [&](int launches, float* ms) -> int {
+        SPMV_TRY(launch());  // warm
+        return time_launches(ctx, launches, launch, ms);
     };
     struct Try
     {
@@ -895,21 +889,17 @@ static int panel_launch(spmv_ctx* ctx, const spmv_mat* A, const double* x, doubl
     // two workgroups share a CU when their accumulators fit twice into the 160 KiB LDS
     const int per_cu = (lds <= 80000 && A->pb_two_per_cu) ? 2 : 1;
     const int grid   = std::min(A->pb_ngroups, kNumCu * per_cu);
-    // chunks of 2, 4 or 8 x 1024 entries.  16 existed through round 3: every instance of it spilled registers to scratch and
-    // ran slower (C2: 1.70 ms against 1.13, the x window of a chunk leaves L2); a request for 16 runs 8.
-    const int unroll_rq = A->pb_unroll > 0 ? A->pb_unroll : (A->pb_unroll_tuned > 0 ? A->pb_unroll_tuned : 8);
-    const int unroll    = unroll_rq >= 16 ? 8 : (unroll_rq >= 8 ? 8 : (unroll_rq >= 4 ? 4 : 2));
-    const int sync_rq   = (A->pb_sync >= 0 ? A->pb_sync : A->pb_sync_tuned) & 3;
-    const int sync      = sync_rq == 2 ? 3 : sync_rq;  // (2 was the split barrier through an LDS counter: measured no better than 3, deleted in round 5)
-    const int layout    = A->pb_pack ? (A->pb_pair ? 4 : 3) : 0;
+    // chunks of 2, 4 or 8 x 1024 entries, their order and barrier: requests, else the trial's, else defaults (panel_settings.hpp;
+    // a chunk of 16 on C2: 1.70 ms against 1.13, the x window of a chunk leaves L2)
+    const panel_settings run = panel_effective(A->pb_unroll, A->pb_unroll_tuned, A->pb_pipe, A->pb_pipe_tuned, A->pb_sync, A->pb_sync_tuned);
+    const int unroll = run.unroll, pipe = run.pipe, sync = run.sync;
+    const int layout = A->pb_pack ? (A->pb_pair ? 4 : 3) : 0;
     // the kernel dereferences exactly these arrays: refuse on the host rather than fault on the GPU
     const bool have = layout >= 3 ? (A->pb_pack && A->pb_sbase && A->pb_soff && A->pb_val && A->pb_rowbits > 0 && A->pb_rowbits < 32)
                                   : (A->pb_col && A->pb_row && A->pb_val);
     if (!A->pb_gstart || !x || !y || !have)
         SPMV_FAIL(SPMV_ERR_INVALID, "panel kernel: layout %d is selected but its arrays are not there", layout);
     const int32_t* arg_col = layout >= 3 ? (const int32_t*)A->pb_pack : A->pb_col;
-    const int      pipe_rq = A->pb_pipe >= 0 ? A->pb_pipe : (A->pb_pipe_tuned > 0 ? A->pb_pipe_tuned : 1);
-    const int      pipe    = std::max(0, std::min(pipe_rq, 2));
 #define SPMV_PANEL_PP(U, LY, OR, TR, SY)                                                                                               \
     {                                                                                                                                  \
         static std::atomic<unsigned long long> granted{0}; /* bit per device */                                                        \

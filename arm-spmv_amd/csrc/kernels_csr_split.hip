@@ -354,11 +354,4 @@ int csr_split_long_rows_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x,
     SPMV_HIP(hipGetLastError());
     return SPMV_OK;
 }
-
-int csr_split_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
-{
-    if (!A->split_short) SPMV_FAIL(SPMV_ERR_INVALID, "long-row split selected but never built");
-    SPMV_TRY(csr_apply(ctx, A->split_short, x, y));
-    return csr_split_long_rows_apply(ctx, A, x, y);
-}
 }  // namespace spmv

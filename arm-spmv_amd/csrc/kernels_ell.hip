@@ -979,7 +979,6 @@ int ell_apply_plan(spmv_mat* m)
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
 {
     if (A->nrow == 0) return SPMV_OK;
-    if (runs_from_rowgrouped(A)) return csr_apply(ctx, A->rowgrouped, x, y);
     return ell_own_apply(ctx, A, x, y);
 }
 

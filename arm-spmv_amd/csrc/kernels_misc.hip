@@ -439,7 +439,6 @@ int csc_apply_plan(spmv_mat* m)
 int csc_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
 {
     if (A->ncol == 0 || A->nnz == 0) return SPMV_OK;
-    if (runs_from_rowgrouped(A)) return csr_apply(ctx, A->rowgrouped, x, y);
     return csc_scatter_apply(ctx, A, x, y);
 }
 

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "panel_settings.hpp"
 
 namespace spmv
 {
@@ -41,17 +42,15 @@ int collect(const spmv_mat* m, std::vector<plan_node>& out)
     const bool csr = m->format == SPMV_FMT_CSR;
     if (csr && m->kernel == SPMV_CSR_PANEL)
     {
-        // the panel layout: what it was built with, and what a launch reads (requests first, else what the trial found, else
-        // defaults: the same precedence as panel_launch)
+        // the panel layout: what it was built with, and what a launch runs (panel_effective: the function panel_launch calls)
         n.pb_group_rows = m->pb_group_rows;
         n.pb_width      = m->pb_val ? m->pb_built_width : m->pb_panel_width;
         n.pb_sort       = m->pb_val ? m->pb_built_sort : m->pb_sort;
         n.pb_aos        = m->pb_val ? m->pb_built_layout : m->pb_aos;
-        const int unroll = m->pb_unroll > 0 ? m->pb_unroll : (m->pb_unroll_tuned > 0 ? m->pb_unroll_tuned : 8);
-        n.pb_unroll      = unroll >= 8 ? 8 : (unroll >= 4 ? 4 : 2);
-        n.pb_pipe        = std::max(0, std::min(m->pb_pipe >= 0 ? m->pb_pipe : (m->pb_pipe_tuned > 0 ? m->pb_pipe_tuned : 1), 2));
-        const int sync   = (m->pb_sync >= 0 ? m->pb_sync : m->pb_sync_tuned) & 3;
-        n.pb_sync        = sync == 2 ? 3 : sync;
+        const panel_settings run = panel_effective(m->pb_unroll, m->pb_unroll_tuned, m->pb_pipe, m->pb_pipe_tuned, m->pb_sync, m->pb_sync_tuned);
+        n.pb_unroll      = run.unroll;
+        n.pb_pipe        = run.pipe;
+        n.pb_sync        = run.sync;
         n.pb_two_per_cu  = m->pb_two_per_cu;
         n.pb_rounds      = m->pb_val ? std::max(1, m->pb_built_rounds) : std::max(1, m->pb_rounds_req);
     }

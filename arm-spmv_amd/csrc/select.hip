@@ -117,25 +117,23 @@ void select_scratch::release()
     x = y = nullptr;
 }
 
+// The one timed loop: spmv_apply_timed and its siblings, and every timing launch of a handle's set-up.
+int time_launches(spmv_ctx* ctx, int n, const std::function<int()>& launch, float* ms_per_launch)
+{
+    SPMV_HIP(hipEventRecord(ctx->ev_begin, ctx->stream));
+    for (int i = 0; i < n; ++i) SPMV_TRY(launch());
+    SPMV_HIP(hipEventRecord(ctx->ev_end, ctx->stream));
+    SPMV_HIP(hipEventSynchronize(ctx->ev_end));
+    float ms = 0.f;
+    SPMV_HIP(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+    *ms_per_launch = ms / (float)n;
+    return SPMV_OK;
+}
+
 int select_time(spmv_ctx* ctx, const std::function<int()>& launch, float best_so_far, float* out_ms)
 {
-    auto run = [&](int n, float* ms) -> int {
-        if (hipEventRecord(ctx->ev_begin, ctx->stream) != hipSuccess) return SPMV_ERR_HIP;
-        for (int i = 0; i < n; ++i)
-        {
-            const int rc = launch();
-            if (rc != SPMV_OK) return rc;
-        }
-        if (hipEventRecord(ctx->ev_end, ctx->stream) != hipSuccess || hipEventSynchronize(ctx->ev_end) != hipSuccess ||
-            hipEventElapsedTime(ms, ctx->ev_begin, ctx->ev_end) != hipSuccess)
-        {
-            set_error("kernel selection: a timing launch failed: %s", hipGetErrorString(hipGetLastError()));
-            return SPMV_ERR_HIP;
-        }
-        *ms /= (float)n;
-        return SPMV_OK;
-    };
-    int rc = launch();  // warm-up (first-use set-up of the kernel, LDS grants)
+    auto run = [&](int n, float* ms) { return time_launches(ctx, n, launch, ms); };
+    int  rc  = launch();  // warm-up (first-use set-up of the kernel, LDS grants)
     if (rc != SPMV_OK) return rc;
     float first = 0.f;
     if ((rc = run(1, &first)) != SPMV_OK) return rc;
@@ -215,11 +213,9 @@ int csr_apply_plan(spmv_mat* m)
     SPMV_REQUIRE((m->b && m->v) || m->nnz == 0, "plan: this handle gave up its CSR arrays (panel_keep_csr = 0)");
     select_reset(m);
     (void)hipStreamSynchronize(m->ctx->stream);
-    if (p.kernel != SPMV_CSR_PANEL) csr_panel_free(m);
-    if (p.kernel != SPMV_CSR_TWOPHASE) csr_twophase_free(m);
-    if (p.kernel != SPMV_CSR_SEGSCAN) csr_segscan_free(m);
-    csr_split_free(m);     // (rebuilt from the plan: its parts carry decisions of their own)
-    csr_ell_copy_free(m);  // (idem)
+    // every layout but the plan's own kernel's; the split and the ELL copy go even then (rebuilt from the plan: their parts carry
+    // decisions of their own)
+    csr_layouts_free(m, ~(1u << p.kernel) | (1u << SPMV_CSR_SPLIT) | (1u << SPMV_CSR_ELL));
     const int32_t trial_before = m->pb_trial;
     m->pb_trial       = 0;
     m->kernel         = p.kernel;
@@ -240,20 +236,15 @@ int csr_apply_plan(spmv_mat* m)
                 m->pb_sync        = p.pb_sync;
                 m->pb_two_per_cu  = p.pb_two_per_cu;
                 m->pb_rounds_req  = std::max(1, p.pb_rounds);
-                rc                = csr_panel_build(m);
                 break;
             case SPMV_CSR_TWOPHASE:
                 m->tp_pcols_req = p.tp_pcols;
                 m->tp_rotate    = p.tp_rotate;
-                rc              = csr_twophase_build(m);
                 break;
-            case SPMV_CSR_SEGSCAN: rc = csr_segscan_build(m); break;
-            case SPMV_CSR_SPLIT:
+            case SPMV_CSR_SPLIT:  // (its build hands the parts' nodes down)
                 m->split_threshold = p.split_threshold;
                 m->split_mode      = p.split_mode;
-                rc                 = csr_split_build(m);  // (hands the parts' nodes down)
                 break;
-            case SPMV_CSR_ELL: rc = csr_ell_copy_build(m); break;
             case SPMV_CSR_LDSWIN:
                 if (m->win_max_span <= 0 || m->win_max_span > csr_ldswin_capacity())
                 {
@@ -262,8 +253,9 @@ int csr_apply_plan(spmv_mat* m)
                     rc = SPMV_ERR_UNSUPPORTED;
                 }
                 break;
-            default: break;  // VECTOR, SCALAR: the CSR arrays as they are
+            default: break;  // SEGSCAN, ELL, VECTOR, SCALAR: nothing to copy from the node
         }
+    if (rc == SPMV_OK && m->nrow > 0 && m->nnz > 0) rc = csr_layout_build(m, p.kernel);
     m->pb_trial = trial_before;
     return rc;
 }
@@ -291,18 +283,10 @@ int csr_select_kernel(spmv_mat* m)
     constexpr int kSplitLow = 100;  // a candidate of this function only (not a kernel id): kernel SPLIT with every row of 256 entries and more split off
     m->split_auto_low = false;
     auto build = [&](int kernel) -> int {
-        if (kernel == kSplitLow || kernel == SPMV_CSR_SPLIT)
-        {
-            m->split_auto_low = kernel == kSplitLow;
-            m->kernel         = SPMV_CSR_SPLIT;
-            return csr_split_build(m);
-        }
-        m->kernel = kernel;
-        if (kernel == SPMV_CSR_PANEL) return csr_panel_build(m);
-        if (kernel == SPMV_CSR_TWOPHASE) return csr_twophase_build(m);
-        if (kernel == SPMV_CSR_SEGSCAN) return csr_segscan_build(m);
-        if (kernel == SPMV_CSR_ELL) return csr_ell_copy_build(m);
-        return SPMV_OK;
+        const bool low = kernel == kSplitLow;
+        if (low || kernel == SPMV_CSR_SPLIT) m->split_auto_low = low;
+        m->kernel = low ? (int)SPMV_CSR_SPLIT : kernel;
+        return csr_layout_build(m, m->kernel);
     };
     if (m->nrow == 0 || m->nnz == 0 || !m->b || !m->v) return build(model);
     const double mean = (double)m->nnz / (double)m->nrow;
@@ -425,11 +409,7 @@ int csr_select_kernel(spmv_mat* m)
             }
         }
     if (best < 0) best = model;
-    if (best != SPMV_CSR_PANEL) csr_panel_free(m);
-    if (best != SPMV_CSR_TWOPHASE) csr_twophase_free(m);
-    if (best != SPMV_CSR_SEGSCAN) csr_segscan_free(m);
-    if (best != SPMV_CSR_SPLIT && best != kSplitLow) csr_split_free(m);
-    if (best != SPMV_CSR_ELL) csr_ell_copy_free(m);
+    csr_layouts_free(m, ~(1u << (best == kSplitLow ? (int)SPMV_CSR_SPLIT : best)));  // all but the winner's
     return build(best);  // (a layout that is already in memory with the current parameters is kept as it is)
 }
 

@@ -2,8 +2,9 @@
 // (src/vec_vec.cpp:15-29, :31-94) and the `diagonal // for SymGS` fields (include/matrix.h:36,81) were written for is
 // a Krylov iteration.  The reference never got as far as calling them; here is that loop, device-resident:
 //
-//   mat_apply_ex   y = A*x or y += A*x with the dot product w.y of the updated y riding along (fused into the
-//                  write-back of the panel kernel: saves a pass over w and y; other kernels run a dot pass behind)
+//   mat_apply_ex   (kernels_csr.hip: the product dispatch) y = A*x or y += A*x with the dot product w.y of the updated y
+//                  riding along (fused into the write-back of the panel kernel: saves a pass over w and y; other kernels
+//                  run a dot pass behind)
 //   cg_solve       conjugate gradients for symmetric positive definite A, plain, Jacobi- or symmetric-Gauss-Seidel-
 //                  preconditioned (symgs.hip).  Three launches per iteration
 //                  (product+dot, x/r update+dot, direction update); alpha and beta are computed on the device from
@@ -471,44 +472,6 @@ int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t 
     if (n == 0) return SPMV_OK;
     hipLaunchKernelGGL(dot_accumulate_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, ctx->stream, x, y, n, device_out);
     SPMV_HIP(hipGetLastError());
-    return SPMV_OK;
-}
-
-int mat_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
-{
-    switch (A->format)
-    {
-        case SPMV_FMT_CSR: return csr_apply(ctx, A, x, y);
-        case SPMV_FMT_ELL: return ell_apply(ctx, A, x, y);
-        case SPMV_FMT_COO: return coo_apply(ctx, A, x, y);
-        case SPMV_FMT_CSC: return csc_apply(ctx, A, x, y);
-        case SPMV_FMT_DIA: return dia_apply(ctx, A, x, y);
-        default: SPMV_FAIL(SPMV_ERR_INVALID, "unknown format %d", A->format);
-    }
-}
-
-int mat_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex)
-{
-    // COO / ELL / CSC handles that run from their row-grouped copy: that copy is a CSR handle with a kernel of its own
-    if (runs_from_rowgrouped(A) && A->nnz > 0 && A->nrow > 0 && A->ncol > 0) return mat_apply_ex(ctx, A->rowgrouped, x, y, ex);
-    // the panel kernel does all of it in its write-back
-    if (A->format == SPMV_FMT_CSR && A->kernel == SPMV_CSR_PANEL && A->nrow > 0 && A->nnz > 0) return csr_panel_apply_ex(ctx, A, x, y, ex);
-    if (A->format == SPMV_FMT_CSR && A->kernel == SPMV_CSR_TWOPHASE) return csr_twophase_apply_ex(ctx, A, x, y, ex);
-    if (A->format == SPMV_FMT_CSR && A->kernel == SPMV_CSR_SPLIT && A->split_short)
-    {
-        // the short rows with the overwrite fused into their kernel, the long rows added on top, the dot product over the finished y
-        apply_extra first;
-        first.overwrite = ex.overwrite;
-        SPMV_TRY(mat_apply_ex(ctx, A->split_short, x, y, first));
-        SPMV_TRY(csr_split_long_rows_apply(ctx, A, x, y));
-        if (ex.dot_w) SPMV_TRY(vec_dot_accumulate(ctx, ex.dot_w, y, A->nrow, ex.dot_out));
-        return SPMV_OK;
-    }
-    int rc = SPMV_OK;
-    if (A->format == SPMV_FMT_CSR && csr_vector_apply_ex(ctx, A, x, y, ex, &rc)) return rc;  // row-parallel kernel: fused too
-    if (ex.overwrite) SPMV_TRY(vec_fill(ctx, y, A->nrow, 0.0));
-    SPMV_TRY(mat_apply(ctx, A, x, y));
-    if (ex.dot_w) SPMV_TRY(vec_dot_accumulate(ctx, ex.dot_w, y, A->nrow, ex.dot_out));
     return SPMV_OK;
 }
 

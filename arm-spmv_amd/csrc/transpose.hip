@@ -306,7 +306,7 @@ int transpose_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y
 {
     const transpose_state* st = A->tr;
     if (A->format == SPMV_FMT_DIA) return dia_transpose_apply(ctx, A, st, x, y);
-    return st->comp ? mat_apply(ctx, st->comp, x, y) : SPMV_OK;
+    return st->comp ? mat_apply_ex(ctx, st->comp, x, y) : SPMV_OK;
 }
 }  // namespace
 
@@ -384,13 +384,9 @@ int spmv_apply_transpose_timed(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec*
     SPMV_REQUIRE(reps > 0 && ms_per_apply, "spmv_apply_transpose_timed: reps=%d", reps);
     SPMV_TRY(transpose_setup(const_cast<spmv_mat*>(A)));  // outside the timed region
     SPMV_HIP(hipSetDevice(ctx->device));
-    SPMV_HIP(hipEventRecord(ctx->ev_begin, ctx->stream));
-    for (int32_t i = 0; i < reps; ++i) SPMV_TRY(transpose_apply(ctx, A, x->d, y->d));
-    SPMV_HIP(hipEventRecord(ctx->ev_end, ctx->stream));
-    SPMV_HIP(hipEventSynchronize(ctx->ev_end));
     float ms = 0.f;
-    SPMV_HIP(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
-    *ms_per_apply = (double)ms / reps;
+    SPMV_TRY(time_launches(ctx, reps, [&] { return transpose_apply(ctx, A, x->d, y->d); }, &ms));
+    *ms_per_apply = ms;
     return SPMV_OK;
 }
 }  // extern "C"

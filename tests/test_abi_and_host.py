@@ -200,6 +200,28 @@ def test_split_virtual_rows_hold_every_entry_once_in_order(tmp_path):
     assert r.returncode == 0 and " 0 violations" in r.stdout, r.stdout + r.stderr
 
 
+def test_panel_launch_settings_are_what_launch_and_plan_computed_and_always_instantiated(tmp_path):
+    """The panel kernel's chunk size, load order and barrier (csrc/panel_settings.hpp: panel_effective, called by panel_launch
+    and by the plan's collect) for every request and every build-time trial result that can reach a launch: equal to the
+    expressions the two sites held separately (restated in tests/panel_settings_check.cpp), always one of the instantiated
+    combinations, and - on the values include/spmv_abi.h documents - equal to what spmv_mat_get_param reports."""
+    import shutil
+    import subprocess
+
+    if not shutil.which("g++"):
+        pytest.skip("no g++ here")
+    exe = tmp_path / "panel_settings_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT / 'arm-spmv_amd' / 'csrc'}", str(ROOT / "tests" / "panel_settings_check.cpp"), "-o", str(exe)],
+                   check=True, timeout=120)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    words = r.stdout.replace(",", "").split()
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert int(words[1]) == 34 * 4 * 6 * 3 * 10 * 4  # every combination of the ranges above
+    assert words[3] == "0" and words[5] == "0"  # differences from the two sites; results outside the instantiated set
+    assert int(words[8]) == 5 * 4 * 4 * 3 * 5 * 4 and words[10] == "0"  # documented requests: get_param reports what runs
+
+
 def test_plan_blobs_are_checked_without_a_device(pkg):
     """spmv_plan_check: the validation spmv_mat_set_plan / spmv_ctx_set_plan run on a blob, callable anywhere (a plan received
     from another rank, read from a file).  A node is 32 four-byte fields: format, kernel, lanes, flags, 9 panel fields, 2 split,

@@ -1,6 +1,6 @@
 """What do fp64 device atomics on pinned, device-mapped HOST memory do on this box?
 
-spmv_apply_host keeps y in device memory for kernels that add into y with atomics (abi.hip: adds_into_y_with_atomics) because
+spmv_apply_host keeps y in device memory for kernels that add into y with atomics (kernels_csr.hip: adds_into_y_with_atomics) because
 that is platform behaviour, not a HIP guarantee.  This probe forces the other route (SPMV_EXPERIMENTS=1 SPMV_HOST_Y_IN_PLACE=1:
 y stays in the staging buffer whatever the kernel) and compares with the oracle-checked default, so that the header can SAY what
 was seen.  Run: SPMV_EXPERIMENTS=1 SPMV_HOST_Y_IN_PLACE=1 python tools/probe_apply_host_atomics.py  (and once without, as control)
