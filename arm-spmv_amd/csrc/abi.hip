@@ -363,6 +363,8 @@ int spmv_ctx_get_param(const spmv_ctx* ctx, const char* name, int64_t* value)
         *value = ctx->xcds_seen;
     else if (!strcmp(name, "trial_arena_bytes"))
         *value = (int64_t)ctx->arena_bytes;
+    else if (!strcmp(name, "cg_graph_replays"))
+        *value = ctx->cg_graph_replays;
     else
         SPMV_FAIL(SPMV_ERR_INVALID, "unknown context parameter '%s'", name);
     return SPMV_OK;

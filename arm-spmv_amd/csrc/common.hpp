@@ -110,6 +110,7 @@ struct spmv_ctx
     // column bin per XCD) are not built when it is not 1; nothing leans on it for correctness.
     int32_t xcd_round_robin = -1;
     int32_t xcds_seen       = 0;
+    int64_t cg_graph_replays = 0;  // spmv_cg under SPMV_CG_GRAPH=1: launches of the captured four iterations so far (tests read it)
     // spmv_apply_host (abi.hip): the caller's HOST vectors staged through pinned, device-mapped host memory (small vectors: the
     // GPU copies them in and out itself, one stream, no hipMemcpy) and device buffers for x and y; grown on demand
     double* stage_pinned     = nullptr;  // host address

@@ -504,7 +504,10 @@ static bool fuses_extras(const spmv_mat* A)
 {
     if (A->format != SPMV_FMT_CSR || A->nrow == 0) return false;
     if (A->kernel == SPMV_CSR_SPLIT) return A->split_short;
-    return csr_kernel_fuses_in_one_launch(A->kernel) && (A->kernel != SPMV_CSR_PANEL || A->nnz > 0);
+    // panel and two-phase build no layout for a handle without entries and launch nothing: their extras take the general path
+    // (y zeroed, nothing added, the dot product over y - which is w . y0 where y is not overwritten)
+    const bool needs_entries = A->kernel == SPMV_CSR_PANEL || A->kernel == SPMV_CSR_TWOPHASE;
+    return csr_kernel_fuses_in_one_launch(A->kernel) && (!needs_entries || A->nnz > 0);
 }
 
 // Does a product of this handle add into y with device atomics (global_atomic_add_f64)?  Decided by the kernel that RUNS,

@@ -883,6 +883,12 @@ int csr_panel_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double
 
 static int panel_launch(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, bool trial, const apply_extra& ex)
 {
+    // rows without a single entry: csr_panel_build builds nothing for them and there is nothing to add (as every other kernel)
+    if (A->nrow == 0 || A->nnz == 0)
+    {
+        if (ex.overwrite && A->nrow > 0) SPMV_TRY(vec_fill(ctx, y, A->nrow, 0.0));
+        return SPMV_OK;
+    }
     if (!A->pb_val) SPMV_FAIL(SPMV_ERR_INVALID, "panel kernel selected but its layout was not built");
     // the fullest group's accumulators (+ the spare one the pads of the packed layout add into)
     const size_t lds = ((size_t)A->pb_max_rows + (A->pb_pack ? 1 : 0)) * sizeof(double);

@@ -12,8 +12,10 @@
 //                  the residual every `check_every` iterations only.  (A hipGraph replay of the iterations in
 //                  between was built and measured slower than plain launches: kept behind SPMV_CG_GRAPH=1.)
 //
-// Not part of the reference's API: the results are checked against the oracle's product (residual of the solution)
-// in tests/test_gpu_solver.py.
+// Not part of the reference's API, so there is no reference output.  What pins it: every iterate x_k and residual of cg_solve,
+// in each arrangement below and at both vector widths, against conjugate gradients in extended precision
+// (tests/solver_ref.py, tests/test_gpu_solver_steps.py); overwrite and the fused dot of mat_apply_ex bit for bit on exact inputs
+// (tests/test_gpu_exact.py); the solution through the oracle's product (tests/test_gpu_solver.py).
 #include <cmath>
 #include <cstdlib>
 #include <vector>
@@ -711,6 +713,7 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
                     break;
                 }
                 k += 4;
+                ++ctx->cg_graph_replays;
             }
             else
             {

@@ -29,6 +29,32 @@ def choose_bits(terms: int, reps: int = 1) -> tuple[int, int]:
     raise ValueError(f"no exact inputs for {terms} terms x {reps} calls per output")
 
 
+def choose_bits_dot(total_terms: int, nout: int, reps: int = 1) -> tuple[int, int]:
+    """(B, E) for a product whose dot w . y is exact as well: w, the values, x and y0 all dyadic with B bits and exponents in
+    [-E, E], so every term w_i * a * x of the dot is a multiple of 2^-3E (three dyadic factors) of at most 2^(3B + 3E).  The whole
+    of sum_i |w_i| (|y0_i| + reps * sum_j |a_ij x_j|) - `total_terms` products over `nout` outputs - stays below 2^53 on that grid,
+    so every partial sum of the dot is exact in any order (lanes, wavefronts, the 32 slots, the host's sum over them), and every
+    y_i is (|w_i| 2^E >= 1)."""
+    t, n = max(1, int(total_terms)) * max(1, int(reps)), max(1, int(nout))
+    for e in range(E_MAX, -1, -1):
+        for b in range(B_MAX, 0, -1):
+            if 2.0 ** (b + 2 * e) * (t * 2.0 ** (2 * b + 4 * e) + n * 2.0 ** (b + 3 * e)) < BUDGET:
+                return b, e
+    raise ValueError(f"no exact inputs for a dot over {total_terms} terms x {reps} calls in {nout} outputs")
+
+
+def exact_dot(w, y, e_w: int, e_y: int) -> float:
+    """w . y in int64 (w on the grid 2^-e_w, y on 2^-e_y), returned as float64.  Raises where sum |w_i y_i| reaches 2^53 on the
+    grid 2^-(e_w + e_y): a float64 sum would stop being exact in some order (and below that bound int64 cannot overflow)."""
+    iw, iy = scaled(w, e_w), scaled(y, e_y)
+    if iw.shape != iy.shape:
+        raise ValueError("exact_dot: shapes differ")
+    mag = float(np.dot(np.abs(iw).astype(np.float64), np.abs(iy).astype(np.float64))) if iw.size else 0.0
+    if mag * (1 + 1e-9) >= BUDGET:
+        raise ValueError(f"exact_dot: the sum needs {np.log2(mag):.1f} bits (budget 53): choose smaller bits / exponents")
+    return float(np.ldexp(float(np.sum(iw * iy)), -(e_w + e_y)))
+
+
 def dyadic(rng, shape, bits: int, e: int, e_lo: int | None = None) -> np.ndarray:
     """float64 +-m * 2^x, m in [1, 2^bits), x in [e_lo, e] (e_lo = -e by default)"""
     lo = -e if e_lo is None else e_lo

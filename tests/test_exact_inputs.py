@@ -107,6 +107,51 @@ def test_choose_bits_prefers_the_widest_range_and_keeps_the_budget():
         assert (2**b - 1) ** 2 * 2.0 ** (4 * e) > 1e10, (terms, b, e)
 
 
+def test_choose_bits_dot_keeps_the_whole_dot_within_the_budget():
+    for total, nout, reps in ((1, 1, 1), (50, 7, 3), (6000, 300, 3), (400_000, 90_000, 3), (2_300_000, 600_000, 3), (3_000_001, 3_000_001, 1)):
+        b, e = ex.choose_bits_dot(total, nout, reps)
+        assert 2.0 ** (b + 2 * e) * (total * reps * 2.0 ** (2 * b + 4 * e) + nout * 2.0 ** (b + 3 * e)) < 2.0**53
+        assert e <= ex.choose_bits(total, reps)[1]  # never a wider range than one output of that many terms may have
+        assert e == ex.E_MAX or 2.0 ** (1 + 2 * (e + 1)) * (total * reps * 2.0 ** (2 + 4 * (e + 1)) + nout * 2.0 ** (1 + 3 * (e + 1))) >= 2.0**53
+    with pytest.raises(ValueError):
+        ex.choose_bits_dot(2**52, 1)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_exact_dot_is_the_float64_sum_in_any_order(orc, seed):
+    """w . (y0 + reps * A x) on inputs from choose_bits_dot: the integer sum, the oracle's dot (both flavours) and a float64 sum in
+    shuffled orders, forward, reversed and pairwise, all return the same bits"""
+    rng = np.random.default_rng(400 + seed)
+    nrow, ncol = int(rng.choice([1, 7, 300, 20_000])), int(rng.choice([1, 5, 400, 3000]))
+    nnz = int(rng.choice([0, 1, 50, 6000, 200_000]))
+    reps = 3
+    row, col = _random_coo(rng, nrow, ncol, nnz)
+    bits, e = ex.choose_bits_dot(nnz, nrow, reps)
+    val, x = ex.dyadic(rng, nnz, bits, e), ex.dyadic(rng, ncol, bits, e)
+    y0, w = ex.dyadic(rng, nrow, bits, e), ex.dyadic(rng, nrow, bits, e)
+    for y in (ex.exact_product(nrow, row, col, val, x, e), ex.exact_product(nrow, row, col, val, x, e, y0=y0, reps=reps)):
+        want = ex.exact_dot(w, y, e, 2 * e)
+        assert want == ol.dot(orc, w, y) == ol.dot(orc, w, y, fma=True)
+        t = w * y
+        assert want == float(np.sum(t)) == float(np.cumsum(t)[-1]) == float(np.cumsum(t[::-1])[-1])
+        for _ in range(4):
+            p = rng.permutation(nrow)
+            assert want == float(np.cumsum(t[p])[-1]) == ol.dot(orc, ol.f64(w[p]), ol.f64(y[p]), fma=True)
+        # 32 partial sums over interleaved rows, then their sum: the shape of the slotted accumulator
+        assert want == float(sum(float(np.sum(t[s::32])) for s in range(32)))
+    # one term left out changes the bits; a sum beyond the budget raises
+    if nnz:
+        y = ex.exact_product(nrow, row, col, val, x, e, y0=y0, reps=reps)
+        less = y.copy()
+        less[row[0]] -= val[0] * x[col[0]]
+        assert ex.exact_dot(w, less, e, 2 * e) != ex.exact_dot(w, y, e, 2 * e)
+    with pytest.raises(ValueError, match="budget"):
+        ex.exact_dot(np.full(1 << 12, 2.0**20), np.full(1 << 12, 2.0**22), 0, 0)
+    with pytest.raises(ValueError):
+        ex.exact_dot(np.ones(3), np.array([1.0, np.nan, 1.0]), 0, 0)
+    assert ex.exact_dot(np.zeros(0), np.zeros(0), 3, 6) == 0.0
+
+
 def test_the_budget_guard_raises():
     # one output of 2^20 terms of 2^34 each (scaled by 2^2E): 2^54 > 2^53
     e = 10

@@ -811,10 +811,225 @@ def test_full_size_c3_multi_k8_equals_the_ell_kernel_per_column(ctx):
     SEEN["full:c3 multi"].add(k)
 
 
+# ---- overwrite and the fused dot product (spmv_apply_dot) -----------------------------------------------------------------------
+# kernels_csr.hip: the kernels that take y = A x and w . y into their own write-back (SPLIT: into the kernel of its short rows,
+# the dot behind); every other kernel runs behind a fill of y and in front of a dot pass
+FUSES = {AUTO, VECTOR, PANEL, TWOPHASE, SPLIT}
+EXTRAS_SEEDS = tuple(range(6)) + tuple(range(6, N_CSR, 2))  # the six edge shapes and every other random shape
+
+
+def _vec(ctx, a):
+    a = np.asarray(a, dtype=np.float64)
+    return ctx.vector_from(a) if a.size else ctx.vector(0)
+
+
+class ExactDot:
+    """Exact with a dyadic w: y = A x over a y that is NaN / +-inf everywhere, y0 + A x once and REPS times, and w . y of each -
+    all from integer arithmetic (the bits of choose_bits_dot keep the whole dot within 2^53)"""
+
+    def __init__(self, rng, nout, nin, entries, bits, e, used=None):
+        self.nout, self.e = nout, e
+        self.x, self.y0, self.w = ex.dyadic(rng, nin, bits, e), ex.dyadic(rng, nout, bits, e), ex.dyadic(rng, nout, bits, e)
+        self.want0 = ex.exact_product(nout, *entries, self.x, e)
+        self.want1 = ex.exact_product(nout, *entries, self.x, e, y0=self.y0)
+        self.wantr = ex.exact_product(nout, *entries, self.x, e, y0=self.y0, reps=REPS)
+        self.dot0, self.dot1, self.dotr = (ex.exact_dot(self.w, y, e, 2 * e) for y in (self.want0, self.want1, self.wantr))
+        self.xp = ex.poison(self.x, entries[1] if used is None else used)
+        self.poisoned_y = ex.poison(np.zeros(nout), [])  # overwrite must not read it
+
+    def check(self, ctx, A, what, dx=None, dw=None):
+        dx = dx if dx is not None else _vec(ctx, self.xp)
+        dw = dw if dw is not None else _vec(ctx, self.w)
+        dy = _vec(ctx, self.poisoned_y)
+        for call in range(2):  # y = A x twice: the second call must not add to the first
+            d = ctx.apply_dot(A, dx, dy, dw, overwrite=True)
+            got = dy.download()
+            assert np.array_equal(got, self.want0), f"{what}, overwrite (call {call + 1}) onto NaN / inf: {_fail(got, self.want0)}"
+            assert d == self.dot0, f"{what}, overwrite (call {call + 1}): w . y = {d!r}, exact {self.dot0!r}"
+        dy = _vec(ctx, self.y0)
+        for call in range(REPS):
+            d = ctx.apply_dot(A, dx, dy, dw, overwrite=False)
+            if call in (0, REPS - 1):
+                want, wdot = (self.want1, self.dot1) if call == 0 else (self.wantr, self.dotr)
+                got = dy.download()
+                assert np.array_equal(got, want), f"{what}, y += A x, {call + 1} calls: {_fail(got, want)}"
+                assert d == wdot, f"{what}, y += A x, {call + 1} calls: w . y = {d!r}, exact {wdot!r}"
+
+
+@pytest.mark.parametrize("seed", EXTRAS_SEEDS)
+def test_exact_apply_dot_every_kernel(ctx, pkg, seed):
+    """spmv_apply_dot under every CSR kernel and parameter set of the forward test: y = A x over a y of NaN / +-inf (empty rows come
+    back as 0), y0 + A x once and REPS times, and the dot w . y of each, all bit for bit"""
+    capi = pkg.capi
+    nrow, ncol, rp, cc = _csr_shape(seed)
+    rng = np.random.default_rng(BASE + 19_000 + seed)
+    if seed % 3 == 0:
+        cc = ex.avoid_columns(cc, ncol, PANEL_COLS)
+    bits, e = ex.choose_bits_dot(len(cc), nrow, REPS)
+    cv = _dyadic_values(rng, len(cc), bits, e, zeros=seed % 4 == 1)
+    D = ExactDot(rng, nrow, ncol, ex.csr_entries(rp, cc, cv), bits, e)
+    empty = np.diff(rp) == 0
+    assert np.all(D.want0[empty] == 0.0)
+    what = f"seed {seed}: CSR {nrow} x {ncol}, {len(cc)} entries, {int(empty.sum())} empty rows"
+    A = ctx.csr(nrow, ncol, rp, cc, cv)
+    dx, dw = _vec(ctx, D.xp), _vec(ctx, D.w)
+    for label, setup in _csr_kernel_runs(capi, A, rng, len(cc), ncol):
+        if setup() is False:
+            continue
+        k = A.info.kernel
+        D.check(ctx, A, f"{what}, {label} (kernel {k})", dx=dx, dw=dw)
+        _record_csr(A, label, family="extras")
+        SEEN["extras"].add(AUTO if label == "auto" else k)
+        SEEN["extras:path"].add("fused" if (AUTO if label == "auto" else k) in FUSES else "behind")
+        if empty.any():
+            SEEN["extras:empty_rows"].add(AUTO if label == "auto" else k)
+    RUNS["extras"] += 1
+
+
+@pytest.mark.parametrize("seed", range(5))
+def test_exact_apply_dot_coo_csc_ell_dia_handles(ctx, pkg, seed):
+    """the same for the other formats: their own kernels (no extras of their own: fill, product, dot pass) and their row-grouped
+    copies (a CSR handle, whose kernel takes the extras)"""
+    capi = pkg.capi
+    rng = np.random.default_rng(BASE + 19_500 + seed)
+    # COO
+    nrow, ncol, row, col = _coo_shape(rng, seed)
+    bits, e = ex.choose_bits_dot(len(row), nrow, REPS)
+    val = _dyadic_values(rng, len(row), bits, e, zeros=seed % 4 == 1)
+    D = ExactDot(rng, nrow, ncol, ex.coo_entries(row, col, val), bits, e)
+    A = ctx.coo(nrow, ncol, row, col, val)
+    for kernel in (AUTO, VECTOR, PANEL):
+        A.set_kernel(kernel)
+        D.check(ctx, A, f"seed {seed}: COO {nrow} x {ncol}, {len(row)} entries, kernel {kernel} (runs {A.info.kernel})")
+        SEEN["extras:coo"].add(A.info.kernel)
+    # CSC
+    nrow, ncol, cp, cols, cr = _csc_shape(rng, seed)
+    bits, e = ex.choose_bits_dot(len(cr), nrow, REPS)
+    cv = _dyadic_values(rng, len(cr), bits, e, zeros=seed % 4 == 1)
+    D = ExactDot(rng, nrow, ncol, ex.csc_entries(cp, cr, cv), bits, e)
+    A = ctx.csc(nrow, ncol, cp, cr, cv)
+    for kernel in (AUTO, VECTOR, PANEL):
+        A.set_kernel(kernel)
+        D.check(ctx, A, f"seed {seed}: CSC {nrow} x {ncol}, {len(cr)} entries, kernel {kernel} (runs {A.info.kernel})")
+        SEEN["extras:csc"].add(A.info.kernel)
+    # ELL: pad products count as reads (0.0 * x[0])
+    nrow, ncol, k, col, pad = _ell_shape(rng)
+    bits, e = ex.choose_bits_dot(len(col), nrow, REPS)
+    val = ex.dyadic(rng, len(col), bits, e)
+    val[pad] = 0.0
+    D = ExactDot(rng, nrow, ncol, ex.ell_entries(nrow, k, col, val), bits, e)
+    A = ctx.ell(nrow, ncol, k, int((~pad).sum()), col, val)
+    for kernel, lanes in ((AUTO, 0), (VECTOR, 1), (VECTOR, 2), (PANEL, 0)):
+        if kernel != AUTO:  # (AUTO: the handle as created)
+            A.set_kernel(kernel, lanes)
+        D.check(ctx, A, f"seed {seed}: ELL {nrow} x {ncol}, k = {k}, {int(pad.sum())} pad slots, kernel {kernel} lanes {lanes} (runs {A.info.kernel})")
+        SEEN["extras:ell"].add(A.info.kernel)
+    # DIA
+    nrow = int(rng.choice([1, 255, 257, 5000, 70_001]))
+    ncol = int(rng.choice([nrow, max(1, nrow // 2), nrow + 300]))
+    span = int(rng.choice([2, 40, max(2, nrow)]))
+    offs = ol.i32(np.sort(rng.choice(np.arange(-span, span + 1), size=min(int(rng.integers(1, 20)), 2 * span + 1), replace=False)))
+    bits, e = ex.choose_bits_dot(nrow * len(offs), nrow, REPS)
+    val = ex.dyadic(rng, nrow * len(offs), bits, e)
+    D = ExactDot(rng, nrow, ncol, ex.dia_entries(nrow, ncol, offs, val), bits, e)
+    A = ctx.dia(nrow, ncol, offs, val)
+    D.check(ctx, A, f"seed {seed}: DIA {nrow} x {ncol}, offsets {list(offs)[:8]}..")
+    SEEN["extras:dia"].add("plain")
+    RUNS["extras:formats"] += 1
+
+
+def test_exact_apply_dot_wrapped_and_degenerate_handles(ctx, pkg):
+    """borrowed arrays (COO, ELL); no entries in nrow > 0 rows (y = 0 over NaN, dot 0); no rows; an ELL handle that is all padding;
+    a ragged ELL handle whose extras go to its row-grouped copy"""
+    rng = np.random.default_rng(BASE + 19_900)
+    nrow, ncol, nnz = 20_000, 15_000, 120_000
+    row = rng.integers(0, nrow, nnz).astype(np.int32)
+    col = ex.avoid_columns(rng.integers(0, ncol, nnz), ncol, PANEL_COLS)
+    bits, e = ex.choose_bits_dot(nnz, nrow, REPS)
+    val = ex.dyadic(rng, nnz, bits, e)
+    dr, dc, dv = _device_ints(ctx, row), _device_ints(ctx, col), ctx.vector_from(val)
+    A = ctx.wrap_coo(nrow, ncol, nnz, dr.device_ptr, dc.device_ptr, dv.device_ptr)
+    ExactDot(rng, nrow, ncol, ex.coo_entries(row, col, val), bits, e).check(ctx, A, "wrap_coo")
+    # ragged ELL, borrowed: rows of 1..9 slots padded with column 0 / value 0; then the same handle from its row-grouped copy
+    k = 9
+    lens = rng.integers(1, k + 1, nrow)
+    ec = ex.avoid_columns(rng.integers(0, ncol, (k, nrow)), ncol, PANEL_COLS).reshape(k, nrow)
+    pad = np.arange(k)[:, None] >= lens[None, :]
+    ec[pad] = 0
+    bits, e = ex.choose_bits_dot(k * nrow, nrow, REPS)
+    ev = ex.dyadic(rng, (k, nrow), bits, e)
+    ev[pad] = 0.0
+    ec, ev = ec.ravel(), ev.ravel()
+    ent = ex.ell_entries(nrow, k, ec, ev)
+    dc2, dv2 = _device_ints(ctx, ec), ctx.vector_from(ev)
+    E = ctx.wrap_ell(nrow, ncol, k, int(lens.sum()), dc2.device_ptr, dv2.device_ptr)
+    D = ExactDot(rng, nrow, ncol, ent, bits, e)
+    D.check(ctx, E, "wrap_ell")
+    E2 = ctx.ell(nrow, ncol, k, int(lens.sum()), ec, ev)
+    E2.set_kernel(PANEL)
+    assert E2.info.kernel == PANEL and E2.get_param("rowgrouped_kernel") >= 0
+    D.check(ctx, E2, f"ragged ELL from its row-grouped copy (kernel {E2.get_param('rowgrouped_kernel')})")
+    SEEN["extras:wrapped"].update({"coo", "ell", "ell copy"})
+    # rows without a single entry: y = 0 over NaN, w . y = 0; y += A x leaves y0 and returns w . y0
+    i0, f0 = np.zeros(0, np.int32), np.zeros(0)
+    nrow, ncol = 777, 50
+    none = (np.zeros(0, np.int64), np.zeros(0, np.int64), f0)
+    D = ExactDot(rng, nrow, ncol, none, 6, 4)
+    assert D.dot0 == 0.0 and not D.want0.any() and not np.isfinite(D.xp).any()
+    C = ctx.csr(nrow, ncol, np.zeros(nrow + 1, np.int32), i0, f0)
+    for kernel in (AUTO, VECTOR, SCALAR, PANEL, TWOPHASE, SEGSCAN, SPLIT):
+        try:
+            C.set_kernel(kernel)
+        except pkg.capi.SpmvError:
+            continue  # a kernel that needs entries to build its layout says so; what can be selected must be right
+        D.check(ctx, C, f"CSR {nrow} x {ncol} without entries, kernel {kernel} (runs {C.info.kernel})")
+        SEEN["extras:no_entries"].add(C.info.kernel)
+    for name, H in (("COO", ctx.coo(nrow, ncol, i0, i0, f0)), ("CSC", ctx.csc(nrow, ncol, np.zeros(ncol + 1, np.int32), i0, f0))):
+        for kernel in (AUTO, VECTOR, PANEL):
+            try:
+                H.set_kernel(kernel)
+            except pkg.capi.SpmvError:
+                continue
+            D.check(ctx, H, f"{name} {nrow} x {ncol} without entries, kernel {kernel}")
+    # an ELL handle that is all padding: every slot reads x[0] (finite) times 0.0
+    k = 3
+    pads = ex.ell_entries(nrow, k, np.zeros(nrow * k, np.int32), np.zeros(nrow * k))
+    P = ExactDot(rng, nrow, ncol, pads, 6, 4)
+    assert np.isfinite(P.xp[0]) and not np.isfinite(P.xp[1:]).any() and not P.want0.any()
+    H = ctx.ell(nrow, ncol, k, 0, np.zeros(nrow * k, np.int32), np.zeros(nrow * k))
+    for kernel in (AUTO, VECTOR, PANEL):
+        try:
+            H.set_kernel(kernel)
+        except pkg.capi.SpmvError:
+            continue
+        P.check(ctx, H, f"ELL {nrow} x {ncol}, all padding, kernel {kernel} (runs {H.info.kernel})")
+    # no rows: nothing to write, w . y = 0
+    Z = ExactDot(rng, 0, 5, none, 6, 4)
+    for name, H in (("CSR", ctx.csr(0, 5, np.zeros(1, np.int32), i0, f0)), ("COO", ctx.coo(0, 5, i0, i0, f0)), ("ELL", ctx.ell(0, 5, 0, 0, i0, f0))):
+        Z.check(ctx, H, f"{name} 0 x 5")
+    SEEN["extras:degenerate"].update({"no entries", "all padding", "no rows"})
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 255, 257, 524_289, 3_000_001])
+def test_exact_dot(ctx, n):
+    """spmv_dot on dyadic vectors whose whole sum stays within 2^53: the bits of the integer sum, at the edges of a wavefront, a
+    workgroup and the grid (524,288 threads)"""
+    rng = np.random.default_rng(BASE + 19_990 + n % 1000)
+    bits, e = ex.choose_bits(max(n, 1), 1)  # n products of two dyadic factors: the budget of one output of n terms
+    x, y = ex.dyadic(rng, n, bits, e), ex.dyadic(rng, n, bits, e)
+    want = ex.exact_dot(x, y, e, e)
+    got = ctx.dot(_vec(ctx, x), _vec(ctx, y))
+    assert got == want, f"n = {n}: spmv_dot {got!r}, exact {want!r}"
+    if n:
+        y[n - 1] = -y[n - 1]  # the last element counts
+        assert ctx.dot(_vec(ctx, x), _vec(ctx, y)) == ex.exact_dot(x, y, e, e) != want
+    SEEN["dot"].add(n)
+
+
 # ---- what ran ------------------------------------------------------------------------------------------------------------------
 def test_every_kernel_ran():
     """across the seeds above: every kernel and layout this file names ran at least once"""
-    expect = {"csr": N_CSR, "coo": N_COO, "csc": N_CSC, "ell": N_ELL, "dia": N_DIA, "multi": N_MULTI}
+    expect = {"csr": N_CSR, "coo": N_COO, "csc": N_CSC, "ell": N_ELL, "dia": N_DIA, "multi": N_MULTI, "extras": len(EXTRAS_SEEDS), "extras:formats": 5}
     if any(RUNS[f] != n for f, n in expect.items()):
         pytest.skip(f"the coverage check needs every seed of this module (ran {dict(RUNS)})")
     need = {
@@ -837,6 +1052,19 @@ def test_every_kernel_ran():
         "multi:lanes": {32, 64},
         "multi:grid_stride": {16},
         "wrapped": {"coo", "ell"},
+        # spmv_apply_dot: every CSR kernel id, the kernels that fuse the extras and the ones that run behind a fill and before a dot pass
+        "extras": {AUTO, VECTOR, SCALAR, LDSWIN, PANEL, TWOPHASE, SEGSCAN, SPLIT, ELLK},
+        "extras:path": {"fused", "behind"},
+        "extras:empty_rows": {AUTO, VECTOR, SCALAR, PANEL, TWOPHASE, SEGSCAN, SPLIT},
+        "extras:panel_layout": {3, 4},
+        "extras:split_mode": {0, 1, 2},
+        "extras:coo": {VECTOR, PANEL},
+        "extras:csc": {VECTOR, PANEL},
+        "extras:ell": {VECTOR, PANEL},
+        "extras:wrapped": {"coo", "ell", "ell copy"},
+        "extras:no_entries": {VECTOR, SCALAR},
+        "extras:degenerate": {"no entries", "all padding", "no rows"},
+        "dot": {0, 1, 63, 64, 65, 255, 257, 524_289, 3_000_001},
     }
     missing = {f: sorted(map(str, want - SEEN[f])) for f, want in need.items() if not want <= SEEN[f]}
     assert not missing, f"never ran: {missing}; ran: { {f: sorted(map(str, v)) for f, v in SEEN.items()} }"

@@ -3,7 +3,8 @@
 The reference has no solver (its vec_dot / vec_axpby are never called), so there is no reference output to pin these
 against ("parity unpinned" for the iteration itself).  What IS pinned: the y of apply_dot against the reference's golden
 y (same gate as the product), its dot against the dot of that y, and the solution of CG through the oracle's product:
-||b - A x|| / ||b|| computed on the CPU with oracle/spmv_oracle.c.
+||b - A x|| / ||b|| computed on the CPU with oracle/spmv_oracle.c.  The iteration itself - every x_k against conjugate gradients
+in extended precision - is in tests/test_gpu_solver_steps.py; apply_dot bit for bit on exact inputs in tests/test_gpu_exact.py.
 """
 import numpy as np
 import pytest
