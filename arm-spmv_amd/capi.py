@@ -100,6 +100,7 @@ SIGNATURES = {
     "spmv_dot": (C.c_int, [_vp, _vp, _vp, _f64p]),
     "spmv_axpby": (C.c_int, [_vp, C.c_double, _vp, C.c_double, _vp, _vp]),
     "spmv_apply_dot": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, _f64p]),
+    "spmv_cg_multi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_cg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_symgs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32]),
     "spmv_symgs_setup": (C.c_int, [_vp, _vp]),
@@ -442,6 +443,17 @@ class Context:
         _check(self._lib.spmv_cg(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, PRECOND_SYMGS if symgs else (PRECOND_JACOBI if jacobi else PRECOND_NONE), C.byref(it),
                                  C.byref(res)))
         return it.value, res.value
+
+    def cg_multi(self, A: "Matrix", B: "Vector", X: "Vector", k: int, max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
+                 jacobi: bool = False, precond: int | None = None):
+        """k independent conjugate-gradient solves A x_c = b_c in one loop, from the X passed in.  B and X are row-major (nrow, k):
+        Vectors of nrow*k entries.  CSR and ELL handles; jacobi: the diagonal preconditioner (CSR).  Columns that have converged are
+        frozen.  Returns (iters: np.int32[k], rel_resid: np.float64[k]) per column.  precond, if given, is passed as it is (PRECOND_*)"""
+        it, res = np.zeros(max(int(k), 1), dtype=np.int32), np.zeros(max(int(k), 1), dtype=np.float64)
+        pc = precond if precond is not None else (PRECOND_JACOBI if jacobi else PRECOND_NONE)
+        _check(self._lib.spmv_cg_multi(self.h, A.h, k, B.h, X.h, max_iter, rel_tol, check_every, pc, it.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       res.ctypes.data_as(_f64p)))
+        return it[:k], res[:k]
 
     def coo_to_csr(self, coo: "Matrix") -> "Matrix":
         h = _vp()

@@ -1358,6 +1358,33 @@ int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, in
     return cg_solve(ctx, A, b->d, x->d, max_iter, rel_tol, check_every, precond, iters, rel_resid);
 }
 
+// k right-hand sides at once (solver_multi.hip).  Every check is made before the device is touched, so that they hold (and are
+// tested) on a machine without one.
+int spmv_cg_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* B, spmv_vec* X, int32_t max_iter, double rel_tol,
+                  int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
+{
+    SPMV_REQUIRE(ctx && A && B && X && iters && rel_resid, "spmv_cg_multi: null argument");
+    SPMV_REQUIRE(k >= 1 && k <= 64, "spmv_cg_multi: k = %d, must be in [1, 64]", k);
+    SPMV_REQUIRE(A->nrow == A->ncol, "spmv_cg_multi: the matrix is %d x %d, not square", A->nrow, A->ncol);
+    SPMV_REQUIRE(B->n == (int64_t)A->nrow * k && X->n == (int64_t)A->nrow * k,
+                 "spmv_cg_multi: B has %lld and X %lld entries, nrow * k = %d * %d", (long long)B->n, (long long)X->n, A->nrow, k);
+    SPMV_REQUIRE(B->n == 0 || X->n == 0 || B->d + B->n <= X->d || X->d + X->n <= B->d, "spmv_cg_multi: B and X must not overlap");
+    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_cg_multi: max_iter=%d rel_tol=%g", max_iter, rel_tol);
+    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS,
+                 "spmv_cg_multi: unknown preconditioner %d", precond);
+    if (A->format != SPMV_FMT_CSR && A->format != SPMV_FMT_ELL)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: CSR and ELL handles only (format %d), as spmv_apply_multi", A->format);
+    if (precond == SPMV_PRECOND_SYMGS)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: the symmetric Gauss-Seidel preconditioner is not built for k columns");
+    if (precond == SPMV_PRECOND_JACOBI && A->format != SPMV_FMT_CSR)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: the Jacobi preconditioner reads the diagonal of a CSR handle");
+    // the product reads the handle's own arrays: a CSR handle that released them (panel_keep_csr = 0) is refused here, on the host
+    const int64_t entries = A->format == SPMV_FMT_CSR ? A->nnz : (int64_t)A->nrow * A->k;
+    SPMV_REQUIRE(entries == 0 || (A->b && A->v), "spmv_cg_multi: this handle gave up its CSR arrays (panel_keep_csr = 0)");
+    SPMV_TRY(use_device(ctx));
+    return cg_multi_solve(ctx, A, k, B->d, X->d, max_iter, rel_tol, check_every, precond, iters, rel_resid);
+}
+
 int spmv_symgs_setup(spmv_ctx* ctx, spmv_mat* A)
 {
     SPMV_REQUIRE(ctx && A, "spmv_symgs_setup: null argument");

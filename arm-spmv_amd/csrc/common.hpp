@@ -439,6 +439,10 @@ bool adds_into_y_with_atomics(const spmv_mat* A);       // global_atomic_add_f64
 int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
              int precond, int* iters, double* rel_resid);
 int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t n, double* device_out);
+int csr_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, int* device_flag);  // 1 / a_ii (csr_inv_diag_kernel); flag != 0: a zero or missing one
+// solver_multi.hip: k independent solves A x_c = b_c in one loop, B and X row-major (n x k); iters and rel_resid: host arrays of k
+int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B, double* X, int max_iter, double rel_tol,
+                   int check_every, int precond, int32_t* iters, double* rel_resid);
 // kernels_ell.hip
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int ell_analyse(spmv_mat* m);

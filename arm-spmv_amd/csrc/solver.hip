@@ -477,6 +477,16 @@ int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t 
     return SPMV_OK;
 }
 
+// dinv[i] = 1 / a_ii of a CSR handle for spmv_cg_multi (solver_multi.hip): the kernel the Jacobi preconditioner above uses
+int csr_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, int* device_flag)
+{
+    if (A->nrow == 0) return SPMV_OK;
+    hipLaunchKernelGGL(csr_inv_diag_kernel, dim3((unsigned)ceil_div(A->nrow, kBlock)), dim3(kBlock), 0, ctx->stream, (int)A->nrow,
+                       A->row_begin, A->a, A->b, A->v, dinv, device_flag);
+    SPMV_HIP(hipGetLastError());
+    return SPMV_OK;
+}
+
 int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
              int precond, int* iters, double* rel_resid)
 {

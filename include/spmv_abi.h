@@ -497,6 +497,35 @@ enum spmv_precond
 };
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter,
             double rel_tol, int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
+/* spmv_cg_multi: k independent conjugate-gradient solves A x_c = b_c in one loop (solver_multi.hip).  B and X are
+ *   ROW-MAJOR (nrow x k), as in spmv_apply_multi: entry (i, c) at [(int64)i*k + c].  X holds the starting vectors and receives the
+ *   solutions.  iters and rel_resid are HOST arrays of k entries.  Synchronous.
+ *   Columns are independent systems - this is not block CG: every column has its own alpha, beta, gamma and delta and follows the
+ *   Chronopoulos-Gear recurrence of spmv_cg's two-launch iteration.  The product W = A U of an iteration runs
+ *   through the spmv_apply_multi path with overwrite: the matrix is read once per iteration for all k systems, and column c of the
+ *   product has the SCALAR order of additions, bit for bit, as that entry point promises.  Three launches per iteration.
+ *   Handles: 1 <= k <= 64; CSR handles (uploaded, wrapped, shards that hold a square matrix) and ELL handles.  precond:
+ *   SPMV_PRECOND_NONE, and SPMV_PRECOND_JACOBI on CSR (the diagonal as spmv_cg takes it, duplicates summed; a zero or missing
+ *   diagonal entry: SPMV_ERR_INVALID).  SPMV_PRECOND_SYMGS, Jacobi on ELL and COO / CSC / DIA handles: SPMV_ERR_UNSUPPORTED.
+ *   Stopping, per column: the host reads the k values of r.r every check_every iterations (>= 1) and after the last one; column
+ *   c has converged when rr_c <= rel_tol^2 * bb_c and is then FROZEN by a flag on the device: later iterations leave its column of
+ *   X and of every work vector untouched, bit for bit (it still rides through the product; converged columns are not compacted).
+ *   iters[c] = the iteration count of the check that froze it, else the iterations run; rel_resid[c] = sqrt(rr_c / bb_c) at that
+ *   check.  The call returns when every column is frozen or after max_iter iterations.
+ *   A column with b_c = 0: iters[c] = 0, rel_resid[c] = 0, its column of X untouched (spmv_cg's rule at b.b = 0); its 0/0 reaches
+ *   no other column and no status word.  A column whose r.r is at or below 1e-28 b_c.b_c passes quietly, as in spmv_cg.
+ *   Breakdown: p.Ap <= 0 or r.M^-1 r <= 0 in a live column, or a non-finite b.b or r.r: SPMV_ERR_INVALID, and spmv_last_error()
+ *   names the column; the other columns of X may then hold any iterate.
+ *   Deterministic: no dot product is added up in arrival order (per-workgroup partial sums per column, added in a fixed order by
+ *   the workgroup that finishes last), so two calls on the same data give the same bits - stronger than spmv_cg - and column c's
+ *   result at fixed (nrow, k, c) depends on column c of B and X alone, not on what the other columns hold.
+ *   Refused before any device use with SPMV_ERR_INVALID: null pointers, k out of range, a non-square matrix, B or X with other
+ *   than nrow * k entries, B and X overlapping, max_iter < 0, rel_tol < 0, a CSR handle without its arrays (panel_keep_csr 0).
+ *   Index arithmetic on the (nrow x k) blocks is 64-bit.  X and B need only be 8-byte aligned; where both are 16-byte aligned and
+ *   k is even the vector kernels use 16-byte accesses.  The handle's forward state, copies and plan stay as they were.
+ *   Device memory: four (Jacobi: five) work blocks of nrow * k doubles for the duration of the call. */
+int spmv_cg_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* B, spmv_vec* X, int32_t max_iter, double rel_tol,
+                  int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
 /* spmv_symgs: `sweeps` symmetric Gauss-Seidel sweeps on A*x = b, x updated in place: forward over the rows in sweep
  *   order with the newest x, then backward — the sweep the reference's `diagonal // for SymGS` fields were reserved
  *   for (include/matrix.h:36,81) and that it never wrote.  A: CSR handle holding the whole square matrix with a non-zero
