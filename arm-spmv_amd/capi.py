@@ -102,6 +102,7 @@ SIGNATURES = {
     "spmv_apply_dot": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, _f64p]),
     "spmv_cg_multi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_cg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
+    "spmv_cgls": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_double, C.POINTER(C.c_int32), _f64p, _f64p]),
     "spmv_symgs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32]),
     "spmv_symgs_setup": (C.c_int, [_vp, _vp]),
     "spmv_symgs_order": (C.c_int, [_vp, _vp, _i32p]),
@@ -454,6 +455,15 @@ class Context:
         _check(self._lib.spmv_cg_multi(self.h, A.h, k, B.h, X.h, max_iter, rel_tol, check_every, pc, it.ctypes.data_as(C.POINTER(C.c_int32)),
                                        res.ctypes.data_as(_f64p)))
         return it[:k], res[:k]
+
+    def cgls(self, A: "Matrix", b: "Vector", x: "Vector", max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
+             damp: float = 0.0):
+        """least squares min ||b - A x||^2 + damp^2 ||x||^2 by CGLS on the device, from the x passed in: any format, any shape (b has
+        nrow entries, x ncol).  The first call builds the handle's transposed state.  Stops at ||A^T r - damp^2 x|| <= rel_tol *
+        ||A^T b||; returns (iterations, ||A^T r - damp^2 x|| / ||A^T b||, ||r|| / ||b||)"""
+        it, nres, res = C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
+        _check(self._lib.spmv_cgls(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, damp, C.byref(it), C.byref(nres), C.byref(res)))
+        return it.value, nres.value, res.value
 
     def coo_to_csr(self, coo: "Matrix") -> "Matrix":
         h = _vp()

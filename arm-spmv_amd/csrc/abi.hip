@@ -4,6 +4,7 @@
 // format kernels (kernels_*.hip), the conversions (convert.hip) and the generators (generate.hip).
 // There is deliberately no CPU implementation of anything behind these entry points.
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -1383,6 +1384,23 @@ int spmv_cg_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* B
     SPMV_REQUIRE(entries == 0 || (A->b && A->v), "spmv_cg_multi: this handle gave up its CSR arrays (panel_keep_csr = 0)");
     SPMV_TRY(use_device(ctx));
     return cg_multi_solve(ctx, A, k, B->d, X->d, max_iter, rel_tol, check_every, precond, iters, rel_resid);
+}
+
+// least squares over A and A^T (solver_cgls.hip).  Every check is made before the device is touched.
+int spmv_cgls(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol, int32_t check_every,
+              double damp, int32_t* iters, double* rel_normal_resid, double* rel_resid)
+{
+    SPMV_REQUIRE(ctx && A && b && x && iters && rel_normal_resid && rel_resid, "spmv_cgls: null argument");
+    SPMV_REQUIRE(b->n == A->nrow, "spmv_cgls: b has %lld entries, the matrix (shard) %d rows", (long long)b->n, A->nrow);
+    SPMV_REQUIRE(x->n == A->ncol, "spmv_cgls: x has %lld entries, the matrix %d columns", (long long)x->n, A->ncol);
+    SPMV_REQUIRE(b->n == 0 || x->n == 0 || b->d + b->n <= x->d || x->d + x->n <= b->d, "spmv_cgls: b and x must not overlap");
+    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_cgls: max_iter=%d rel_tol=%g", max_iter, rel_tol);
+    SPMV_REQUIRE(damp >= 0.0 && std::isfinite(damp), "spmv_cgls: damp=%g, must be finite and not negative", damp);
+    // the transposed product reads the handle's own arrays the other way round: a CSR handle that released them is refused here
+    SPMV_REQUIRE(!(A->format == SPMV_FMT_CSR && A->nnz > 0 && (!A->b || !A->v)),
+                 "spmv_cgls: this handle gave up its CSR arrays (panel_keep_csr = 0)");
+    SPMV_TRY(use_device(ctx));
+    return cgls_solve(ctx, A, b->d, x->d, max_iter, rel_tol, check_every, damp, iters, rel_normal_resid, rel_resid);
 }
 
 int spmv_symgs_setup(spmv_ctx* ctx, spmv_mat* A)

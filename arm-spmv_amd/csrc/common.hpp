@@ -443,6 +443,9 @@ int csr_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, int* de
 // solver_multi.hip: k independent solves A x_c = b_c in one loop, B and X row-major (n x k); iters and rel_resid: host arrays of k
 int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B, double* X, int max_iter, double rel_tol,
                    int check_every, int precond, int32_t* iters, double* rel_resid);
+// solver_cgls.hip: CGLS for min ||b - A x||^2 + damp^2 ||x||^2 over the forward and the transposed product of any handle
+int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
+               double damp, int* iters, double* rel_normal_resid, double* rel_resid);
 // kernels_ell.hip
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int ell_analyse(spmv_mat* m);
@@ -542,6 +545,8 @@ int  rowgrouped_build(spmv_mat* m, int32_t force_kernel);  // reuse, size limit,
 int  rowgrouped_select(spmv_mat* m, int (*trial)(spmv_mat* m, const select_scratch& sv, bool model_copy, float* t_copy, float* t_own));  // COO, CSC AUTO
 int  rowgrouped_set_kernel(spmv_mat* m, int32_t kernel);  // spmv_mat_set_kernel on a COO, CSC or ELL handle
 // transpose.hip: the transposed product's state
+int  transpose_setup(spmv_mat* A);                                       // builds it once (synchronous); no part of the forward state
+int  transpose_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);  // y += A^T x; the state must be set up
 void transpose_free(spmv_mat* A);                                        // drops it (A's arrays are only borrowed)
 int  transpose_set_kernel(spmv_mat* A, int64_t kernel);                  // "transpose_kernel"
 bool transpose_get_param(const spmv_mat* A, const char* name, int64_t* value);  // "transpose_*"; false: not one of them

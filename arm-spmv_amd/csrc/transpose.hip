@@ -273,6 +273,20 @@ int transpose_build(spmv_mat* A, transpose_state* st)
 // a CSR handle that gave up col_ind / values (panel_keep_csr = 0) has no arrays left to read the other way round
 inline bool released_csr(const spmv_mat* A) { return A->format == SPMV_FMT_CSR && A->nnz > 0 && (!A->b || !A->v); }
 
+// Every check is made before the device is touched, so that they hold (and are tested) on a machine without one.
+int check_transpose_args(const char* fn, spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y)
+{
+    SPMV_REQUIRE(ctx && A && x && y, "%s: null argument", fn);
+    SPMV_REQUIRE(x->n == A->nrow, "%s: x has %lld entries, matrix (shard) has %d rows", fn, (long long)x->n, A->nrow);
+    SPMV_REQUIRE(y->n == A->ncol, "%s: y has %lld entries, matrix has %d columns", fn, (long long)y->n, A->ncol);
+    SPMV_REQUIRE(x->n == 0 || y->n == 0 || x->d + x->n <= y->d || y->d + y->n <= x->d, "%s: x and y must not overlap", fn);
+    SPMV_REQUIRE(!released_csr(A), "%s: this handle gave up its CSR arrays (panel_keep_csr = 0)", fn);
+    return SPMV_OK;
+}
+
+}  // namespace
+
+// (these two are called by the least-squares loop as well: solver_cgls.hip)
 int transpose_setup(spmv_mat* A)
 {
     SPMV_REQUIRE(!released_csr(A), "spmv_mat_transpose_setup: this handle gave up its CSR arrays (panel_keep_csr = 0)");
@@ -291,24 +305,12 @@ int transpose_setup(spmv_mat* A)
     return rc;
 }
 
-// Every check is made before the device is touched, so that they hold (and are tested) on a machine without one.
-int check_transpose_args(const char* fn, spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec* y)
-{
-    SPMV_REQUIRE(ctx && A && x && y, "%s: null argument", fn);
-    SPMV_REQUIRE(x->n == A->nrow, "%s: x has %lld entries, matrix (shard) has %d rows", fn, (long long)x->n, A->nrow);
-    SPMV_REQUIRE(y->n == A->ncol, "%s: y has %lld entries, matrix has %d columns", fn, (long long)y->n, A->ncol);
-    SPMV_REQUIRE(x->n == 0 || y->n == 0 || x->d + x->n <= y->d || y->d + y->n <= x->d, "%s: x and y must not overlap", fn);
-    SPMV_REQUIRE(!released_csr(A), "%s: this handle gave up its CSR arrays (panel_keep_csr = 0)", fn);
-    return SPMV_OK;
-}
-
 int transpose_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
 {
     const transpose_state* st = A->tr;
     if (A->format == SPMV_FMT_DIA) return dia_transpose_apply(ctx, A, st, x, y);
     return st->comp ? mat_apply_ex(ctx, st->comp, x, y) : SPMV_OK;
 }
-}  // namespace
 
 void transpose_free(spmv_mat* A)
 {

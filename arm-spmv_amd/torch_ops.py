@@ -22,7 +22,7 @@ def context_on_current_stream(device: int | None = None) -> "capi.Context":
 
 
 class SparseOperator:
-    """A (nrow x ncol) of a capi.Matrix: matvec(x) = A x, rmatvec(y) = A^T y, each into a fresh tensor"""
+    """A (nrow x ncol) of a capi.Matrix: matvec(x) = A x, rmatvec(y) = A^T y, lstsq(b) = argmin ||b - A x||, each into a fresh tensor"""
 
     def __init__(self, ctx: "capi.Context", A: "capi.Matrix"):
         self.ctx, self.A = ctx, A
@@ -48,6 +48,20 @@ class SparseOperator:
         self._check(y, nrow, "rmatvec")
         x = torch.zeros(ncol, dtype=torch.float64, device=self.device)
         self.ctx.apply_transpose(self.A, self.ctx.wrap_vector(y), self.ctx.wrap_vector(x))
+        return x
+
+    def lstsq(self, b: torch.Tensor, x0: torch.Tensor | None = None, **kw) -> torch.Tensor:
+        """argmin ||b - A x||^2 + damp^2 ||x||^2 by capi.Context.cgls from x0 (default 0), into a fresh tensor; kw: max_iter, rel_tol,
+        check_every, damp.  (iterations, normal residual, residual) of the solve are left in self.last_lstsq.  No autograd through
+        the solve"""
+        nrow, ncol = self.shape
+        self._check(b, nrow, "lstsq")
+        if x0 is None:
+            x = torch.zeros(ncol, dtype=torch.float64, device=self.device)
+        else:
+            self._check(x0, ncol, "lstsq x0")
+            x = x0.detach().clone()
+        self.last_lstsq = self.ctx.cgls(self.A, self.ctx.wrap_vector(b.detach()), self.ctx.wrap_vector(x), **kw)
         return x
 
 

@@ -526,6 +526,29 @@ int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, in
  *   Device memory: four (Jacobi: five) work blocks of nrow * k doubles for the duration of the call. */
 int spmv_cg_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* B, spmv_vec* X, int32_t max_iter, double rel_tol,
                   int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
+/* spmv_cgls: least squares min ||b - A x||^2 + damp^2 ||x||^2 by CGLS, starting from the x passed in (solver_cgls.hip; DESIGN.md
+ *   12).  b has nrow entries (a shard: its rows), x has ncol.  A is any handle spmv_apply and spmv_apply_transpose both accept: all
+ *   five formats, uploaded, wrapped, or a shard, which is simply the rectangular matrix it holds.  Synchronous.
+ *   The handle's transposed state is built on first use, although the handle is passed as const, as spmv_apply_transpose and
+ *   SPMV_PRECOND_SYMGS build theirs; the forward state, copies, device_bytes and plan stay as they were.
+ *   Recurrence:  r = b - A x;  s = A^T r - damp^2 x;  p = s;  gamma = s.s;  then per iteration  q = A p;  delta = q.q + damp^2 p.p;
+ *   alpha = gamma / delta;  x += alpha p;  r -= alpha q;  s = A^T r - damp^2 x;  gamma' = s.s;  beta = gamma' / gamma;
+ *   p = s + beta p;  gamma = gamma'.  Six launches per iteration (the two products and four vector kernels); alpha, beta, gamma and
+ *   delta stay on the device; the host reads gamma, r.r and a status word every check_every iterations (>= 1) and after the last.
+ *   Stopping: gamma <= rel_tol^2 * ||A^T b||^2 (the reference does not depend on x0; one more transposed product at the set-up), or
+ *   max_iter iterations.  *iters = iterations run, *rel_normal_resid = sqrt(gamma / ||A^T b||^2) and *rel_resid = sqrt(r.r / b.b) at
+ *   the last check (max_iter = 0: those of x0).  A^T b = 0, b = 0 among it: *iters = 0, both outputs 0, x untouched (spmv_cg's rule
+ *   at b.b = 0).  An iteration whose gamma is at or below 1e-28 ||A^T b||^2 passes quietly, as in spmv_cg; gamma = 0 ends the solve.
+ *   SPMV_ERR_INVALID with a message naming the quantity: a non-finite b.b, ||A^T b||^2, gamma or r.r, or delta <= 0 while gamma is
+ *   above that floor.
+ *   Refused before any device use with SPMV_ERR_INVALID: null pointers, b with other than nrow or x with other than ncol entries,
+ *   b and x overlapping, max_iter < 0, rel_tol < 0, damp < 0 or not finite, a CSR handle without its arrays (panel_keep_csr 0).
+ *   Deterministic dot products (per-workgroup partial sums added in a fixed order by the workgroup that finishes last): a solve is
+ *   exactly as reproducible as the two products its handle runs.  x and b need only be 8-byte aligned; where they are 16-byte
+ *   aligned the vector kernels use 16-byte accesses on them.  nrow = 0 or ncol = 0: SPMV_OK, *iters = 0, nothing is launched.
+ *   Device memory: work vectors r, q (nrow) and p, s (ncol) and a small scalar block for the duration of the call. */
+int spmv_cgls(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
+              int32_t check_every, double damp, int32_t* iters, double* rel_normal_resid, double* rel_resid);
 /* spmv_symgs: `sweeps` symmetric Gauss-Seidel sweeps on A*x = b, x updated in place: forward over the rows in sweep
  *   order with the newest x, then backward — the sweep the reference's `diagonal // for SymGS` fields were reserved
  *   for (include/matrix.h:36,81) and that it never wrote.  A: CSR handle holding the whole square matrix with a non-zero
