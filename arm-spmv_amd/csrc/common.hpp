@@ -56,6 +56,8 @@ constexpr int kNumCu     = 256;
 constexpr int kMaxGrid   = kNumCu * 8;  // grid-stride cap for streaming kernels (8 blocks / CU)
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// workgroups of a grid-stride kernel over n elements, one per thread: at least one, at most kMaxGrid
+static inline int stream_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, ceil_div(n, kBlock))); }
 
 // ---- counter-based PRNG shared by the device generators and their numpy twin ------------------------
 // splitmix64 finaliser; stream keys are derived on the host, the device adds the element index.

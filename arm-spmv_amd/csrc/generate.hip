@@ -106,7 +106,6 @@ __global__ __launch_bounds__(kBlock) void gen_vec_kernel(double* __restrict__ d,
         d[i] = u64_to_unit(splitmix64(key + (uint64_t)(index_offset + i)));
 }
 
-inline unsigned stream_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, ceil_div(n, kBlock))); }
 }  // namespace
 
 int gen_csr_uniform(spmv_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t ncol, int32_t k, int32_t band,

@@ -11,7 +11,6 @@ namespace spmv
 {
 namespace
 {
-typedef double f64x2_t __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(kBlock) void fill_kernel(double* __restrict__ d, int64_t n, double a)
 {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) d[i] = a;
@@ -85,12 +84,12 @@ __global__ __launch_bounds__(kBlock) void axpby_kernel(int64_t n, double alpha, 
 // element-wise arithmetic, so the results are bit-identical to the one-element kernel.  NT: nontemporal loads and
 // stores for vectors far beyond the caches.
 template <int MODE, bool NT>
-__global__ __launch_bounds__(kBlock) void axpby2_kernel(int64_t npairs, double alpha, const f64x2_t* __restrict__ x,
-                                                        double beta, const f64x2_t* __restrict__ y, f64x2_t* __restrict__ w)
+__global__ __launch_bounds__(kBlock) void axpby2_kernel(int64_t npairs, double alpha, const f64x2* __restrict__ x,
+                                                        double beta, const f64x2* __restrict__ y, f64x2* __restrict__ w)
 {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock)
     {
-        f64x2_t xv = {0.0, 0.0}, yv = {0.0, 0.0}, r;
+        f64x2 xv = {0.0, 0.0}, yv = {0.0, 0.0}, r;
         if constexpr (MODE != kBetaY) xv = NT ? __builtin_nontemporal_load(x + i) : x[i];
         if constexpr (MODE != kAlphaX) yv = NT ? __builtin_nontemporal_load(y + i) : y[i];
 #pragma unroll
@@ -174,8 +173,8 @@ __global__ __launch_bounds__(kBlock) void dia_kernel(int nrow, int jmax, int ndi
             const double* p = val + (size_t)(r0 + r) * stride + d0 + d_mine;
             if constexpr (WIDE)
             {
-                f64x2_t v = {0.0, 0.0};
-                if (r0 + r < nrow && d0 + d_mine < ndiags) v = __builtin_nontemporal_load((const f64x2_t*)p);  // stride even: the pair is 16-byte aligned and inside the row
+                f64x2 v = {0.0, 0.0};
+                if (r0 + r < nrow && d0 + d_mine < ndiags) v = __builtin_nontemporal_load((const f64x2*)p);  // stride even: the pair is 16-byte aligned and inside the row
                 stage[2 * j]     = v[0];
                 stage[2 * j + 1] = v[1];
             }
@@ -216,7 +215,6 @@ __global__ __launch_bounds__(kBlock) void dia_kernel(int nrow, int jmax, int ndi
     if (mine) y[i] = acc;
 }
 
-inline int stream_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, ceil_div(n, kBlock))); }
 }  // namespace
 
 namespace
@@ -280,11 +278,11 @@ static void launch_axpby(hipStream_t s, int64_t n, double alpha, const double* x
     {
         const dim3 grid(stream_grid(npairs)), block(kBlock);
         if (n >= (int64_t)(8 << 20))  // three vectors of 64 MiB and more: nothing of them survives in a cache anyway
-            hipLaunchKernelGGL((axpby2_kernel<MODE, true>), grid, block, 0, s, npairs, alpha, (const f64x2_t*)x, beta,
-                               (const f64x2_t*)y, (f64x2_t*)w);
+            hipLaunchKernelGGL((axpby2_kernel<MODE, true>), grid, block, 0, s, npairs, alpha, (const f64x2*)x, beta,
+                               (const f64x2*)y, (f64x2*)w);
         else
-            hipLaunchKernelGGL((axpby2_kernel<MODE, false>), grid, block, 0, s, npairs, alpha, (const f64x2_t*)x, beta,
-                               (const f64x2_t*)y, (f64x2_t*)w);
+            hipLaunchKernelGGL((axpby2_kernel<MODE, false>), grid, block, 0, s, npairs, alpha, (const f64x2*)x, beta,
+                               (const f64x2*)y, (f64x2*)w);
     }
     const int64_t done = npairs * 2;
     if (done < n)

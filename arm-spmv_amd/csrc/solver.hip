@@ -6,8 +6,9 @@
 //                  riding along (fused into the write-back of the panel kernel: saves a pass over w and y; other kernels
 //                  run a dot pass behind)
 //   cg_solve       conjugate gradients for symmetric positive definite A, plain, Jacobi- or symmetric-Gauss-Seidel-
-//                  preconditioned (symgs.hip).  Three launches per iteration
-//                  (product+dot, x/r update+dot, direction update); alpha and beta are computed on the device from
+//                  preconditioned (symgs.hip).  Two launches per iteration (product+dot, cg_fused_kernel), or the textbook
+//                  three (product+dot, cg_update_kernel<Z, WIDE>, cg_direction_kernel<Z, WIDE>: one template each for every
+//                  kind of z = M^-1 r and both access widths); alpha and beta are computed on the device from
 //                  scalars that never leave it, so iterations queue up without a host round trip; the host looks at
 //                  the residual every `check_every` iterations only.  (A hipGraph replay of the iterations in
 //                  between was built and measured slower than plain launches: kept behind SPMV_CG_GRAPH=1.)
@@ -16,32 +17,21 @@
 // in each arrangement below and at both vector widths, against conjugate gradients in extended precision
 // (tests/solver_ref.py, tests/test_gpu_solver_steps.py); overwrite and the fused dot of mat_apply_ex bit for bit on exact inputs
 // (tests/test_gpu_exact.py); the solution through the oracle's product (tests/test_gpu_solver.py).
+//
+// The workgroup sum (block_sum), the Jacobi set-up and the host's read of the scalars are solver_common.hpp's, shared with
+// solver_multi.hip and solver_cgls.hip.  spmv_cg's own dots stay slotted atomic adds in arrival order (common.hpp: kDotSlots).
 #include <cmath>
 #include <cstdlib>
 #include <vector>
 
 #include "common.hpp"
+#include "solver_common.hpp"
 #include "wave.hpp"
 
 namespace spmv
 {
 namespace
 {
-inline int stream_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, ceil_div(n, kBlock))); }
-
-// sum over the workgroup, valid in thread 0
-__device__ __forceinline__ double block_sum(double v)
-{
-    __shared__ double s_part[kBlock / kWave];
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double total = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < kBlock / kWave; ++w) total += s_part[w];
-    return total;
-}
-
 // Totals of two slotted accumulators, for every thread of the workgroup: lanes 0-31 of the first wavefront read the
 // slots of `a`, lanes 32-63 those of `b` (one load latency instead of a chain of 32), halves are summed, LDS broadcast.
 __device__ __forceinline__ void slot_sum2_block(const double* a, const double* b, double* ta, double* tb)
@@ -134,102 +124,6 @@ __global__ __launch_bounds__(kBlock) void cg_init_kernel(int64_t n, const double
     }
 }
 
-// Jacobi-preconditioned pair (scalar width): alpha = rz_k / pq_k; x += alpha p; r -= alpha q; rr_{k+1} += r.r;
-// rz_{k+1} += r . D^-1 r   and   beta = rz_{k+1} / rz_k; p = D^-1 r + beta p
-__global__ __launch_bounds__(kBlock) void pcg_update_kernel(int64_t n, int k, const double* __restrict__ p,
-                                                            const double* __restrict__ q, double* __restrict__ x,
-                                                            double* __restrict__ r, CgScalars* __restrict__ s,
-                                                            const double* __restrict__ dinv)
-{
-    double pq, rz_k;
-    slot_sum2_block(s->pq[k & 3], s->rz[k & 3], &pq, &rz_k);
-    if (!(pq > 0.0))
-    {
-        // Breakdown (the matrix is not positive definite) only while there is a residual to speak of.  Once r is zero
-        // or has shrunk to where r.r and p.Ap underflow (the system was solved between two looks of the host), p.Ap = 0
-        // is the end of the iteration, not an error: x and r stay, r.r of the next iteration stays at its cleared 0,
-        // so every queued iteration ends here as well and the host reads a residual of 0.
-        if (blockIdx.x == 0 && threadIdx.x == 0 && slot_sum(s->rr[k & 3]) > 1e-60 * slot_sum(s->bb)) s->status = 1.0;
-        return;
-    }
-    const double alpha = rz_k / pq;
-    double       rr = 0.0, rz = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-    {
-        x[i]            = fma(alpha, p[i], x[i]);
-        const double ri = fma(-alpha, q[i], r[i]);
-        r[i]            = ri;
-        rr              = fma(ri, ri, rr);
-        rz              = fma(ri * dinv[i], ri, rz);
-    }
-    const double t_rr = block_sum(rr);
-    __syncthreads();
-    const double t_rz = block_sum(rz);
-    if (threadIdx.x == 0)
-    {
-        slot_add(s->rr[(k + 1) & 3], t_rr);
-        slot_add(s->rz[(k + 1) & 3], t_rz);
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void pcg_direction_kernel(int64_t n, int k, const double* __restrict__ r,
-                                                               double* __restrict__ p, CgScalars* __restrict__ s,
-                                                               const double* __restrict__ dinv)
-{
-    double rz_k, rz_next;
-    slot_sum2_block(s->rz[k & 3], s->rz[(k + 1) & 3], &rz_k, &rz_next);
-    const double beta = rz_k > 0.0 ? rz_next / rz_k : 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-        p[i] = fma(beta, p[i], r[i] * dinv[i]);
-    if (blockIdx.x == 0 && threadIdx.x < kDotSlots)
-    {
-        s->rr[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
-        s->rz[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
-        s->pq[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
-    }
-}
-
-// General preconditioner (z = M^-1 r comes from a sweep between the two kernels, r . z from a dot pass behind it):
-// alpha = rz_k / pq_k; x += alpha p; r -= alpha q; rr_{k+1} += r.r    and    beta = rz_{k+1} / rz_k; p = z + beta p
-__global__ __launch_bounds__(kBlock) void gcg_update_kernel(int64_t n, int k, const double* __restrict__ p, const double* __restrict__ q,
-                                                            double* __restrict__ x, double* __restrict__ r, CgScalars* __restrict__ s)
-{
-    double pq, rz_k;
-    slot_sum2_block(s->pq[k & 3], s->rz[k & 3], &pq, &rz_k);
-    if (!(pq > 0.0))
-    {
-        // a breakdown only while there is a residual to speak of (see pcg_update_kernel)
-        if (blockIdx.x == 0 && threadIdx.x == 0 && slot_sum(s->rr[k & 3]) > 1e-60 * slot_sum(s->bb)) s->status = 1.0;
-        return;
-    }
-    const double alpha = rz_k / pq;
-    double       rr    = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-    {
-        x[i]            = fma(alpha, p[i], x[i]);
-        const double ri = fma(-alpha, q[i], r[i]);
-        r[i]            = ri;
-        rr              = fma(ri, ri, rr);
-    }
-    const double total = block_sum(rr);
-    if (threadIdx.x == 0) slot_add(s->rr[(k + 1) & 3], total);
-}
-
-__global__ __launch_bounds__(kBlock) void gcg_direction_kernel(int64_t n, int k, const double* __restrict__ z, double* __restrict__ p,
-                                                               CgScalars* __restrict__ s)
-{
-    double rz_k, rz_next;
-    slot_sum2_block(s->rz[k & 3], s->rz[(k + 1) & 3], &rz_k, &rz_next);
-    const double beta = rz_k > 0.0 ? rz_next / rz_k : 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) p[i] = fma(beta, p[i], z[i]);
-    if (blockIdx.x == 0 && threadIdx.x < kDotSlots)
-    {
-        s->rr[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
-        s->rz[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
-        s->pq[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
-    }
-}
-
 // 1 / a_ii of a CSR handle (duplicates of the diagonal entry are summed, as the product would); flag != 0: a zero or
 // missing diagonal entry
 __global__ __launch_bounds__(kBlock) void csr_inv_diag_kernel(int nrow, int64_t row_begin, const int32_t* __restrict__ row_ptr,
@@ -250,115 +144,107 @@ __global__ __launch_bounds__(kBlock) void csr_inv_diag_kernel(int nrow, int64_t 
     dinv[i] = 1.0 / d;
 }
 
-// alpha = rr_k / pq_k;  x += alpha p;  r -= alpha q;  rr_{k+1} += r.r
-__global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t n, int k, const double* __restrict__ p,
-                                                           const double* __restrict__ q, double* __restrict__ x,
-                                                           double* __restrict__ r, CgScalars* __restrict__ s)
+// ---- three launches per iteration: the product (with p . A p riding along), the update, the direction --------------------------
+// What z = M^-1 r is, and with it where gamma_k = r_k . z_k lives:
+//   r        r itself: no preconditioner, gamma is r . r (ring rr)
+//   jacobi   r * dinv, formed in the kernels; gamma in ring rz, which the update kernel accumulates next to r . r
+//   given    a vector of its own (the symmetric Gauss-Seidel sweep runs between the two kernels); gamma in ring rz, from a dot
+//            pass behind the sweep
+// WIDE: two elements per lane and 16-byte accesses (the vectors are 16-byte aligned; an odd last element by one extra lane) - the
+// plain arrangement only.
+enum class Z
 {
-    double pq, rr_k;
-    slot_sum2_block(s->pq[k & 3], s->rr[k & 3], &pq, &rr_k);
+    r,
+    jacobi,
+    given
+};
+
+// alpha = gamma_k / pq_k;  x += alpha p;  r -= alpha q;  rr_{k+1} += r.r;  (jacobi) rz_{k+1} += r . D^-1 r
+template <Z ZK, bool WIDE>
+__global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t n, int k, const double* __restrict__ p, const double* __restrict__ q,
+                                                           double* __restrict__ x, double* __restrict__ r, CgScalars* __restrict__ s,
+                                                           const double* __restrict__ dinv)
+{
+    static_assert(!WIDE || ZK == Z::r, "16-byte accesses: without a preconditioner only");
+    double (*const G)[kDotDoubles] = ZK == Z::r ? s->rr : s->rz;
+    double pq, gamma;
+    slot_sum2_block(s->pq[k & 3], G[k & 3], &pq, &gamma);
     if (!(pq > 0.0))
     {
-        // a breakdown only while there is a residual to speak of (see pcg_update_kernel)
-        if (blockIdx.x == 0 && threadIdx.x == 0 && rr_k > 1e-60 * slot_sum(s->bb)) s->status = 1.0;
+        // Breakdown (the matrix is not positive definite) only while there is a residual to speak of.  Once r is zero
+        // or has shrunk to where r.r and p.Ap underflow (the system was solved between two looks of the host), p.Ap = 0
+        // is the end of the iteration, not an error: x and r stay, r.r of the next iteration stays at its cleared 0,
+        // so every queued iteration ends here as well and the host reads a residual of 0.
+        if (blockIdx.x == 0 && threadIdx.x == 0 && (ZK == Z::r ? gamma : slot_sum(s->rr[k & 3])) > 1e-60 * slot_sum(s->bb)) s->status = 1.0;
         return;  // uniform over the grid: every thread read the same scalar
     }
-    const double alpha = rr_k / pq;
-    double       rr    = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    const double alpha = gamma / pq;
+    double       rr = 0.0, rz = 0.0;
+    auto one = [&](double pi, double qi, double& xi, double& ri, double di) {
+        xi = fma(alpha, pi, xi);
+        ri = fma(-alpha, qi, ri);
+        rr = fma(ri, ri, rr);
+        if (ZK == Z::jacobi) rz = fma(ri * di, ri, rz);
+    };
+    if constexpr (WIDE)
     {
-        x[i]            = fma(alpha, p[i], x[i]);
-        const double ri = fma(-alpha, q[i], r[i]);
-        r[i]            = ri;
-        rr              = fma(ri, ri, rr);
-    }
-    const double total = block_sum(rr);
-    if (threadIdx.x == 0) slot_add(s->rr[(k + 1) & 3], total);
-}
-
-// The same two kernels with two elements per lane and 16-byte accesses (used when the vectors are 16-byte aligned);
-// an odd last element is handled by one extra lane.
-typedef double f64x2_t __attribute__((ext_vector_type(2)));
-
-__global__ __launch_bounds__(kBlock) void cg_update2_kernel(int64_t n, int k, const double* __restrict__ p,
-                                                            const double* __restrict__ q, double* __restrict__ x,
-                                                            double* __restrict__ r, CgScalars* __restrict__ s)
-{
-    double pq, rr_k;
-    slot_sum2_block(s->pq[k & 3], s->rr[k & 3], &pq, &rr_k);
-    if (!(pq > 0.0))
-    {
-        // a breakdown only while there is a residual to speak of (see pcg_update_kernel)
-        if (blockIdx.x == 0 && threadIdx.x == 0 && rr_k > 1e-60 * slot_sum(s->bb)) s->status = 1.0;
-        return;
-    }
-    const double  alpha  = rr_k / pq;
-    const int64_t npairs = n / 2;
-    double        rr     = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock)
-    {
-        const f64x2_t pv = ((const f64x2_t*)p)[i], qv = ((const f64x2_t*)q)[i];
-        f64x2_t       xv = ((f64x2_t*)x)[i], rv = ((f64x2_t*)r)[i];
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
+        const int64_t npairs = n / 2;
+        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock)
         {
-            xv[e] = fma(alpha, pv[e], xv[e]);
-            rv[e] = fma(-alpha, qv[e], rv[e]);
-            rr    = fma(rv[e], rv[e], rr);
+            const f64x2 pv = ((const f64x2*)p)[i], qv = ((const f64x2*)q)[i], xv = ((f64x2*)x)[i], rv = ((f64x2*)r)[i];
+            double      xe[2] = {xv[0], xv[1]}, re[2] = {rv[0], rv[1]};
+            one(pv[0], qv[0], xe[0], re[0], 1.0);
+            one(pv[1], qv[1], xe[1], re[1], 1.0);
+            ((f64x2*)x)[i] = f64x2{xe[0], xe[1]};
+            ((f64x2*)r)[i] = f64x2{re[0], re[1]};
         }
-        ((f64x2_t*)x)[i] = xv;
-        ((f64x2_t*)r)[i] = rv;
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(p[n - 1], q[n - 1], x[n - 1], r[n - 1], 1.0);
     }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+    else
+        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+            one(p[i], q[i], x[i], r[i], ZK == Z::jacobi ? dinv[i] : 1.0);
+    const double t_rr = block_sum(rr);
+    if (ZK == Z::jacobi) __syncthreads();
+    const double t_rz = ZK == Z::jacobi ? block_sum(rz) : 0.0;
+    if (threadIdx.x == 0)
     {
-        const int64_t i  = n - 1;
-        x[i]             = fma(alpha, p[i], x[i]);
-        const double ri  = fma(-alpha, q[i], r[i]);
-        r[i]             = ri;
-        rr               = fma(ri, ri, rr);
+        slot_add(s->rr[(k + 1) & 3], t_rr);
+        if (ZK == Z::jacobi) slot_add(s->rz[(k + 1) & 3], t_rz);
     }
-    const double total = block_sum(rr);
-    if (threadIdx.x == 0) slot_add(s->rr[(k + 1) & 3], total);
 }
 
-__global__ __launch_bounds__(kBlock) void cg_direction2_kernel(int64_t n, int k, const double* __restrict__ r,
-                                                               double* __restrict__ p, CgScalars* __restrict__ s)
+// beta = gamma_{k+1} / gamma_k;  p = z + beta p;  clear the slots of iteration k + 2.  `z` is r unless Z is given
+template <Z ZK, bool WIDE>
+__global__ __launch_bounds__(kBlock) void cg_direction_kernel(int64_t n, int k, const double* __restrict__ z, double* __restrict__ p,
+                                                              CgScalars* __restrict__ s, const double* __restrict__ dinv)
 {
-    double rr_k, rr_next;
-    slot_sum2_block(s->rr[k & 3], s->rr[(k + 1) & 3], &rr_k, &rr_next);
-    const double  beta   = rr_k > 0.0 ? rr_next / rr_k : 0.0;
-    const int64_t npairs = n / 2;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock)
+    static_assert(!WIDE || ZK == Z::r, "16-byte accesses: without a preconditioner only");
+    double (*const G)[kDotDoubles] = ZK == Z::r ? s->rr : s->rz;
+    double gamma, gamma_next;
+    slot_sum2_block(G[k & 3], G[(k + 1) & 3], &gamma, &gamma_next);
+    const double beta = gamma > 0.0 ? gamma_next / gamma : 0.0;
+    auto one = [&](double zi, double di, double pi) { return fma(beta, pi, ZK == Z::jacobi ? zi * di : zi); };
+    if constexpr (WIDE)
     {
-        const f64x2_t rv = ((const f64x2_t*)r)[i];
-        f64x2_t       pv = ((f64x2_t*)p)[i];
-        pv[0]            = fma(beta, pv[0], rv[0]);
-        pv[1]            = fma(beta, pv[1], rv[1]);
-        ((f64x2_t*)p)[i] = pv;
+        const int64_t npairs = n / 2;
+        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock)
+        {
+            const f64x2 zv = ((const f64x2*)z)[i], pv = ((f64x2*)p)[i];
+            ((f64x2*)p)[i] = f64x2{one(zv[0], 1.0, pv[0]), one(zv[1], 1.0, pv[1])};
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) p[n - 1] = one(z[n - 1], 1.0, p[n - 1]);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) p[n - 1] = fma(beta, p[n - 1], r[n - 1]);
+    else
+        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+            p[i] = one(z[i], ZK == Z::jacobi ? dinv[i] : 1.0, p[i]);
     if (blockIdx.x == 0 && threadIdx.x < kDotSlots)
     {
         s->rr[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
+        if (ZK != Z::r) s->rz[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
         s->pq[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
     }
 }
 
-// beta = rr_{k+1} / rr_k;  p = r + beta p;  clear the slots of iteration k + 2
-__global__ __launch_bounds__(kBlock) void cg_direction_kernel(int64_t n, int k, const double* __restrict__ r,
-                                                              double* __restrict__ p, CgScalars* __restrict__ s)
-{
-    double rr_k, rr_next;
-    slot_sum2_block(s->rr[k & 3], s->rr[(k + 1) & 3], &rr_k, &rr_next);
-    const double beta = rr_k > 0.0 ? rr_next / rr_k : 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-        p[i] = fma(beta, p[i], r[i]);
-    if (blockIdx.x == 0 && threadIdx.x < kDotSlots)
-    {
-        s->rr[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
-        s->pq[(k + 2) & 3][threadIdx.x * kDotStride] = 0.0;
-    }
-}
 // ---- two launches per iteration (round 4) ----------------------------------------------------------------------------------
 // The three-launch iteration needs r.r of the UPDATED residual before it can form beta, hence a kernel boundary between the
 // x / r update and the direction update.  The Chronopoulos-Gear arrangement of the same recurrences moves the product onto
@@ -429,18 +315,18 @@ __global__ __launch_bounds__(kBlock) void cg_fused_kernel(int64_t n, int k, cons
         const int64_t npairs = n / 2;
         for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock)
         {
-            const f64x2_t wv = ((const f64x2_t*)w)[i];
-            const f64x2_t uv = PRE ? ((const f64x2_t*)u)[i] : ((const f64x2_t*)r)[i];
-            const f64x2_t dv = PRE ? ((const f64x2_t*)dinv)[i] : f64x2_t{1.0, 1.0};
-            const f64x2_t pv = ((const f64x2_t*)p)[i], sw = ((const f64x2_t*)sv)[i], xv = ((const f64x2_t*)x)[i], rv = ((const f64x2_t*)r)[i];
+            const f64x2 wv = ((const f64x2*)w)[i];
+            const f64x2 uv = PRE ? ((const f64x2*)u)[i] : ((const f64x2*)r)[i];
+            const f64x2 dv = PRE ? ((const f64x2*)dinv)[i] : f64x2{1.0, 1.0};
+            const f64x2 pv = ((const f64x2*)p)[i], sw = ((const f64x2*)sv)[i], xv = ((const f64x2*)x)[i], rv = ((const f64x2*)r)[i];
             double        pe[2] = {pv[0], pv[1]}, se[2] = {sw[0], sw[1]}, xe[2] = {xv[0], xv[1]}, re[2] = {rv[0], rv[1]}, ue[2];
             one(wv[0], uv[0], pe[0], se[0], xe[0], re[0], dv[0], ue[0]);
             one(wv[1], uv[1], pe[1], se[1], xe[1], re[1], dv[1], ue[1]);
-            ((f64x2_t*)p)[i]  = f64x2_t{pe[0], pe[1]};
-            ((f64x2_t*)sv)[i] = f64x2_t{se[0], se[1]};
-            ((f64x2_t*)x)[i]  = f64x2_t{xe[0], xe[1]};
-            ((f64x2_t*)r)[i]  = f64x2_t{re[0], re[1]};
-            if (PRE) ((f64x2_t*)u)[i] = f64x2_t{ue[0], ue[1]};
+            ((f64x2*)p)[i]  = f64x2{pe[0], pe[1]};
+            ((f64x2*)sv)[i] = f64x2{se[0], se[1]};
+            ((f64x2*)x)[i]  = f64x2{xe[0], xe[1]};
+            ((f64x2*)r)[i]  = f64x2{re[0], re[1]};
+            if (PRE) ((f64x2*)u)[i] = f64x2{ue[0], ue[1]};
         }
         if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
         {
@@ -477,7 +363,7 @@ int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t 
     return SPMV_OK;
 }
 
-// dinv[i] = 1 / a_ii of a CSR handle for spmv_cg_multi (solver_multi.hip): the kernel the Jacobi preconditioner above uses
+// dinv[i] = 1 / a_ii of a CSR handle: the one launch of csr_inv_diag_kernel (through jacobi_inverse_diagonal, solver_common.hpp)
 int csr_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, int* device_flag)
 {
     if (A->nrow == 0) return SPMV_OK;
@@ -519,19 +405,13 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
         // Jacobi: the diagonal the reference's containers carry "for SymGS" (include/matrix.h:36); taken from the CSR arrays
         if (A->format != SPMV_FMT_CSR || !A->b || !A->v)
             SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg: the Jacobi preconditioner reads the diagonal of a CSR handle");
-        SPMV_TRY(ensure_scratch(ctx, 64));
-        int* flag   = (int*)ctx->scratch;
-        int  h_flag = 0;
         if (hipMalloc(&dinv, sizeof(double) * (size_t)n) != hipSuccess)
             SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg: out of device memory for the diagonal (%lld entries)", (long long)n);
-        (void)hipMemsetAsync(flag, 0, sizeof(int), st);
-        hipLaunchKernelGGL(csr_inv_diag_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, st, (int)n, A->row_begin,
-                           A->a, A->b, A->v, dinv, flag);
-        if (hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
-            h_flag != 0)
+        const int rc_d = jacobi_inverse_diagonal(ctx, A, dinv, "spmv_cg");
+        if (rc_d != SPMV_OK)
         {
             release();
-            SPMV_FAIL(SPMV_ERR_INVALID, "spmv_cg: the matrix has a zero or missing diagonal entry (Jacobi preconditioner)");
+            return rc_d;
         }
     }
     if (hipMalloc(&r, sizeof(double) * (size_t)n) != hipSuccess || hipMalloc(&p, sizeof(double) * (size_t)n) != hipSuccess ||
@@ -562,20 +442,12 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
     };
     // ring < 0: everything (once, after the set-up); else the r.r accumulator of that ring slot and the status word
     auto      fetch = [&](int ring) -> int {
-        hipError_t e = hipSuccess;
-        if (ring < 0)
-            e = hipMemcpyAsync(&h, s, sizeof(CgScalars), hipMemcpyDeviceToHost, st);
-        else
-        {
-            e = hipMemcpyAsync(h.rr[ring], s->rr[ring], sizeof(double) * kDotDoubles, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(&h.status, &s->status, sizeof(double), hipMemcpyDeviceToHost, st);
-        }
-        if (e != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        {
-            set_error("spmv_cg: reading the iteration scalars failed: %s", hipGetErrorString(hipGetLastError()));
-            return SPMV_ERR_HIP;
-        }
-        return SPMV_OK;
+        if (ring < 0) return read_scalars(ctx, &h, s, sizeof(CgScalars), "spmv_cg");
+        // the status word is queued ahead of the slot's read, so that one wait serves both: a second wait per look was measured at
+        // 10-20 us (profiles/solver_helpers_ab.txt).  Should queueing it fail, read_scalars reads it and reports
+        if (hipMemcpyAsync(&h.status, &s->status, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
+            SPMV_TRY(read_scalars(ctx, &h.status, &s->status, sizeof(double), "spmv_cg"));
+        return read_scalars(ctx, h.rr[ring], s->rr[ring], sizeof(double) * kDotDoubles, "spmv_cg");
     };
     do
     {
@@ -667,28 +539,34 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
             ex.dot_w     = p;
             ex.dot_out   = s->pq[kk & 3];
             SPMV_TRY(mat_apply_ex(ctx, A, p, q, ex));  // q = A p, pq_k = p . q
+#define SPMV_CG_UPDATE(ZK, WIDE, GRID) \
+    hipLaunchKernelGGL((cg_update_kernel<ZK, WIDE>), dim3(GRID), dim3(kBlock), 0, st, n, kk, p, q, x, r, s, dinv)
+#define SPMV_CG_DIRECTION(ZK, WIDE, GRID, ZVEC) \
+    hipLaunchKernelGGL((cg_direction_kernel<ZK, WIDE>), dim3(GRID), dim3(kBlock), 0, st, n, kk, ZVEC, p, s, dinv)
             if (z)
             {
-                hipLaunchKernelGGL(gcg_update_kernel, dim3(grid), dim3(kBlock), 0, st, n, kk, p, q, x, r, s);
+                SPMV_CG_UPDATE(Z::given, false, grid);
                 SPMV_TRY(symgs_sweep(ctx, A, r, z, true));
                 SPMV_TRY(vec_dot_accumulate(ctx, r, z, n, s->rz[(kk + 1) & 3]));
-                hipLaunchKernelGGL(gcg_direction_kernel, dim3(grid), dim3(kBlock), 0, st, n, kk, z, p, s);
+                SPMV_CG_DIRECTION(Z::given, false, grid, z);
             }
             else if (dinv)
             {
-                hipLaunchKernelGGL(pcg_update_kernel, dim3(grid), dim3(kBlock), 0, st, n, kk, p, q, x, r, s, dinv);
-                hipLaunchKernelGGL(pcg_direction_kernel, dim3(grid), dim3(kBlock), 0, st, n, kk, r, p, s, dinv);
+                SPMV_CG_UPDATE(Z::jacobi, false, grid);
+                SPMV_CG_DIRECTION(Z::jacobi, false, grid, r);
             }
             else if (wide)
             {
-                hipLaunchKernelGGL(cg_update2_kernel, dim3(grid2), dim3(kBlock), 0, st, n, kk, p, q, x, r, s);
-                hipLaunchKernelGGL(cg_direction2_kernel, dim3(grid2), dim3(kBlock), 0, st, n, kk, r, p, s);
+                SPMV_CG_UPDATE(Z::r, true, grid2);
+                SPMV_CG_DIRECTION(Z::r, true, grid2, r);
             }
             else
             {
-                hipLaunchKernelGGL(cg_update_kernel, dim3(grid), dim3(kBlock), 0, st, n, kk, p, q, x, r, s);
-                hipLaunchKernelGGL(cg_direction_kernel, dim3(grid), dim3(kBlock), 0, st, n, kk, r, p, s);
+                SPMV_CG_UPDATE(Z::r, false, grid);
+                SPMV_CG_DIRECTION(Z::r, false, grid, r);
             }
+#undef SPMV_CG_UPDATE
+#undef SPMV_CG_DIRECTION
             return SPMV_OK;
         };
         // Between two looks at the residual nothing depends on the host, and the scalar slots repeat with period 4, so

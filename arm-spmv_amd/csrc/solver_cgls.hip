@@ -28,11 +28,10 @@
 // (rounding noise of the recurrence; 0 ends the solve) passes quietly: x and r stay, s is formed again from them, p restarts at s.
 // delta <= 0 (or NaN) with gamma above that floor, or a NaN gamma, raises the status word and leaves x and r alone.
 //
-// Every dot product is DETERMINISTIC, by the ticket pattern of solver_multi.hip: a workgroup sums its lanes in a fixed order (xor
-// butterfly inside a wavefront, then the four wavefronts in order) and stores the result in a [workgroups] buffer; the workgroup
-// that takes the last ticket of the launch (one atomic counter, __threadfence on both sides, by the one thread that stores the
-// workgroup's sum and takes its ticket) adds the buffer up in buffer order and writes the scalar the next launch reads.  No atomic
-// adds in arrival order: a solve is exactly as reproducible as the two products its handle runs.
+// Every dot product is DETERMINISTIC, by the last-ticket pattern of solver_common.hpp (grid_totals): a workgroup sums its lanes in
+// a fixed order (xor butterfly inside a wavefront, then the four wavefronts in order) and stores the result in a [workgroups]
+// buffer; the workgroup that takes the last ticket of the launch adds the buffer up in buffer order and writes the scalar the next
+// launch reads.  No atomic adds in arrival order: a solve is exactly as reproducible as the two products its handle runs.
 //
 // Vector kernels: kBlock threads, grid-stride loops, 64-bit indices.  r, q, p, s are fresh 256-byte aligned allocations and go in
 // 16-byte accesses (two elements per lane, an odd last element by one extra lane); the caller's x (update) and b (init) go in
@@ -43,6 +42,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "solver_common.hpp"
 #include "wave.hpp"
 
 namespace spmv
@@ -62,69 +62,6 @@ struct CglsScalars
     int32_t  status;       // 1: delta <= 0 (or NaN) with gamma above the floor, 2: gamma is NaN
     uint32_t ticket;       // workgroups of the current launch that have stored their partial sums
 };
-
-inline int stream_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, ceil_div(n, kBlock))); }
-
-// sum over the workgroup in a fixed order (xor butterfly inside a wavefront, then the four wavefronts in order), in every thread
-__device__ __forceinline__ double block_sum_all(double v, double* s_part)
-{
-    v = wave_sum(v);
-    __syncthreads();  // the previous call's readers are done with s_part
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kBlock / kWave; ++w) t += s_part[w];
-    return t;
-}
-
-// true (in every thread) for the workgroup that stored its partial sums last: all the others' are visible to it.  Thread 0 alone
-// stores a workgroup's partial sums, so it alone fences: a fence by all 256 threads costs two to four times one lane's, in every
-// workgroup of every launch.  (What the launch writes into the vectors needs no fence: its readers are later launches.)
-__device__ __forceinline__ bool took_last_ticket(uint32_t* ticket)
-{
-    __shared__ uint32_t s_last;
-    __syncthreads();  // every thread of the workgroup has read the launch's scalars: the last workgroup may write them
-    if (threadIdx.x == 0)
-    {
-        __threadfence();  // this workgroup's partial sums before its ticket
-        const bool last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-        if (last) __threadfence();  // the ticket before the others' partial sums (which are read with atomic loads besides)
-        s_last = last ? 1u : 0u;
-    }
-    __syncthreads();
-    return s_last != 0;
-}
-
-// The launch's totals of NQ per-thread sums: part[q * gridDim.x + workgroup] takes the workgroups' sums, and the workgroup with
-// the last ticket adds each plane up - lane t the workgroups t, t + 256, ... in that order, then block_sum_all - and returns true
-// with the totals in every thread.  The order of the additions belongs to (n, grid), not to the workgroup that comes last.
-template <int NQ>
-__device__ __forceinline__ bool grid_totals(const double (&val)[NQ], double* __restrict__ part, uint32_t* ticket, double (&total)[NQ])
-{
-    __shared__ double s_part[kBlock / kWave];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-    {
-        const double t = block_sum_all(val[q], s_part);
-        if (threadIdx.x == 0) part[(int64_t)q * gridDim.x + blockIdx.x] = t;
-    }
-    if (!took_last_ticket(ticket)) return false;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-    {
-        double acc = 0.0;
-        for (int g = threadIdx.x; g < (int)gridDim.x; g += kBlock)
-        {
-            // an atomic load: straight from memory, whatever an earlier launch left in this CU's caches
-            const unsigned long long bits = __hip_atomic_load((const unsigned long long*)(part + (int64_t)q * gridDim.x + g),
-                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            acc += __longlong_as_double((long long)bits);
-        }
-        total[q] = block_sum_all(acc, s_part);
-    }
-    return true;
-}
 
 // r = b - q (q = A x0), b.b, r.r.  WIDE: b is 16-byte aligned (q and r always are)
 template <bool WIDE>
@@ -405,14 +342,7 @@ int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int
         return SPMV_OK;
     };
     CglsScalars h;
-    auto        fetch = [&]() -> int {
-        if (hipMemcpyAsync(&h, s, sizeof(CglsScalars), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        {
-            set_error("spmv_cgls: reading the iteration scalars failed: %s", hipGetErrorString(hipGetLastError()));
-            return SPMV_ERR_HIP;
-        }
-        return SPMV_OK;
-    };
+    auto        fetch = [&]() { return read_scalars(ctx, &h, s, sizeof(CglsScalars), "spmv_cgls"); };
     int rc = SPMV_OK;
     do
     {

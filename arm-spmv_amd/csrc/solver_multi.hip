@@ -19,10 +19,12 @@
 //
 // The dot products are DETERMINISTIC: no atomic adds in arrival order.  A workgroup reduces its lanes' sums per column in a fixed
 // order (an xor butterfly over the row groups of a wavefront, then the four wavefronts in order) and stores the result in a
-// [workgroups][k] buffer; the workgroup that takes the last ticket of the launch (one atomic counter, __threadfence on both sides)
-// adds the buffer up per column - again in an order fixed by (n, k) alone - and writes the column's scalars, which the next launch
-// reads.  Which workgroup comes last changes nothing: the order of the additions belongs to the buffer, not to the adder.  So two
-// calls give the same bits, and column c depends on column c of B and X alone at a given (n, k, c).
+// [workgroups][k] buffer; the workgroup that takes the last ticket of the launch (took_last_ticket, solver_common.hpp: the pattern
+// spmv_cgls runs too, with the one fencing thread per workgroup it needs) adds the buffer up per column - again in an order fixed
+// by (n, k) alone - and writes the column's scalars, which the next launch reads.  Which workgroup comes last changes nothing: the
+// order of the additions belongs to the buffer, not to the adder.  So two calls give the same bits, and column c depends on column
+// c of B and X alone at a given (n, k, c).  The buffer's layout, part[workgroup][column], and with it the order of the additions
+// are this file's own (column_sum, store_partials, column_total): grid_totals' part[quantity][workgroup] adds in another order.
 //
 // Per-column state on the device (CgmScalars): `frozen` is written by the host when a column has converged (or b_c = 0) - the
 // kernels then neither read nor write that column of X, R, U, P, S; a column whose r.r is at or below 1e-28 b.b passes quietly as
@@ -33,6 +35,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "solver_common.hpp"
 #include "wave.hpp"
 
 namespace spmv
@@ -57,14 +60,12 @@ struct CgmScalars
     uint32_t pad;
 };
 
-typedef double f64x2_t __attribute__((ext_vector_type(2)));
-
 template <int V>
 __device__ __forceinline__ void load_cols(const double* p, double (&v)[V])
 {
     if constexpr (V == 2)
     {
-        const f64x2_t t = *(const f64x2_t*)p;
+        const f64x2 t = *(const f64x2*)p;
         v[0]            = t[0];
         v[1]            = t[1];
     }
@@ -75,7 +76,7 @@ template <int V>
 __device__ __forceinline__ void store_cols(double* p, const double (&v)[V])
 {
     if constexpr (V == 2)
-        *(f64x2_t*)p = f64x2_t{v[0], v[1]};
+        *(f64x2*)p = f64x2{v[0], v[1]};
     else
         *p = v[0];
 }
@@ -108,19 +109,6 @@ __device__ __forceinline__ void store_partials(const double (&val)[V], int KP, i
     }
 }
 
-// true (in every thread) for the workgroup that stored its partial sums last: all the others' are visible to it
-__device__ __forceinline__ bool took_last_ticket(uint32_t* ticket)
-{
-    __shared__ uint32_t s_last;
-    __threadfence();  // this workgroup's partial sums before its ticket
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-    __syncthreads();
-    const bool last = s_last != 0;
-    if (last) __threadfence();  // the ticket before the others' partial sums
-    return last;
-}
-
 // column (threadIdx.x)'s total of part[0 .. gridDim.x)[c], for threads < KC (KC: the next power of two >= k): the 256 / KC
 // slices of workgroups g = slice, slice + slices, ... are added up by one lane each, then column_sum over the slices
 __device__ __forceinline__ double column_total(const double* part, int k, int kc_log2, double (*s_part)[kWave])
@@ -128,13 +116,7 @@ __device__ __forceinline__ double column_total(const double* part, int k, int kc
     const int KC = 1 << kc_log2, c = threadIdx.x & (KC - 1), slice = threadIdx.x >> kc_log2, slices = kBlock >> kc_log2;
     double    acc = 0.0;
     if (c < k)
-        for (int g = slice; g < (int)gridDim.x; g += slices)
-        {
-            // an atomic load: straight from memory, whatever an earlier launch left in this CU's caches
-            const unsigned long long bits = __hip_atomic_load((const unsigned long long*)(part + (int64_t)g * k + c), __ATOMIC_RELAXED,
-                                                              __HIP_MEMORY_SCOPE_AGENT);
-            acc += __longlong_as_double((long long)bits);
-        }
+        for (int g = slice; g < (int)gridDim.x; g += slices) acc += partial_sum_load(part + (int64_t)g * k + c);
     return column_sum(acc, KC, s_part);
 }
 
@@ -408,19 +390,13 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
     };
     if (pre)
     {
-        SPMV_TRY(ensure_scratch(ctx, 64));
-        int* flag   = (int*)ctx->scratch;
-        int  h_flag = 0;
         if (hipMalloc(&dinv, sizeof(double) * (size_t)n) != hipSuccess)
             SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg_multi: out of device memory for the diagonal (%lld entries)", (long long)n);
-        (void)hipMemsetAsync(flag, 0, sizeof(int), st);
-        const int rc_d = csr_inverse_diagonal(ctx, A, dinv, flag);
-        if (rc_d != SPMV_OK || hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess || h_flag != 0)
+        const int rc_d = jacobi_inverse_diagonal(ctx, A, dinv, "spmv_cg_multi");
+        if (rc_d != SPMV_OK)
         {
             release();
-            if (rc_d != SPMV_OK) return rc_d;
-            SPMV_FAIL(SPMV_ERR_INVALID, "spmv_cg_multi: the matrix has a zero or missing diagonal entry (Jacobi preconditioner)");
+            return rc_d;
         }
     }
     // R, P, S, W and (Jacobi) U: one allocation, every vector on a 256-byte boundary
@@ -438,14 +414,7 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
     CgmScalars           h;
     std::vector<int32_t> frozen(kCgmMaxK, 0);
     std::vector<double>  limit(k), rr(k);
-    auto fetch = [&]() -> int {
-        if (hipMemcpyAsync(&h, s, sizeof(CgmScalars), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        {
-            set_error("spmv_cg_multi: reading the iteration scalars failed: %s", hipGetErrorString(hipGetLastError()));
-            return SPMV_ERR_HIP;
-        }
-        return SPMV_OK;
-    };
+    auto fetch = [&]() { return read_scalars(ctx, &h, s, sizeof(CgmScalars), "spmv_cg_multi"); };
     auto freeze = [&]() -> int {  // the host's flags to the device, before the next iteration is queued
         if (hipMemcpyAsync(s->frozen, frozen.data(), sizeof(int32_t) * kCgmMaxK, hipMemcpyHostToDevice, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)

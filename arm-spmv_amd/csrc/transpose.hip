@@ -31,7 +31,6 @@ struct transpose_state
 
 namespace
 {
-typedef double f64x2_t __attribute__((ext_vector_type(2)));
 
 // ---- ELL: the row of every slot (slot s of row i sits at i + s * nrow) ---------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void ell_slot_rows_kernel(int nrow, int64_t total, int32_t* __restrict__ rows)
@@ -87,8 +86,8 @@ __global__ __launch_bounds__(kBlock) void dia_transpose_kernel(int nrow, int jma
             const bool    in = r < rows && i >= 0 && i < nrow && d0 + d_mine < ndiags;
             if constexpr (WIDE)
             {
-                f64x2_t v = {0.0, 0.0};
-                if (in) v = __builtin_nontemporal_load((const f64x2_t*)(val + (size_t)i * ndiags + d0 + d_mine));
+                f64x2 v = {0.0, 0.0};
+                if (in) v = __builtin_nontemporal_load((const f64x2*)(val + (size_t)i * ndiags + d0 + d_mine));
                 stage[2 * p]     = v[0];
                 stage[2 * p + 1] = v[1];
             }

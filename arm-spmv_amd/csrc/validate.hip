@@ -29,7 +29,6 @@ __global__ __launch_bounds__(kBlock) void check_offsets_kernel(const int32_t* __
     if (blockIdx.x == 0 && threadIdx.x == 0 && (ptr[0] != 0 || ptr[n] != nnz)) atomicOr(flags, 4);
 }
 
-inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, ceil_div(n, kBlock))); }
 }  // namespace
 
 int mat_validate(const spmv_mat* m)
@@ -52,24 +51,24 @@ int mat_validate(const spmv_mat* m)
     switch (m->format)
     {
         case SPMV_FMT_CSR:
-            hipLaunchKernelGGL(check_offsets_kernel, dim3(grid_for(m->nrow)), dim3(kBlock), 0, s, m->a, (int64_t)m->nrow, nnz, flags);
-            if (nnz) hipLaunchKernelGGL(check_range_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, s, m->b, nnz, m->ncol, flags);
+            hipLaunchKernelGGL(check_offsets_kernel, dim3(stream_grid(m->nrow)), dim3(kBlock), 0, s, m->a, (int64_t)m->nrow, nnz, flags);
+            if (nnz) hipLaunchKernelGGL(check_range_kernel, dim3(stream_grid(nnz)), dim3(kBlock), 0, s, m->b, nnz, m->ncol, flags);
             break;
         case SPMV_FMT_CSC:
-            hipLaunchKernelGGL(check_offsets_kernel, dim3(grid_for(m->ncol)), dim3(kBlock), 0, s, m->a, (int64_t)m->ncol, nnz, flags);
-            if (nnz) hipLaunchKernelGGL(check_range_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, s, m->b, nnz, m->nrow, flags);
+            hipLaunchKernelGGL(check_offsets_kernel, dim3(stream_grid(m->ncol)), dim3(kBlock), 0, s, m->a, (int64_t)m->ncol, nnz, flags);
+            if (nnz) hipLaunchKernelGGL(check_range_kernel, dim3(stream_grid(nnz)), dim3(kBlock), 0, s, m->b, nnz, m->nrow, flags);
             break;
         case SPMV_FMT_COO:
             if (nnz)
             {
-                hipLaunchKernelGGL(check_range_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, s, m->a, nnz, m->nrow, flags);
-                hipLaunchKernelGGL(check_range_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, s, m->b, nnz, m->ncol, flags);
+                hipLaunchKernelGGL(check_range_kernel, dim3(stream_grid(nnz)), dim3(kBlock), 0, s, m->a, nnz, m->nrow, flags);
+                hipLaunchKernelGGL(check_range_kernel, dim3(stream_grid(nnz)), dim3(kBlock), 0, s, m->b, nnz, m->ncol, flags);
             }
             break;
         case SPMV_FMT_ELL:
         {
             const int64_t total = (int64_t)m->nrow * m->k;
-            if (total) hipLaunchKernelGGL(check_range_kernel, dim3(grid_for(total)), dim3(kBlock), 0, s, m->b, total, m->ncol, flags);
+            if (total) hipLaunchKernelGGL(check_range_kernel, dim3(stream_grid(total)), dim3(kBlock), 0, s, m->b, total, m->ncol, flags);
             break;
         }
         case SPMV_FMT_DIA: break;  // the product bounds every column by min(nrow, ncol) itself (kernels_misc.hip)
