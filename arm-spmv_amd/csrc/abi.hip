@@ -99,10 +99,7 @@ void mat_free(spmv_mat* m)
     }
     if (m->win_lo) (void)hipFree(m->win_lo);
     if (m->win_span) (void)hipFree(m->win_span);
-    if (m->ell_diag) (void)hipFree(m->ell_diag);
-    if (m->ell_diag_mask) (void)hipFree(m->ell_diag_mask);
-    ell_free_tiles(m);
-    ell_free_dia_order(m);
+    ell_layouts_free(m);
     csr_layouts_free(m, kCsrAllLayouts);
     symgs_free(m);
     if (m->rowgrouped) mat_free(m->rowgrouped);
@@ -723,6 +720,7 @@ int spmv_mat_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes_per_row)
 int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
 {
     SPMV_REQUIRE(m && name, "null argument");
+    if (int rc = SPMV_OK; ell_set_param(m, name, value, &rc)) return rc;  // "ell_tiled_values", "ell_dia_order"
     if (!strcmp(name, "panel_rows"))
         m->pb_group_rows = (int32_t)value;
     else if (!strcmp(name, "panel_width"))
@@ -778,35 +776,6 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
             m->v = nullptr;
             m->device_bytes -= m->nnz * 12;
         }
-    }
-    else if (!strcmp(name, "ell_tiled_values"))
-    {
-        // ELL whose slots are diagonals: 1 = keep a copy of the values in tiles of 512 rows for the product (never made unasked:
-        // 8 bytes per slot for 1-7 %), 0 = drop it and multiply from the column-major array
-        SPMV_REQUIRE(m->format == SPMV_FMT_ELL && (value == 0 || value == 1), "ell_tiled_values: an ELL handle and 0 or 1");
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        SPMV_HIP(hipStreamSynchronize(m->ctx->stream));
-        if (value == 0)
-            ell_free_tiles(m);
-        else
-            SPMV_TRY(ell_build_tiles(m, /*only_if_worth=*/false));
-    }
-    else if (!strcmp(name, "ell_dia_order"))
-    {
-        // ELL whose slots are diagonals: 1 = keep the values once more in DIA order (row-major) and multiply with the DIA kernel,
-        // now; 0 = drop the copy and never build it; -1 = a candidate of AUTO's trial (the default).  8 bytes per slot.
-        SPMV_REQUIRE(m->format == SPMV_FMT_ELL && value >= -1 && value <= 1, "ell_dia_order: an ELL handle and -1, 0 or 1");
-        SPMV_HIP(hipSetDevice(m->ctx->device));
-        SPMV_HIP(hipStreamSynchronize(m->ctx->stream));
-        m->ell_dia_order_req = (int32_t)value;
-        if (value == 1)
-        {
-            SPMV_TRY(ell_build_dia_order(m, /*only_if_worth=*/false));
-            if (runs_from_rowgrouped(m)) m->kernel = SPMV_CSR_VECTOR;  // (the format's own kernel runs: this variant of it)
-            m->ell_variant = 3;
-        }
-        else
-            ell_free_dia_order(m);
     }
     else if (!strcmp(name, "coo_column_bins"))
     {
@@ -932,12 +901,6 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         *value = (m->b && m->v) || m->nnz == 0 ? 1 : 0;
     else if (!strcmp(name, "device_bytes"))
         *value = m->device_bytes;
-    else if (!strcmp(name, "ell_tiled_values"))  // ELL: 1 if the product reads the values from the copy in tiles of 512 rows
-        *value = m->ell_tval ? 1 : 0;
-    else if (!strcmp(name, "ell_dia_order"))  // ELL: 1 if the product runs the DIA kernel over the DIA-order copy of the values
-        *value = m->ell_variant == 3 && m->ell_rval ? 1 : 0;
-    else if (!strcmp(name, "ell_non_conforming_rows"))  // ... and the rows the side kernel does
-        *value = m->ell_rval ? m->ell_nc_count : 0;
     else if (!strcmp(name, "coo_column_bins"))  // bins of the copy the segmented scan runs over (8 x bins per XCD), 0: none
         *value = m->cb_bins;
     else if (!strcmp(name, "coo_bins_padded"))
@@ -961,8 +924,6 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         *value = (m->pb_sync >= 0 ? m->pb_sync : m->pb_sync_tuned) == 2 ? 3 : (m->pb_sync >= 0 ? m->pb_sync : m->pb_sync_tuned);  // (2, the split barrier, runs 3 since round 5)
     else if (!strcmp(name, "panel_layout"))  // layout in memory: 0 three arrays, 1 records, 3 packed 12-byte entries
         *value = m->pb_pack ? (m->pb_pair ? 4 : 3) : 0;
-    else if (!strcmp(name, "ell_diagonal_slots"))  // ELL: 1 if the slots were found to be diagonals (no column stream for conforming rows)
-        *value = m->ell_diag ? 1 : 0;
     else if (!strcmp(name, "twophase_panel_cols"))
         *value = m->tp_pcols;
     else if (!strcmp(name, "twophase_pieces_carved"))  // pieces of the product stream that lie inside the released CSR copy's allocations
@@ -988,26 +949,8 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         *value = (int64_t)m->win_avg_span;
     else if (!strcmp(name, "contiguous_permille"))
         *value = (int64_t)(m->contig_frac * 1000.0 + 0.5);
-    else if (!strcmp(name, "select_candidates"))
-        *value = m->sel_candidates;
-    else if (!strcmp(name, "select_rounds"))  // rounds the handle's last trial went through until its candidates' minima stood still (2 .. 6; 0: no trial)
-        *value = m->sel_rounds;
-    else if (!strncmp(name, "select_us_", 10))
-    {
-        int slot = -1;
-        for (int i = SPMV_CSR_VECTOR; i <= SPMV_CSR_ELL; ++i)  // the slot of a CSR kernel is its id
-            if (!strcmp(name + 10, csr_kernel_name(i))) slot = i;
-        if (!strcmp(name + 10, "variant1")) slot = 6;  // ELL / COO handles: the slots that are "segscan" / "split" on a CSR handle
-        if (!strcmp(name + 10, "variant2")) slot = 7;
-        if (!strcmp(name + 10, "split_low")) slot = 0;  // kernel SPLIT with rows of 256 entries and more split off (timed from 8M entries on)
-        if (!strcmp(name + 10, "dia_order")) slot = 9;  // ELL handles: the DIA-order copy of the values
-        SPMV_REQUIRE(slot >= 0, "unknown parameter '%s'", name);
-        *value = (int64_t)(m->sel_us[slot] + 0.5f);
-    }
     else if (!strcmp(name, "rowgrouped_kernel"))
         *value = runs_from_rowgrouped(m) ? m->rowgrouped->kernel : 0;
-    else if (!strcmp(name, "ell_variant"))
-        *value = m->ell_variant;
     else if (!strcmp(name, "panel_rounds"))
         *value = m->pb_built_rounds;
     else if (!strcmp(name, "panel_rounds_us_one"))
@@ -1026,19 +969,13 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         *value = m->split_long ? m->split_long->kernel : 0;
     else if (!strcmp(name, "split_long_entries"))
         *value = m->split_long_nnz;
-    else if (!strcmp(name, "ell_copy_slots"))
-        *value = m->ell_copy ? (int64_t)m->ell_copy->nrow * m->ell_copy->k : 0;
-    else if (!strcmp(name, "ell_copy_diagonal_slots"))
-        *value = m->ell_copy && m->ell_copy->ell_diag ? 1 : 0;
-    else if (!strcmp(name, "ell_copy_variant"))
-        *value = m->ell_copy ? m->ell_copy->ell_variant : 0;
     else if (!strcmp(name, "min_row_entries"))
         *value = m->min_row_nnz;
     else if (!strcmp(name, "adds_into_y_with_atomics"))  // 1: the product adds into y with device atomics (spmv_apply_host stages y in device memory)
         *value = adds_into_y_with_atomics(m) ? 1 : 0;
     else if (!strcmp(name, "split_inner_kernel"))
         *value = m->format == SPMV_FMT_CSR && m->kernel == SPMV_CSR_SPLIT && m->split_short ? m->split_short->kernel : 0;
-    else
+    else if (!ell_get_param(m, name, value) && !select_get_param(m, name, value))  // "ell_*", "ell_copy_*"; "select_candidates", "select_rounds", "select_us_<name>"
         SPMV_FAIL(SPMV_ERR_INVALID, "unknown parameter '%s'", name);
     return SPMV_OK;
 }

@@ -12,6 +12,7 @@
 #include <functional>
 #include <vector>
 
+#include "ell_settings.hpp"
 #include "spmv_abi.h"
 
 namespace spmv
@@ -212,9 +213,9 @@ struct spmv_mat
     double   contig_frac  = 0.0;   // CSR: fraction of the entries whose column is the previous entry's + 1 (dense blocks, bands)
 
     // AUTO selection by measurement (select.hip): candidates timed when the handle was analysed, microseconds per product
-    // by spmv_csr_kernel id (COO / ELL: [1] the format's own kernel, [4] the row-grouped copy); 0 = not timed
+    // by slot (spmv::select_slot below); 0 = not timed
     int32_t  sel_candidates = 0;
-    float    sel_us[10]     = {0};
+    float    sel_us[10]     = {0};  // [spmv::kSelSlots]
     int32_t  sel_rounds     = 0;  // rounds the last trial went through until its minima stood still ("select_rounds")
 
     // CSR panel kernel (kernels_csr_panel.hip): entries re-ordered per row group by column panel / x line
@@ -315,8 +316,7 @@ struct spmv_mat
     int32_t* ell_diag      = nullptr;
     void*    ell_diag_mask = nullptr;
     int32_t  ell_diag_lds = 0;  // doubles of LDS the x stretches of a block take (0: none, x from global memory)
-    int32_t  ell_variant  = 0;  // which of the format's own kernels AUTO timed fastest: 0 two rows per lane (diagonal slots where found),
-                                // 1 one row per lane, 2 two rows per lane reading every column index
+    int32_t  ell_variant  = 0;  // which of the format's own kernels runs (ell_settings.hpp: ell_variant_id; written by ell_use_variant and AUTO's trial)
     double*  ell_tval = nullptr;  // the values in tiles of 512 rows, (tile * k + slot) * 512 + row (ell_build_tiles); owned
     // ELL whose slots are diagonals, DIA-ORDER copy (kernels_ell.hip: ell_build_dia_order; ell_variant 3): the values once more
     // ROW-major, row * k + slot, multiplied by the DIA kernel (a workgroup streams one contiguous stretch and x goes through an
@@ -375,7 +375,6 @@ int  csr_layout_build(spmv_mat* m, int32_t kernel);       // (re)builds `kernel`
 void csr_layouts_free(spmv_mat* m, uint32_t kernels);     // frees those of the kernels whose bit 1u << id is set
 bool csr_layout_built(const spmv_mat* m, int32_t kernel);  // kernel_reads_own_layout(kernel) and that layout is in memory
 constexpr uint32_t kCsrAllLayouts = ~0u;
-const char* csr_kernel_name(int32_t kernel);  // "vector" .. "ell" for VECTOR .. ELL ("select_us_<kernel>")
 void csr_choose_kernel(spmv_mat* m);  // the model's pick (no launches)
 int  csr_ldswin_capacity();           // columns of x the LDS-window kernel's tile holds
 // select.hip: AUTO by measurement
@@ -397,6 +396,19 @@ struct select_scratch
 int  select_rounds(spmv_ctx* ctx, int n, const std::function<int(int)>& launch, float* t, int* rounds_run);
 // ms per product of `launch`: 1 warm-up + 1 product, and 2 x 4 more (the minimum) unless that one was 3x behind best_so_far
 int  select_time(spmv_ctx* ctx, const std::function<int()>& launch, float best_so_far, float* ms);
+// The slots of spmv_mat::sel_us, microseconds per product of a candidate a trial timed ("select_us_<name>").  A CSR kernel's slot
+// is its id, 1 (SPMV_CSR_VECTOR) .. 8 (SPMV_CSR_ELL); on a COO, CSC or ELL handle 1 is the format's own kernel and 4
+// (SPMV_CSR_PANEL) the row-grouped copy.  The others:
+enum select_slot : int
+{
+    kSelSplitLow = 0,  // "split_low": CSR, kernel SPLIT with rows of 256 entries and more split off (timed from 8M entries on)
+    kSelVariant1 = 6,  // "variant1": ELL one row per lane; COO the scan over column bins (a CSR handle's "segscan")
+    kSelVariant2 = 7,  // "variant2": ELL two rows per lane reading every column (a CSR handle's "split")
+    kSelDiaOrder = 9,  // "dia_order": ELL, the DIA-order copy of the values
+    kSelSlots    = 10
+};
+static_assert(sizeof(spmv_mat::sel_us) / sizeof(float) == kSelSlots, "sel_us holds one figure per slot");
+bool select_get_param(const spmv_mat* m, const char* name, int64_t* value);  // "select_*" through the one table from name to slot; false: not one of them
 void select_note(spmv_mat* m, int slot, float ms);  // records a timed candidate (sel_us[slot], sel_candidates)
 void select_reset(spmv_mat* m);
 constexpr int64_t kSelectMinNnz = (int64_t)64 << 10;  // below: every kernel takes a launch latency, nothing to choose
@@ -448,19 +460,22 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
 // solver_cgls.hip: CGLS for min ||b - A x||^2 + damp^2 ||x||^2 over the forward and the transposed product of any handle
 int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                double damp, int* iters, double* rel_normal_resid, double* rel_resid);
-// kernels_ell.hip
+// kernels_ell.hip (what a product launches: ell_settings.hpp)
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int ell_analyse(spmv_mat* m);
+int  ell_use_variant(spmv_mat* m, int variant, bool keep_requested_copy);  // switches the format's own kernel; builds / drops the DIA-order copy
+int  ell_use_tiles(spmv_mat* m, bool on);  // builds / drops the copy of the values in tiles of 512 rows
+int  ell_build_dia_order(spmv_mat* m, bool only_if_worth);  // the DIA-order copy of the values (ell_variant 3)
+void ell_free_dia_order(spmv_mat* m);
+void ell_layouts_free(spmv_mat* m);  // slot descriptors, mask, tiles, DIA-order copy
+bool ell_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "ell_*"; false: not one of them
+bool ell_get_param(const spmv_mat* m, const char* name, int64_t* value);    // "ell_*", "ell_copy_*"; false: not one of them
 int ell_select_kernel(spmv_mat* m);                    // AUTO: the format's own variants and (where a candidate) the row-grouped copy, timed
 int ell_rowgrouped_copy(spmv_mat* m, int32_t force_kernel, spmv_mat** out);  // the row-grouped copy's CSR handle (rowgrouped_build)
 int  csr_ell_copy_build(spmv_mat* m);  // SPMV_CSR_ELL: the ELL copy of a CSR handle with (nearly) equal rows
 void csr_ell_copy_free(spmv_mat* m);
 bool csr_ell_copy_worth(const spmv_mat* m);
 // kernels_coo.hip
-int  ell_build_tiles(spmv_mat* m, bool only_if_worth);
-void ell_free_tiles(spmv_mat* m);
-int  ell_build_dia_order(spmv_mat* m, bool only_if_worth);  // the DIA-order copy of the values (ell_variant 3)
-void ell_free_dia_order(spmv_mat* m);
 int coo_analyse(spmv_mat* m);
 int coo_select_kernel(spmv_mat* m);                    // AUTO: the segmented scan or the row-grouped copy (which picks its own kernel), timed
 int  coo_build_bins(spmv_mat* m, int bins_per_xcd, bool only_if_worth);  // bins_per_xcd 0: as many as keep a slice of x inside an XCD's L2

@@ -347,11 +347,11 @@ int coo_trial(spmv_mat* m, const select_scratch& sv, bool model_copy, float* t_c
             if (rc == SPMV_OK)
             {
                 t_bins = t[0] >= 0.f ? t[0] : 1e30f;
-                if (t[0] >= 0.f) select_note(m, 6, t_bins);  // "select_us_variant1"
+                if (t[0] >= 0.f) select_note(m, kSelVariant1, t_bins);
                 if (m->rowgrouped && t[1] >= 0.f)
                 {
                     t_copy                    = t[1];
-                    m->sel_us[SPMV_CSR_PANEL] = t_copy * 1000.f;
+                    m->sel_us[SPMV_CSR_PANEL] = t_copy * 1000.f;  // (not select_note: the copy was counted as a candidate above; this improves its figure)
                 }
             }
         }

@@ -446,13 +446,6 @@ int csr_analyse(spmv_mat* m)
 }
 
 // ---- the layouts of their own that CSR kernels multiply from ---------------------------------------------------------------
-const char* csr_kernel_name(int32_t kernel)
-{
-    // (inside a host function: a constant array at namespace scope of a .hip file is emitted into the device code object too)
-    static const char* const kNames[SPMV_CSR_ELL + 1] = {"", "vector", "ldswin", "scalar", "panel", "twophase", "segscan", "split", "ell"};
-    return kNames[kernel];
-}
-
 int csr_layout_build(spmv_mat* m, int32_t kernel)
 {
     switch (kernel)

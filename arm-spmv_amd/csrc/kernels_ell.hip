@@ -12,8 +12,8 @@
 //
 // Roofline: HBM-bound; algorithmic bytes per application = 12*nrow*K + 8*ncol + 16*nrow.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
-
 
 #include "common.hpp"
 #include "wave.hpp"
@@ -478,7 +478,7 @@ int ell_select_kernel(spmv_mat* m)
     select_reset(m);
     rowgrouped_drop(m);
     m->kernel      = SPMV_CSR_VECTOR;
-    m->ell_variant = 0;
+    m->ell_variant = kEllTwoRows;
     const int64_t slots = (int64_t)m->nrow * m->k;
     if (slots == 0 || m->nrow <= 0) return SPMV_OK;
     select_scratch sv;
@@ -516,44 +516,45 @@ int ell_select_kernel(spmv_mat* m)
         }
         if (rc != SPMV_OK) return rc;
     }
-    // candidates 0 .. 2: the format's own variants; 3: the copy.  Timed in rounds until their minima stand still (select.hip:
-    // this is what replaced round 5's 2 ms of sleep in front of small handles' trials)
+    // the candidates: the format's own variants first, the row-grouped copy last.  Timed in rounds until their minima stand still
+    // (select.hip: this is what replaced round 5's 2 ms of sleep in front of small handles' trials)
     const bool has_v2 = m->ell_diag && m->ell_diag_mask;  // (without diagonal slots variant 0 reads the indices already)
     // the DIA-order copy of the values (variant 3), where the slots are diagonals and it is not forbidden ("ell_dia_order" 0)
     if (m->ell_dia_order_req != 0) SPMV_TRY(ell_build_dia_order(m, /*only_if_worth=*/m->ell_dia_order_req < 0));
-    int        ids[5], n = 0;  // 0, 1, 2: the format's own variants; 4: the DIA-order copy (variant 3); 3: the row-grouped copy, last
-    ids[n++] = 0;
-    ids[n++] = 1;
-    if (has_v2) ids[n++] = 2;
-    if (m->ell_rval) ids[n++] = 4;
-    if (m->rowgrouped) ids[n++] = 3;
-    float t[5] = {-1.f, -1.f, -1.f, -1.f, -1.f};
+    struct { bool copy; int variant; } cand[kEllVariants + 1];  // the row-grouped copy, else this variant of the format's own kernel
+    int n = 0;
+    cand[n++] = {false, kEllTwoRows};
+    cand[n++] = {false, kEllOneRow};
+    if (has_v2) cand[n++] = {false, kEllReadColumns};
+    if (m->ell_rval) cand[n++] = {false, kEllDiaOrder};
+    if (m->rowgrouped) cand[n++] = {true, 0};
+    float t[kEllVariants + 1] = {-1.f, -1.f, -1.f, -1.f, -1.f};
     rc = select_rounds(ctx, n,
                        [&](int j) {
-                           if (ids[j] == 3) return csr_apply(ctx, m->rowgrouped, sv.x, sv.y);
-                           m->ell_variant = ids[j] == 4 ? 3 : ids[j];
+                           if (cand[j].copy) return csr_apply(ctx, m->rowgrouped, sv.x, sv.y);
+                           m->ell_variant = cand[j].variant;
                            return ell_own_apply(ctx, m, sv.x, sv.y);
                        },
                        t, &m->sel_rounds);
     (void)hipStreamSynchronize(ctx->stream);
     if (rc != SPMV_OK) return rc;
-    float best_ms = 1e30f;
-    int   best_v  = 0;
+    const int kVariantSlot[kEllVariants] = {SPMV_CSR_VECTOR, kSelVariant1, kSelVariant2, kSelDiaOrder};  // "select_us_vector", "_variant1", ...
+    float     best_ms = 1e30f;
+    int       best_v  = kEllTwoRows;
     for (int j = 0; j < n; ++j)
     {
-        if (ids[j] == 3 || t[j] < 0.f) continue;
-        const int v = ids[j] == 4 ? 3 : ids[j];
-        select_note(m, v == 0 ? SPMV_CSR_VECTOR : (v == 3 ? 9 : 5 + v), t[j]);  // slots 1, 6 ("variant1"), 7 ("variant2"), 9 ("dia_order")
+        if (cand[j].copy || t[j] < 0.f) continue;
+        const int v = cand[j].variant;
+        select_note(m, kVariantSlot[v], t[j]);
         // two rows per lane is the model's pick: another variant has to win by 2 % - the DIA-order copy, which costs 8 bytes per
         // slot of memory, by 5 %
-        if (t[j] < best_ms * (v == 3 ? 0.95f : (v ? 0.98f : 1.0f)))
+        if (t[j] < best_ms * (v == kEllDiaOrder ? 0.95f : (v != kEllTwoRows ? 0.98f : 1.0f)))
         {
             best_ms = t[j];
             best_v  = v;
         }
     }
-    m->ell_variant = best_v;
-    if (best_v != 3 && m->ell_dia_order_req < 0) ell_free_dia_order(m);  // (a copy that was asked for stays, used or not)
+    SPMV_TRY(ell_use_variant(m, best_v, /*keep_requested_copy=*/true));  // (a copy that was asked for stays, used or not)
     if (m->rowgrouped)
     {
         const float t_copy = t[n - 1];
@@ -727,32 +728,25 @@ __global__ __launch_bounds__(kBlock) void ell_tile_values_kernel(int nrow, int k
 }
 }  // namespace
 
-void ell_free_tiles(spmv_mat* m)
-{
-    if (!m->ell_tval) return;
-    (void)hipFree(m->ell_tval);
-    m->ell_tval = nullptr;
-    m->device_bytes -= (int64_t)ceil_div(m->nrow, kEllTileRows) * kEllTileRows * m->k * (int64_t)sizeof(double);
-}
+// bytes of the tiled copy of the values: whole tiles of 512 rows, the last one padded
+static int64_t ell_tiles_bytes(const spmv_mat* m) { return (int64_t)ceil_div(m->nrow, kEllTileRows) * kEllTileRows * m->k * (int64_t)sizeof(double); }
 
 // The values once more, in tiles of 512 rows, for the product over slots that are diagonals (the kernel's TILED form).  Costs
 // 8 bytes per slot of device memory for 1-7 % of C3's time (see the kernel), so it is made only when asked for
 // ("ell_tiled_values" = 1).
-int ell_build_tiles(spmv_mat* m, bool only_if_worth)
+static int ell_build_tiles(spmv_mat* m)
 {
     if (m->ell_tval || !m->ell_diag || m->nrow % 2 != 0) return SPMV_OK;
     const int64_t slots = (int64_t)m->nrow * m->k;
-    if (only_if_worth && slots < ((int64_t)1 << 20)) return SPMV_OK;  // (a few megabytes: the strides do not matter)
-    spmv_ctx*     ctx    = m->ctx;
-    const int64_t padded = (int64_t)ceil_div(m->nrow, kEllTileRows) * kEllTileRows * m->k;
-    double*       t      = nullptr;
-    if (hipMalloc(&t, sizeof(double) * (size_t)padded) != hipSuccess)
+    spmv_ctx*     ctx   = m->ctx;
+    const int64_t bytes = ell_tiles_bytes(m);
+    double*       t     = nullptr;
+    if (hipMalloc(&t, (size_t)bytes) != hipSuccess)
     {
         (void)hipGetLastError();
-        if (only_if_worth) return SPMV_OK;
-        SPMV_FAIL(SPMV_ERR_ALLOC, "out of device memory for the tiled copy of the values of an ELL handle (%lld bytes)", (long long)(padded * 8));
+        SPMV_FAIL(SPMV_ERR_ALLOC, "out of device memory for the tiled copy of the values of an ELL handle (%lld bytes)", (long long)bytes);
     }
-    hipError_t e = hipMemsetAsync(t, 0, sizeof(double) * (size_t)padded, ctx->stream);
+    hipError_t e = hipMemsetAsync(t, 0, (size_t)bytes, ctx->stream);
     hipLaunchKernelGGL(ell_tile_values_kernel, dim3((unsigned)std::min<int64_t>(kMaxGrid, ceil_div(slots, kBlock))), dim3(kBlock), 0, ctx->stream, m->nrow, m->k,
                        m->v, t);
     if (e == hipSuccess) e = hipGetLastError();
@@ -763,7 +757,19 @@ int ell_build_tiles(spmv_mat* m, bool only_if_worth)
         SPMV_FAIL(SPMV_ERR_HIP, "tiling the values of an ELL handle failed: %s", hipGetErrorString(e));
     }
     m->ell_tval = t;
-    m->device_bytes += padded * (int64_t)sizeof(double);
+    m->device_bytes += bytes;
+    return SPMV_OK;
+}
+
+// builds (on; a no-op without diagonal slots) or drops the tiled copy of the values; a drop waits for the stream first
+int ell_use_tiles(spmv_mat* m, bool on)
+{
+    if (on) return ell_build_tiles(m);
+    if (!m->ell_tval) return SPMV_OK;
+    (void)hipStreamSynchronize(m->ctx->stream);
+    (void)hipFree(m->ell_tval);
+    m->ell_tval = nullptr;
+    m->device_bytes -= ell_tiles_bytes(m);
     return SPMV_OK;
 }
 
@@ -849,18 +855,21 @@ __global__ __launch_bounds__(kBlock) void ell_rows_list_kernel(int nlist, const 
 }
 }  // namespace
 
+// bytes of the DIA-order copy: the values row-major at an even stride, a bit per row, the side kernel's rows (never an empty array)
+static int64_t ell_dia_order_bytes(const spmv_mat* m, int64_t nc_rows) { return 8 * (int64_t)m->nrow * (m->k + (m->k & 1)) + 8 * (((int64_t)m->nrow + 63) / 64) + 4 * std::max<int64_t>(nc_rows, 1); }
+
 void ell_free_dia_order(spmv_mat* m)
 {
     if (m->format != SPMV_FMT_ELL || !m->ell_rval) return;
+    (void)hipStreamSynchronize(m->ctx->stream);  // (a product may still read the copy)
     (void)hipFree(m->ell_rval);
     if (m->ell_skip) (void)hipFree(m->ell_skip);
     if (m->ell_nc_rows) (void)hipFree(m->ell_nc_rows);
-    m->device_bytes -= (int64_t)sizeof(double) * m->nrow * (m->k + (m->k & 1)) + (int64_t)sizeof(u64) * ((m->nrow + 63) / 64) + (int64_t)sizeof(int32_t) * std::max(m->ell_nc_count, 1);
+    m->device_bytes -= ell_dia_order_bytes(m, m->ell_nc_count);
     m->ell_rval     = nullptr;
     m->ell_skip     = nullptr;
     m->ell_nc_rows  = nullptr;
     m->ell_nc_count = 0;
-    if (m->ell_variant == 3) m->ell_variant = 0;
 }
 
 // only_if_worth: the trial's gate - diagonal slots found, a million slots and more (below, a product is launch latency),
@@ -913,7 +922,7 @@ int ell_build_dia_order(spmv_mat* m, bool only_if_worth)
         m->ell_nc_count = (int32_t)nc.size();
         m->ell_off_min  = *std::min_element(h_off.begin(), h_off.end());
         m->ell_off_max  = *std::max_element(h_off.begin(), h_off.end());
-        m->device_bytes += (int64_t)sizeof(double) * nrow * kp + (int64_t)sizeof(u64) * (int64_t)words + (int64_t)sizeof(int32_t) * std::max(m->ell_nc_count, 1);
+        m->device_bytes += ell_dia_order_bytes(m, m->ell_nc_count);
         return SPMV_OK;
     } while (0);
     if (rval) (void)hipFree(rval);
@@ -924,6 +933,28 @@ int ell_build_dia_order(spmv_mat* m, bool only_if_worth)
     if (only_if_worth && rc == SPMV_ERR_ALLOC) return SPMV_OK;  // no room: not a candidate
     if (rc == SPMV_ERR_ALLOC) SPMV_FAIL(rc, "out of device memory for the DIA-order copy of an ELL handle (%lld bytes)", (long long)(slots * 8));
     SPMV_FAIL(rc, "building the DIA-order copy of an ELL handle failed");
+}
+
+// Makes `variant` the one the format's own kernel runs: the only writer of ell_variant besides the trial's timing launches.  Variant
+// 3 gets its DIA-order copy built (a failure is returned and the variant stays); another variant drops a copy that is left, the
+// stream drained first - unless keep_requested_copy and "ell_dia_order" is 0 / 1, not the trial's -1 (AUTO's pick, set_kernel).
+int ell_use_variant(spmv_mat* m, int variant, bool keep_requested_copy)
+{
+    if (variant == kEllDiaOrder)
+        SPMV_TRY(ell_build_dia_order(m, /*only_if_worth=*/false));
+    else if (!(keep_requested_copy && m->ell_dia_order_req >= 0))
+        ell_free_dia_order(m);  // (8 bytes per slot nobody multiplies from now; waits for the stream first)
+    m->ell_variant = variant;
+    return SPMV_OK;
+}
+
+// every copy and descriptor an ELL handle owns besides its arrays (mat_free; the handle is going: device_bytes is not kept)
+void ell_layouts_free(spmv_mat* m)
+{
+    if (m->ell_diag) (void)hipFree(m->ell_diag);
+    if (m->ell_diag_mask) (void)hipFree(m->ell_diag_mask);
+    (void)ell_use_tiles(m, false);
+    ell_free_dia_order(m);
 }
 
 int ell_analyse(spmv_mat* m)
@@ -945,17 +976,7 @@ int ell_apply_plan(spmv_mat* m)
     select_reset(m);
     rowgrouped_drop(m);
     m->kernel        = SPMV_CSR_VECTOR;
-    m->ell_variant   = p.ell_variant >= 0 && p.ell_variant <= 3 ? p.ell_variant : 0;
-    if (m->ell_variant == 3)
-    {
-        SPMV_TRY(ell_build_dia_order(m, /*only_if_worth=*/false));  // (refused where the slots are no diagonals: the plan does not fit)
-        m->ell_variant = 3;
-    }
-    else
-    {
-        (void)hipStreamSynchronize(m->ctx->stream);
-        ell_free_dia_order(m);
-    }
+    SPMV_TRY(ell_use_variant(m, p.ell_variant >= 0 && p.ell_variant < kEllVariants ? p.ell_variant : kEllTwoRows, /*keep_requested_copy=*/false));  // (refused: the plan does not fit)
     m->lanes_per_row = p.lanes_per_row;
     m->flags         = p.flags;
     if ((int64_t)m->nrow * m->k == 0) return SPMV_OK;
@@ -966,112 +987,111 @@ int ell_apply_plan(spmv_mat* m)
         SPMV_TRY(rowgrouped_build(m, SPMV_CSR_AUTO));  // (hands the copy's node down)
         m->kernel = m->rowgrouped ? SPMV_CSR_PANEL : SPMV_CSR_VECTOR;
     }
-    if (p.ell_tiled)
-        SPMV_TRY(ell_build_tiles(m, /*only_if_worth=*/false));
-    else
-    {
-        (void)hipStreamSynchronize(m->ctx->stream);
-        ell_free_tiles(m);
-    }
-    return SPMV_OK;
+    return ell_use_tiles(m, p.ell_tiled != 0);
 }
 
-int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
+// ---- the parameters of ELL handles and of a CSR handle's ELL copy (spmv_mat_set_param / spmv_mat_get_param) ---------------------
+// false: not one of ELL's names; true: *rc says how it went
+bool ell_set_param(spmv_mat* m, const char* name, int64_t value, int* rc)
 {
-    if (A->nrow == 0) return SPMV_OK;
-    return ell_own_apply(ctx, A, x, y);
+    const bool tiled = !strcmp(name, "ell_tiled_values");
+    if (!tiled && strcmp(name, "ell_dia_order")) return false;
+    *rc = [&]() -> int {
+        // ELL whose slots are diagonals.  "ell_tiled_values": 1 = keep a copy of the values in tiles of 512 rows for the product (never
+        // made unasked: 8 bytes per slot for 1-7 %), 0 = drop it and multiply from the column-major array.  "ell_dia_order": 1 = keep the
+        // values once more in DIA order (row-major) and multiply with the DIA kernel, now; 0 = drop the copy and never build it; -1 = a
+        // candidate of AUTO's trial (the default).  8 bytes per slot.
+        SPMV_REQUIRE(m->format == SPMV_FMT_ELL && value <= 1 && value >= (tiled ? 0 : -1), "%s",
+                     tiled ? "ell_tiled_values: an ELL handle and 0 or 1" : "ell_dia_order: an ELL handle and -1, 0 or 1");
+        SPMV_HIP(hipSetDevice(m->ctx->device));
+        SPMV_HIP(hipStreamSynchronize(m->ctx->stream));
+        if (tiled) return ell_use_tiles(m, value == 1);
+        m->ell_dia_order_req = (int32_t)value;
+        if (value != 1) return ell_use_variant(m, m->ell_variant == kEllDiaOrder ? kEllTwoRows : m->ell_variant, /*keep_requested_copy=*/false);
+        SPMV_TRY(ell_use_variant(m, kEllDiaOrder, false));
+        if (runs_from_rowgrouped(m)) m->kernel = SPMV_CSR_VECTOR;  // (the format's own kernel runs: this variant of it)
+        return SPMV_OK;
+    }();
+    return true;
+}
+
+bool ell_get_param(const spmv_mat* m, const char* name, int64_t* value)
+{
+    if (!strcmp(name, "ell_tiled_values"))  // ELL: 1 if the product reads the values from the copy in tiles of 512 rows
+        *value = m->ell_tval ? 1 : 0;
+    else if (!strcmp(name, "ell_dia_order"))  // ELL: 1 if the product runs the DIA kernel over the DIA-order copy of the values
+        *value = m->ell_variant == kEllDiaOrder && m->ell_rval ? 1 : 0;
+    else if (!strcmp(name, "ell_non_conforming_rows"))  // ... and the rows the side kernel does
+        *value = m->ell_rval ? m->ell_nc_count : 0;
+    else if (!strcmp(name, "ell_diagonal_slots"))  // ELL: 1 if the slots were found to be diagonals (no column stream for conforming rows)
+        *value = m->ell_diag ? 1 : 0;
+    else if (!strcmp(name, "ell_variant"))
+        *value = m->ell_variant;
+    else if (!strcmp(name, "ell_copy_slots"))  // CSR: the ELL copy (kernel SPMV_CSR_ELL), 0 without one
+        *value = m->ell_copy ? (int64_t)m->ell_copy->nrow * m->ell_copy->k : 0;
+    else if (!strcmp(name, "ell_copy_diagonal_slots"))
+        *value = m->ell_copy && m->ell_copy->ell_diag ? 1 : 0;
+    else if (!strcmp(name, "ell_copy_variant"))
+        *value = m->ell_copy ? m->ell_copy->ell_variant : 0;
+    else
+        return false;
+    return true;
 }
 
 namespace
 {
+// a run-time unroll depth / bool as the std::integral_constant that f takes: the template arguments of the launches below
+template <class F>
+void with_bool(bool b, F&& f)
+{
+    if (b) return f(std::true_type{});
+    return f(std::false_type{});
+}
+template <class F>
+void with_unroll(int unroll, F&& f)
+{
+    if (unroll == 2) return f(std::integral_constant<int, 2>{});
+    if (unroll == 8) return f(std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 4>{});
+}
+
+// what runs is ell_effective's answer (ell_settings.hpp: every decision, none here); this function only launches it
 int ell_own_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y)
 {
-    if (A->ell_variant == 3 && A->ell_rval && A->ell_diag && !(A->flags & SPMV_FLAG_ELL_READ_COLUMNS))
+    const ell_settings run = ell_effective(A->ell_variant, A->lanes_per_row, (A->flags & SPMV_FLAG_ELL_READ_COLUMNS) != 0, A->nrow % 2 == 0, ((uintptr_t)A->b % 8) == 0,
+                                           ((uintptr_t)A->v % 16) == 0, ((uintptr_t)y % 16) == 0, A->ell_diag != nullptr, A->ell_diag_mask != nullptr,
+                                           A->ell_tval != nullptr, A->ell_rval != nullptr, A->ell_diag_lds, A->ell_pad_marked);
+    const unsigned grid = (unsigned)ceil_div(run.path == ell_path::one_row ? A->nrow : A->nrow / 2, kBlock);  // (the format's own kernels)
+    const size_t   lds  = run.xwin ? sizeof(double) * (size_t)A->ell_diag_lds : 0;
+    switch (run.path)
     {
-        // the DIA kernel over the row-major copy (every row whose slots are all diagonals), then the few other rows from the
-        // column-major arrays; every column of a conforming row is a real column: the bound is ncol
-        SPMV_TRY(dia_rows_apply(ctx, A->nrow, A->ncol, A->k, A->ell_diag, A->ell_rval, x, y, true, A->ell_off_min, A->ell_off_max, A->flags, A->ell_skip, A->k + (A->k & 1)));
-        if (A->ell_nc_count > 0)
-        {
-            hipLaunchKernelGGL(ell_rows_list_kernel, dim3((unsigned)ceil_div((int64_t)A->ell_nc_count * kWave, kBlock)), dim3(kBlock), 0, ctx->stream, A->ell_nc_count, A->ell_nc_rows,
-                               A->nrow, A->k, A->b, A->v, x, y);
-            SPMV_HIP(hipGetLastError());
-        }
-        return SPMV_OK;
-    }
-    const bool aligned = (A->nrow % 2 == 0) && (((uintptr_t)A->b % 8) == 0) && (((uintptr_t)A->v % 16) == 0) &&
-                         (((uintptr_t)y % 16) == 0);
-    // lanes_per_row == 1 (spmv_mat_set_kernel) or the variant AUTO timed fastest (ell_variant 1) select the one-row kernel
-    const bool x2 = aligned && !(A->lanes_per_row == 1) && A->ell_variant != 1;
-    if (x2 && A->ell_diag && A->ell_diag_mask && !(A->flags & SPMV_FLAG_ELL_READ_COLUMNS) && A->ell_variant != 2)
-    {
-        const unsigned grid = (unsigned)ceil_div(A->nrow / 2, kBlock);
-        const bool     xwin = A->ell_diag_lds > 0 && A->ell_diag_lds <= 5120;  // the x stretches of 512 rows fit 40 KB of LDS
-        const size_t   lds  = xwin ? sizeof(double) * (size_t)A->ell_diag_lds : 0;
-#define SPMV_ELL_DIAG_M(U, W, T, M)                                                                                                              \
-    hipLaunchKernelGGL((ell_diag_kernel_x2<U, W, T, M>), dim3(grid), dim3(kBlock), lds, ctx->stream, A->nrow, A->k, A->b, T ? A->ell_tval : A->v, x, y, \
-                       A->ell_diag, (const u64*)A->ell_diag_mask, A->ncol)
-#define SPMV_ELL_DIAG(U, W)                                    \
-    do                                                         \
-    {                                                          \
-        if (A->ell_pad_marked) /* the ELL copy of a CSR handle: padding left out */ \
-        {                                                      \
-            if (A->ell_tval)                                   \
-                SPMV_ELL_DIAG_M(U, W, true, true);             \
-            else                                               \
-                SPMV_ELL_DIAG_M(U, W, false, true);            \
-        }                                                      \
-        else if (A->ell_tval)                                  \
-            SPMV_ELL_DIAG_M(U, W, true, false);                \
-        else                                                   \
-            SPMV_ELL_DIAG_M(U, W, false, false);               \
-    } while (0)
-        // slots in flight per lane: 4 by default; lanes_per_row 4 / 8 select 8 / 2 (tools/tune.py ell: A/B)
-        if (A->lanes_per_row == 4)
-        {
-            if (xwin) SPMV_ELL_DIAG(8, true); else SPMV_ELL_DIAG(8, false);
-        }
-        else if (A->lanes_per_row == 8)
-        {
-            if (xwin) SPMV_ELL_DIAG(2, true); else SPMV_ELL_DIAG(2, false);
-        }
-        else
-        {
-            if (xwin) SPMV_ELL_DIAG(4, true); else SPMV_ELL_DIAG(4, false);
-        }
-#undef SPMV_ELL_DIAG
-#undef SPMV_ELL_DIAG_M
-    }
-    else if (x2)
-    {
-        const unsigned grid = (unsigned)ceil_div(A->nrow / 2, kBlock);
-        // slots in flight per lane: 4 by default; lanes_per_row 4 / 8 select 8 / 2 (tools/tune.py ell: A/B)
-#define SPMV_ELL_X2(U)                                                                                                                                     \
-    do                                                                                                                                                     \
-    {                                                                                                                                                      \
-        if (A->ell_pad_marked)                                                                                                 \
-            hipLaunchKernelGGL((ell_kernel_x2<U, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, A->nrow, A->k, A->b, A->v, x, y);  \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((ell_kernel_x2<U, false>), dim3(grid), dim3(kBlock), 0, ctx->stream, A->nrow, A->k, A->b, A->v, x, y); \
-    } while (0)
-        if (A->lanes_per_row == 4)
-            SPMV_ELL_X2(8);
-        else if (A->lanes_per_row == 8)
-            SPMV_ELL_X2(2);
-        else
-            SPMV_ELL_X2(4);
-#undef SPMV_ELL_X2
-    }
-    else
-    {
-        const unsigned grid = (unsigned)ceil_div(A->nrow, kBlock);
-        if (A->ell_pad_marked)
-            hipLaunchKernelGGL((ell_kernel<8, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, A->nrow, A->k, A->b, A->v, x, y);
-        else
-            hipLaunchKernelGGL((ell_kernel<8, false>), dim3(grid), dim3(kBlock), 0, ctx->stream, A->nrow, A->k, A->b, A->v, x, y);
+        case ell_path::dia_order:
+            // the DIA kernel over the row-major copy (every row whose slots are all diagonals), then the few other rows from the
+            // column-major arrays; every column of a conforming row is a real column: the bound is ncol
+            SPMV_TRY(dia_rows_apply(ctx, A->nrow, A->ncol, A->k, A->ell_diag, A->ell_rval, x, y, true, A->ell_off_min, A->ell_off_max, A->flags, A->ell_skip, A->k + (A->k & 1)));
+            if (A->ell_nc_count > 0)
+                hipLaunchKernelGGL(ell_rows_list_kernel, dim3((unsigned)ceil_div((int64_t)A->ell_nc_count * kWave, kBlock)), dim3(kBlock), 0, ctx->stream, A->ell_nc_count, A->ell_nc_rows,
+                                   A->nrow, A->k, A->b, A->v, x, y);
+            break;
+        case ell_path::diag_x2:
+            with_unroll(run.unroll, [&](auto U) { with_bool(run.xwin, [&](auto W) { with_bool(run.tiled, [&](auto T) { with_bool(run.masked, [&](auto M) {
+                hipLaunchKernelGGL((ell_diag_kernel_x2<U(), W(), T(), M()>), dim3(grid), dim3(kBlock), lds, ctx->stream, A->nrow, A->k, A->b, T() ? A->ell_tval : A->v, x, y, A->ell_diag,
+                                   (const u64*)A->ell_diag_mask, A->ncol);
+            }); }); }); });
+            break;
+        case ell_path::columns_x2:
+            with_unroll(run.unroll, [&](auto U) { with_bool(run.masked, [&](auto M) {
+                hipLaunchKernelGGL((ell_kernel_x2<U(), M()>), dim3(grid), dim3(kBlock), 0, ctx->stream, A->nrow, A->k, A->b, A->v, x, y);
+            }); });
+            break;
+        case ell_path::one_row:
+            with_bool(run.masked, [&](auto M) { hipLaunchKernelGGL((ell_kernel<8, M()>), dim3(grid), dim3(kBlock), 0, ctx->stream, A->nrow, A->k, A->b, A->v, x, y); });
+            break;
     }
     SPMV_HIP(hipGetLastError());
     return SPMV_OK;
 }
 }  // namespace
+
+int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y) { return A->nrow == 0 ? SPMV_OK : ell_own_apply(ctx, A, x, y); }
 }  // namespace spmv

@@ -105,15 +105,8 @@ int rowgrouped_set_kernel(spmv_mat* m, int32_t kernel)
             if (rc != SPMV_OK && rc != SPMV_ERR_ALLOC) return rc;  // (no room for the copy: the scan runs over the handle's own arrays)
             (void)hipGetLastError();
         }
-        if (m->format == SPMV_FMT_ELL)
-        {
-            m->ell_variant = 0;  // lanes_per_row (spmv_mat_set_kernel) picks the variant of the format's own kernel
-            if (m->ell_dia_order_req < 0 && m->ell_rval)
-            {
-                SPMV_HIP(hipStreamSynchronize(m->ctx->stream));
-                ell_free_dia_order(m);  // (a DIA-order copy the trial had kept: 8 bytes per slot nobody multiplies from now)
-            }
-        }
+        // lanes_per_row (spmv_mat_set_kernel) picks the variant of the format's own kernel; a DIA-order copy the trial had kept goes
+        if (m->format == SPMV_FMT_ELL) SPMV_TRY(ell_use_variant(m, kEllTwoRows, /*keep_requested_copy=*/true));
         return SPMV_OK;
     }
     if (kernel == SPMV_CSR_AUTO)

@@ -190,9 +190,39 @@ int select_rounds(spmv_ctx* ctx, int n, const std::function<int(int)>& launch, f
     return SPMV_OK;
 }
 
+static int select_slot_of(const char* name)  // the one table from name to slot; -1: no such name
+{
+    // (inside a host function: a constant array at namespace scope of a .hip file is emitted into the device code object too)
+    static const struct
+    {
+        const char* name;
+        int         slot;
+    } kNames[] = {{"vector", SPMV_CSR_VECTOR},     {"ldswin", SPMV_CSR_LDSWIN},   {"scalar", SPMV_CSR_SCALAR}, {"panel", SPMV_CSR_PANEL},
+                  {"twophase", SPMV_CSR_TWOPHASE}, {"segscan", SPMV_CSR_SEGSCAN}, {"split", SPMV_CSR_SPLIT},   {"ell", SPMV_CSR_ELL},
+                  {"split_low", kSelSplitLow},     {"variant1", kSelVariant1},    {"variant2", kSelVariant2},  {"dia_order", kSelDiaOrder}};
+    for (const auto& e : kNames)
+        if (!strcmp(name, e.name)) return e.slot;
+    return -1;
+}
+
+// "select_candidates", "select_rounds", "select_us_<name>"; false: not one of them (an unknown "select_us_" name included)
+bool select_get_param(const spmv_mat* m, const char* name, int64_t* value)
+{
+    const int slot = strncmp(name, "select_us_", 10) ? -1 : select_slot_of(name + 10);
+    if (slot >= 0)
+        *value = (int64_t)(m->sel_us[slot] + 0.5f);
+    else if (!strcmp(name, "select_candidates"))
+        *value = m->sel_candidates;
+    else if (!strcmp(name, "select_rounds"))  // rounds the handle's last trial went through until its candidates' minima stood still (2 .. 6; 0: no trial)
+        *value = m->sel_rounds;
+    else
+        return false;
+    return true;
+}
+
 void select_note(spmv_mat* m, int slot, float ms)
 {
-    if (slot >= 0 && slot < 10) m->sel_us[slot] = ms * 1000.f;
+    if (slot >= 0 && slot < kSelSlots) m->sel_us[slot] = ms * 1000.f;
     ++m->sel_candidates;
 }
 void select_reset(spmv_mat* m)
@@ -401,7 +431,7 @@ int csr_select_kernel(spmv_mat* m)
     for (size_t i = 0; i < cand.size(); ++i)  // the model's pick first; a later candidate has to win by 2 %
         if (t[i] >= 0.f)
         {
-            select_note(m, cand[i] == kSplitLow ? 0 : cand[i], t[i]);
+            select_note(m, cand[i] == kSplitLow ? (int)kSelSplitLow : cand[i], t[i]);
             if (t[i] < best_ms * (best >= 0 ? 0.98f : 1.0f))
             {
                 best    = cand[i];

@@ -222,6 +222,31 @@ def test_panel_launch_settings_are_what_launch_and_plan_computed_and_always_inst
     assert int(words[8]) == 5 * 4 * 4 * 3 * 5 * 4 and words[10] == "0"  # documented requests: get_param reports what runs
 
 
+def test_ell_launch_settings_are_what_the_product_decided_and_always_instantiated(tmp_path):
+    """What a product of an ELL handle launches (csrc/ell_settings.hpp: ell_effective, called by ell_own_apply) for every variant,
+    lanes_per_row, flag, row parity, alignment, set of copies in memory, window size and padding mark: equal to the nested
+    conditions and launch macros ell_own_apply held before (restated in tests/ell_settings_check.cpp) and always one of the
+    instantiated kernels - the fall-through of variant 3 without its copy, the 5120-double window cap and unroll 8 on the one-row
+    path included."""
+    import shutil
+    import subprocess
+
+    if not shutil.which("g++"):
+        pytest.skip("no g++ here")
+    exe = tmp_path / "ell_settings_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT / 'arm-spmv_amd' / 'csrc'}", str(ROOT / "tests" / "ell_settings_check.cpp"), "-o", str(exe)],
+                   check=True, timeout=120)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    words = r.stdout.replace(",", "").split()
+    assert r.returncode == 0, r.stdout + r.stderr
+    # variants x lanes_per_row x (flag, parity, 3 alignments, descriptors, mask, tiles, DIA-order copy, padding mark) x window sizes
+    assert int(words[1]) == 4 * 8 * 2 ** 10 * 4
+    assert words[3] == "0" and words[5] == "0"  # differences from ell_own_apply as it stood; results outside the instantiated set
+    paths = [int(w) for w in words[-4:]]
+    assert sum(paths) == int(words[1]) and min(paths) > 0  # every path is reached: DIA order, diagonal slots, columns, one row
+
+
 def test_plan_blobs_are_checked_without_a_device(pkg):
     """spmv_plan_check: the validation spmv_mat_set_plan / spmv_ctx_set_plan run on a blob, callable anywhere (a plan received
     from another rank, read from a file).  A node is 32 four-byte fields: format, kernel, lanes, flags, 9 panel fields, 2 split,

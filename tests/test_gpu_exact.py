@@ -439,6 +439,129 @@ def test_exact_ell_forward_and_transposed(ctx, pkg, seed):
     RUNS["ell"] += 1
 
 
+# ---- ELL: every launch the handle's settings can reach, on the smallest handles where each path can go wrong -----------------------
+ELL_READ_COLUMNS = 8  # SPMV_FLAG_ELL_READ_COLUMNS
+ELL_HOME_ROWS = (1024, 1536, 1025)  # the 4 * 256 floor of diagonal detection; one and a half tiles of 512 rows; odd: no descriptors
+ELL_HOME_PATTERNS = ("tridiagonal", "eleven_far_diagonals", "tridiagonal_with_strays")
+
+
+def _ell_home_shape(rng, nrow, pattern):
+    """(ncol, k, offsets, col (k, nrow), pad (k, nrow)): slot s of row i holds column i + offsets[s]; a column outside the matrix
+    is padding (column 0, value 0.0)"""
+    if pattern == "eleven_far_diagonals":
+        # more than 1024 apart: eleven clusters of 512 doubles, 5632 > the 5120-double cap, so no x windows
+        offs, ncol = np.arange(11) * 1100, nrow + 10 * 1100 + 8
+    else:
+        offs, ncol = np.array([-1, 0, 1]), nrow
+    col = np.arange(nrow)[None, :] + offs[:, None]
+    pad = (col < 0) | (col >= ncol)
+    col[pad] = 0
+    if pattern == "tridiagonal_with_strays":  # about 1 % of the slots point elsewhere: rows for the side kernel, far fewer than 1/16
+        stray = (rng.uniform(size=col.shape) < 0.01) & ~pad
+        col[stray] = rng.integers(0, ncol, int(stray.sum()))
+    return ncol, len(offs), offs, col, pad
+
+
+@pytest.mark.parametrize("pattern", ELL_HOME_PATTERNS)
+@pytest.mark.parametrize("nrow", ELL_HOME_ROWS)
+def test_exact_ell_every_setting_launches_and_reports_as_before(ctx, pkg, nrow, pattern):
+    """lanes_per_row (0, 1, 4, 8) x flags (0, read columns) x "ell_tiled_values" (0, 1) x "ell_dia_order" (0, 1) on ELL handles of
+    1024, 1536 and 1025 rows whose slots are diagonals that fit the x windows, that exceed them, and that have stray columns:
+    every product equals the exact reference bit for bit, and after every setting the handle reports what the rules of the
+    engine say (written out here, not read off the code under test):
+      * the slots are found to be diagonals on an even handle of 1024 rows and more (here every pattern conforms in far more than
+        half of its row pairs), never on an odd one;
+      * set_kernel(VECTOR) makes variant 0 run; "ell_dia_order" 1 builds the copy and makes variant 3 run - refused without
+        diagonal slots - and 0 drops the copy; "ell_variant" says so whatever the flags are;
+      * the tiled copy exists where it was asked for and the slots are diagonals; without them the request is a no-op;
+      * the side kernel's rows are those with a slot off its diagonal, padding included;
+      * with both copies dropped device_bytes is back where it began.
+    These handles are below the size at which AUTO times anything: no trial takes part."""
+    capi = pkg.capi
+    rng = np.random.default_rng(BASE + 14_500 + 7 * nrow + ELL_HOME_PATTERNS.index(pattern))
+    ncol, k, offs, col2, pad2 = _ell_home_shape(rng, nrow, pattern)
+    col, pad = col2.astype(np.int32).ravel(), pad2.ravel()
+    ent = ex.ell_entries(nrow, k, col, np.zeros(len(col)))
+    bits, e = _bits((ent[0], nrow))
+    val = ex.dyadic(rng, len(col), bits, e)
+    val[pad] = 0.0
+    F = Exact(rng, nrow, ncol, ex.ell_entries(nrow, k, col, val), bits, e)
+    diagonal = nrow % 2 == 0 and nrow >= 1024
+    off_diagonal_rows = int(np.any(col2 != np.arange(nrow)[None, :] + offs[:, None], axis=0).sum())
+    assert 0 < off_diagonal_rows * 16 <= nrow or pattern == "eleven_far_diagonals" and off_diagonal_rows == 0
+    what = f"ELL {nrow} x {ncol}, k = {k}, {pattern}"
+    A = ctx.ell(nrow, ncol, k, int((~pad).sum()), col, val)
+    dx = ctx.vector_from(F.xp)
+    bytes0 = A.get_param("device_bytes")
+    assert A.get_param("ell_diagonal_slots") == int(diagonal), what
+    assert (A.info.kernel, A.get_param("ell_variant"), A.get_param("ell_tiled_values"), A.get_param("ell_dia_order")) == (VECTOR, 0, 0, 0), what
+    F.check(ctx, A, f"{what}, as created", dx=dx)
+    for lanes in (0, 1, 4, 8):
+        for flags in (0, ELL_READ_COLUMNS):
+            for tiled in (0, 1):
+                for dia in (0, 1):
+                    A.set_kernel(VECTOR, lanes)
+                    assert A.get_param("ell_variant") == 0, what  # (a copy that was asked for stays; the variant does not)
+                    A.set_flags(flags)
+                    A.set_param("ell_tiled_values", tiled)
+                    if dia and not diagonal:
+                        with pytest.raises(capi.SpmvError, match="were not found to be diagonals"):
+                            A.set_param("ell_dia_order", 1)
+                        A.set_param("ell_dia_order", 0)
+                        continue  # (refused: the setting does not exist on this handle)
+                    A.set_param("ell_dia_order", dia)
+                    now = f"{what}, lanes={lanes} flags={flags} tiled={tiled} dia_order={dia}"
+                    F.check(ctx, A, now, dx=dx)
+                    got = {n: A.get_param(n) for n in ("ell_variant", "ell_tiled_values", "ell_dia_order", "ell_non_conforming_rows", "ell_diagonal_slots")}
+                    want = {"ell_variant": 3 if dia else 0, "ell_tiled_values": int(bool(tiled and diagonal)), "ell_dia_order": dia,
+                            "ell_non_conforming_rows": off_diagonal_rows if dia else 0, "ell_diagonal_slots": int(diagonal)}
+                    assert got == want and A.info.kernel == VECTOR, now
+                    assert (A.get_param("device_bytes") > bytes0) == bool(dia or (tiled and diagonal)), now
+    A.set_param("ell_tiled_values", 0)
+    A.set_param("ell_dia_order", 0)
+    assert A.get_param("device_bytes") == bytes0 and A.get_param("ell_variant") == 0, what
+    A.set_flags(0)
+    F.check(ctx, A, f"{what}, both copies dropped", dx=dx)
+
+
+@pytest.mark.parametrize("nrow", ELL_HOME_ROWS)
+def test_exact_ell_copy_of_a_csr_handle_leaves_its_padding_out(ctx, pkg, nrow):
+    """the masked kernels: a tridiagonal CSR handle in which every eighth row (and the first and the last) holds k - 1 = 2 entries,
+    forced onto its ELL copy.  The product is exact; the copy's slots are diagonals on an even handle (three of four row pairs
+    conform in every slot), not on an odd one.  That the padding takes no part in the sums shows where x is not finite: a padding
+    slot holds 0.0 and points at its row's own last column, so with x = inf there a row ends at +-inf, the sign of its stored entry,
+    as in the reference's CSR loop - a kernel that multiplied the padding would add 0.0 * inf and end at NaN."""
+    rng = np.random.default_rng(BASE + 14_600 + nrow)
+    rows = np.arange(nrow)
+    keep = np.stack([rows >= 1, np.ones(nrow, bool), (rows + 1 < nrow) & (rows % 8 != 3)], axis=1)  # columns i - 1, i, i + 1
+    lens = keep.sum(axis=1)
+    assert set(lens.tolist()) == {2, 3}
+    row_ptr = np.concatenate(([0], np.cumsum(lens))).astype(np.int32)
+    col = (rows[:, None] + np.array([-1, 0, 1])[None, :])[keep].astype(np.int32)
+    ent = ex.csr_entries(row_ptr, col, np.zeros(len(col)))
+    bits, e = _bits((ent[0], nrow))
+    val = ex.dyadic(rng, len(col), bits, e)
+    F = Exact(rng, nrow, nrow, ex.csr_entries(row_ptr, col, val), bits, e)
+    A = ctx.csr(nrow, nrow, row_ptr, col, val)
+    A.set_kernel(ELLK)
+    what = f"CSR {nrow} x {nrow}, rows of 2 and 3 entries, ELL copy"
+    assert A.info.kernel == ELLK and A.get_param("ell_copy_slots") == 3 * nrow, what
+    assert A.get_param("ell_copy_diagonal_slots") == int(nrow % 2 == 0) and A.get_param("ell_copy_variant") == 0, what
+    F.check(ctx, A, what)
+    short = np.flatnonzero(lens == 2)[1:-1:5]  # short rows (i % 8 == 3): their last column is i, which rows i - 1, i, i + 1 read
+    x_inf = F.x.copy()
+    x_inf[short] = np.inf
+    want = F.want1.copy()
+    for j in short:
+        for i in (j - 1, j, j + 1):  # (one inf per row: the short rows are eight apart)
+            want[i] = np.inf * np.sign(val[row_ptr[i] + int(np.flatnonzero(col[row_ptr[i]:row_ptr[i + 1]] == j)[0])])
+    dy = ctx.vector_from(F.y0)
+    ctx.apply(A, ctx.vector_from(x_inf), dy)
+    ctx.sync()
+    got = dy.download()
+    assert len(short) >= 20 and np.array_equal(got, want), f"{what}, x = inf at the last column of {len(short)} short rows: {_fail(got, want)}"
+
+
 def test_ell_transposed_carries_inf_through_padding_as_nan(ctx, orc):
     """an inf in x at a padded row reaches y[pad column] as NaN under every companion kernel (0.0 * inf), as the slot-list oracle
     says"""
