@@ -103,6 +103,7 @@ SIGNATURES = {
     "spmv_cg_multi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_cg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_cgls": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_double, C.POINTER(C.c_int32), _f64p, _f64p]),
+    "spmv_bicgstab": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_symgs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32]),
     "spmv_symgs_setup": (C.c_int, [_vp, _vp]),
     "spmv_symgs_order": (C.c_int, [_vp, _vp, _i32p]),
@@ -464,6 +465,15 @@ class Context:
         it, nres, res = C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
         _check(self._lib.spmv_cgls(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, damp, C.byref(it), C.byref(nres), C.byref(res)))
         return it.value, nres.value, res.value
+
+    def bicgstab(self, A: "Matrix", b: "Vector", x: "Vector", max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
+                 precond: int = 0):
+        """A x = b for a square, not necessarily symmetric A by right-preconditioned BiCGSTAB on the device, from the x passed in: any
+        format, two forward products per iteration, no transposed state.  precond: PRECOND_NONE, or PRECOND_JACOBI on a CSR handle.
+        Stops at ||r|| <= rel_tol * ||b||; returns (iterations, ||r|| / ||b||)"""
+        it, res = C.c_int32(0), C.c_double(0.0)
+        _check(self._lib.spmv_bicgstab(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))
+        return it.value, res.value
 
     def coo_to_csr(self, coo: "Matrix") -> "Matrix":
         h = _vp()

@@ -1340,6 +1340,32 @@ int spmv_cgls(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, 
     return cgls_solve(ctx, A, b->d, x->d, max_iter, rel_tol, check_every, damp, iters, rel_normal_resid, rel_resid);
 }
 
+// nonsymmetric square systems over two forward products (solver_bicgstab.hip).  Every check is made before the device is touched.
+int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol, int32_t check_every,
+                  int32_t precond, int32_t* iters, double* rel_resid)
+{
+    SPMV_REQUIRE(ctx && A && b && x && iters && rel_resid, "spmv_bicgstab: null argument");
+    SPMV_REQUIRE(A->nrow == A->ncol, "spmv_bicgstab: the matrix (shard) is %d x %d, not square", A->nrow, A->ncol);
+    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "spmv_bicgstab: b has %lld and x %lld entries, the matrix %d rows", (long long)b->n,
+                 (long long)x->n, A->nrow);
+    SPMV_REQUIRE(b->n == 0 || b->d + b->n <= x->d || x->d + x->n <= b->d, "spmv_bicgstab: b and x must not overlap");
+    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_bicgstab: max_iter=%d rel_tol=%g", max_iter, rel_tol);
+    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS,
+                 "spmv_bicgstab: unknown preconditioner %d", precond);
+    if (precond == SPMV_PRECOND_SYMGS)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_bicgstab: the symmetric Gauss-Seidel preconditioner is not built for this solver");
+    if (precond == SPMV_PRECOND_JACOBI && A->format != SPMV_FMT_CSR)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_bicgstab: the Jacobi preconditioner reads the diagonal of a CSR handle");
+    // Jacobi reads the handle's own arrays; the plain solve needs the forward product alone and takes such a handle
+    SPMV_REQUIRE(!(precond == SPMV_PRECOND_JACOBI && A->nnz > 0 && (!A->b || !A->v)),
+                 "spmv_bicgstab: this handle gave up its CSR arrays (panel_keep_csr = 0): no diagonal for the Jacobi preconditioner");
+    *iters     = 0;
+    *rel_resid = 0.0;
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return bicgstab_solve(ctx, A, b->d, x->d, max_iter, rel_tol, check_every, precond, iters, rel_resid);
+}
+
 int spmv_symgs_setup(spmv_ctx* ctx, spmv_mat* A)
 {
     SPMV_REQUIRE(ctx && A, "spmv_symgs_setup: null argument");

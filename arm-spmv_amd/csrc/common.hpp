@@ -460,6 +460,9 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
 // solver_cgls.hip: CGLS for min ||b - A x||^2 + damp^2 ||x||^2 over the forward and the transposed product of any handle
 int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                double damp, int* iters, double* rel_normal_resid, double* rel_resid);
+// solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle (precond: NONE, JACOBI)
+int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
+                   int precond, int* iters, double* rel_resid);
 // kernels_ell.hip (what a product launches: ell_settings.hpp)
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int ell_analyse(spmv_mat* m);

@@ -22,7 +22,8 @@ def context_on_current_stream(device: int | None = None) -> "capi.Context":
 
 
 class SparseOperator:
-    """A (nrow x ncol) of a capi.Matrix: matvec(x) = A x, rmatvec(y) = A^T y, lstsq(b) = argmin ||b - A x||, each into a fresh tensor"""
+    """A (nrow x ncol) of a capi.Matrix: matvec(x) = A x, rmatvec(y) = A^T y, lstsq(b) = argmin ||b - A x||, solve(b) = A^-1 b (square A), each
+    into a fresh tensor"""
 
     def __init__(self, ctx: "capi.Context", A: "capi.Matrix"):
         self.ctx, self.A = ctx, A
@@ -64,6 +65,21 @@ class SparseOperator:
         self.last_lstsq = self.ctx.cgls(self.A, self.ctx.wrap_vector(b.detach()), self.ctx.wrap_vector(x), **kw)
         return x
 
+
+    def solve(self, b: torch.Tensor, x0: torch.Tensor | None = None, **kw) -> torch.Tensor:
+        """x with A x = b for a square A by capi.Context.bicgstab from x0 (default 0), into a fresh tensor; kw: max_iter, rel_tol,
+        check_every, precond.  (iterations, residual) of the solve are left in self.last_solve.  No autograd through the solve"""
+        nrow, ncol = self.shape
+        if nrow != ncol:
+            raise ValueError(f"solve: the operator is {nrow} x {ncol}, not square (lstsq takes any shape)")
+        self._check(b, nrow, "solve")
+        if x0 is None:
+            x = torch.zeros(ncol, dtype=torch.float64, device=self.device)
+        else:
+            self._check(x0, ncol, "solve x0")
+            x = x0.detach().clone()
+        self.last_solve = self.ctx.bicgstab(self.A, self.ctx.wrap_vector(b.detach()), self.ctx.wrap_vector(x), **kw)
+        return x
 
 class _SpMV(torch.autograd.Function):
     @staticmethod

@@ -549,6 +549,36 @@ int spmv_cg_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* B
  *   Device memory: work vectors r, q (nrow) and p, s (ncol) and a small scalar block for the duration of the call. */
 int spmv_cgls(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
               int32_t check_every, double damp, int32_t* iters, double* rel_normal_resid, double* rel_resid);
+/* spmv_bicgstab: A x = b for a square A that need not be symmetric, by right-preconditioned BiCGSTAB, starting from the x passed in
+ *   (solver_bicgstab.hip).  b and x have nrow entries.  A is any handle spmv_apply accepts: all five formats, uploaded,
+ *   wrapped, or a shard that holds a square matrix.  Synchronous.  Both products of an iteration are forward ones and run the
+ *   handle's own kernel; no transposed state is built, and the handle's kernel, copies, device_bytes and plan stay as they were.
+ *   Recurrence:  r = b - A x;  rhat = r;  p = r;  rho = rhat.r;  then per iteration  phat = M^-1 p;  v = A phat;
+ *   alpha = rho / rhat.v;  s = r - alpha v;  shat = M^-1 s;  t = A shat;  omega = t.s / t.t;  x += alpha phat + omega shat;
+ *   r = s - omega t;  rho' = rhat.r;  beta = (rho' / rho) * (alpha / omega);  p = r + beta (p - omega v);  rho = rho'.
+ *   precond: SPMV_PRECOND_NONE (M = I: phat and shat are p and s, no copies) or SPMV_PRECOND_JACOBI (M = diag(A) of a CSR handle,
+ *   duplicates summed; a zero or missing diagonal entry: SPMV_ERR_INVALID).  The preconditioner is applied on the right, so r is
+ *   the residual of A x = b itself.  SPMV_PRECOND_SYMGS and Jacobi on a non-CSR handle: SPMV_ERR_UNSUPPORTED (out of scope here).
+ *   Seven launches per iteration (the two products, two dot kernels, three vector kernels); alpha, omega, beta, rho and the dots
+ *   stay on the device; the host reads r.r and a status word every check_every iterations (>= 1) and after the last one.
+ *   Stopping: r.r <= rel_tol^2 * b.b on the recurrence's r, or max_iter iterations.  *iters = iterations run, *rel_resid =
+ *   sqrt(r.r / b.b) at the last check.  b.b = 0: *iters = 0, *rel_resid = 0, x untouched (spmv_cg's rule).  r0.r0 = 0 or already
+ *   within the tolerance, or max_iter = 0: no iteration, *rel_resid is that of x0.  An iteration that starts with r.r at or below
+ *   1e-28 b.b passes quietly (x and the work vectors stay); r.r = 0 ends the solve.  t.t = 0 (s = 0: the half step landed):
+ *   omega = 0, x += alpha phat, r = s.
+ *   Breakdown - rho = 0, rhat.v = 0, or omega = 0 while r.r is above that floor, or a non-finite b.b, rho or r.r:
+ *   SPMV_ERR_INVALID, and spmv_last_error() names the quantity and "at or before iteration k"; the kernel that detects it leaves x
+ *   and r alone, so x holds an iterate of the recurrence.
+ *   Refused before any device use with SPMV_ERR_INVALID: null pointers, nrow != ncol, b or x with other than nrow entries, b and x
+ *   overlapping, max_iter < 0, rel_tol < 0, an unknown precond, Jacobi on a CSR handle without its arrays (panel_keep_csr 0; the
+ *   plain solve takes such a handle).  nrow = 0: SPMV_OK, *iters = 0, nothing is launched.
+ *   Deterministic dot products (per-workgroup partial sums added in a fixed order by the workgroup that finishes last): a solve is
+ *   exactly as reproducible as the product its handle runs.  x and b need only be 8-byte aligned; where they are 16-byte aligned
+ *   the vector kernels use 16-byte accesses on them.
+ *   Device memory: six work vectors of nrow doubles (Jacobi: nine) and a small scalar block for the duration of the call, released
+ *   on every path. */
+int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
+                  int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
 /* spmv_symgs: `sweeps` symmetric Gauss-Seidel sweeps on A*x = b, x updated in place: forward over the rows in sweep
  *   order with the newest x, then backward — the sweep the reference's `diagonal // for SymGS` fields were reserved
  *   for (include/matrix.h:36,81) and that it never wrote.  A: CSR handle holding the whole square matrix with a non-zero
