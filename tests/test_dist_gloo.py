@@ -157,19 +157,11 @@ class _OracleOps:
     def axpby(self, alpha, x, beta, y, w):
         w.numpy()[:] = alpha * x.numpy() + beta * y.numpy()
 
-    # overlap variant (dist.HipShardOps.enable_overlap): the shard split by column range with numpy
+    # overlap variant (dist.HipShardOps.enable_overlap): the shard split by column range with numpy (tests/sharded_ref.py)
     def enable_overlap(self, c0, c1):
-        srp, scol, sval = self.m
-        rows = np.repeat(np.arange(len(srp) - 1), np.diff(srp))
-        inside = (scol >= c0) & (scol < c1)
+        import sharded_ref  # (here, not at the top: the spawned workers put tests/ on sys.path themselves)
 
-        def part(mask, rebase):
-            rp = np.zeros(len(srp), np.int64)
-            np.add.at(rp, rows[mask] + 1, 1)
-            return (np.cumsum(rp).astype(np.int32), np.ascontiguousarray(scol[mask] - rebase, dtype=np.int32),
-                    np.ascontiguousarray(sval[mask]))
-
-        self.m_in, self.m_out = part(inside, c0), part(~inside, 0)
+        self.m_in, self.m_out = sharded_ref.split_columns(*self.m, c0, c1)
         self.overlap = True
 
     def begin_local(self, p_own, q_own):

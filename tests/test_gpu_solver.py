@@ -229,10 +229,11 @@ def test_cg_graph_replay_takes_the_same_iterations(ctx, pkg, monkeypatch):
 
 
 def test_sharded_cg_with_the_engine_as_local_ops():
-    """dist.cg_sharded + dist.HipShardOps on one GPU (world 1; the N > 1 collectives are covered on CPU with gloo in
-    tests/test_dist_gloo.py): same answer as the single-device spmv_cg.  In a child process, because torch must
-    initialise its HIP runtime BEFORE the engine's library is loaded (as bench.py does) and this process has long
-    loaded the engine."""
+    """dist.cg_sharded + dist.HipShardOps on one GPU at world 1 (50,000 rows): same answer as the single-device spmv_cg.  N > 1:
+    the collectives alone on CPU with gloo in tests/test_dist_gloo.py; the engine on real shards - every local operation of
+    every rank of 1, 2, 3 and 8, and the iteration on three ranks over gloo - in tests/test_gpu_sharded.py.  In a child
+    process, because torch must initialise its HIP runtime BEFORE the engine's library is loaded (as bench.py does) and this
+    process has long loaded the engine."""
     import subprocess
     import sys
     from pathlib import Path
