@@ -18,7 +18,7 @@ LIB_PATH = Path(os.environ.get("SPMV_HIP_SO") or _PKG / "lib" / "libspmv_hip.so"
 
 FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA = 0, 1, 2, 3, 4
 CSR_AUTO, CSR_VECTOR, CSR_LDSWIN, CSR_SCALAR, CSR_PANEL, CSR_TWOPHASE, CSR_SEGSCAN, CSR_SPLIT, CSR_ELL = 0, 1, 2, 3, 4, 5, 6, 7, 8
-PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS = 0, 1, 2
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0 = 0, 1, 2, 3
 FLAG_DPP_REDUCE, FLAG_XCD_REMAP = 1, 2
 
 _i32p = C.POINTER(C.c_int32)
@@ -107,6 +107,10 @@ SIGNATURES = {
     "spmv_symgs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32]),
     "spmv_symgs_setup": (C.c_int, [_vp, _vp]),
     "spmv_symgs_order": (C.c_int, [_vp, _vp, _i32p]),
+    "spmv_ilu0_setup": (C.c_int, [_vp, _vp]),
+    "spmv_ilu0_solve": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_ilu0_factors": (C.c_int, [_vp, _vp, _f64p]),
+    "spmv_ilu0_order": (C.c_int, [_vp, _vp, _i32p]),
     "spmv_coo_to_csr": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_coo_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_csr_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -437,13 +441,36 @@ class Context:
         _check(self._lib.spmv_symgs_order(self.h, A.h, out.ctypes.data_as(_i32p)))
         return out
 
+    def ilu0_setup(self, A: "Matrix") -> None:
+        """ILU(0) of a CSR handle holding the whole square matrix, on the device: order, symbolic and numeric set-up (synchronous,
+        idempotent).  Sweep order: A.set_param("ilu0_order", 1 multicolour (default) | 0 rows)"""
+        _check(self._lib.spmv_ilu0_setup(self.h, A.h))
+
+    def ilu0_solve(self, A: "Matrix", r: "Vector", z: "Vector") -> None:
+        """z = U^-1 L^-1 r with the ILU(0) factors of A (set up on first use), asynchronous; r and z must not overlap"""
+        _check(self._lib.spmv_ilu0_solve(self.h, A.h, r.h, z.h))
+
+    def ilu0_factors(self, A: "Matrix") -> np.ndarray:
+        """the factor values aligned to the handle's own CSR entries, as an in-place csrilu0 would leave them (l_ik below the
+        diagonal in sweep order, u_ij on and above it; of duplicates the first stored one carries the value, the others 0.0)"""
+        out = np.zeros(A.info.nnz, dtype=np.float64)
+        _check(self._lib.spmv_ilu0_factors(self.h, A.h, out.ctypes.data_as(_f64p)))
+        return out
+
+    def ilu0_order(self, A: "Matrix") -> np.ndarray:
+        """sets the handle up if need be and returns order[k] = the k-th row of the ILU(0) sweep"""
+        out = np.zeros(A.info.nrow, dtype=np.int32)
+        _check(self._lib.spmv_ilu0_order(self.h, A.h, out.ctypes.data_as(_i32p)))
+        return out
+
     def cg(self, A: "Matrix", b: "Vector", x: "Vector", max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
-           jacobi: bool = False, symgs: bool = False):
+           jacobi: bool = False, symgs: bool = False, precond: int | None = None):
         """conjugate gradients on the device from the x passed in (jacobi: diagonal preconditioner, symgs: one symmetric
-        Gauss-Seidel sweep per iteration; CSR handles); returns (iterations, ||r|| / ||b||)"""
+        Gauss-Seidel sweep per iteration; CSR handles); returns (iterations, ||r|| / ||b||).  precond, if given, is passed as it
+        is (PRECOND_*; PRECOND_ILU0: the ILU(0) factors of a CSR handle, set up on first use)"""
         it, res = C.c_int32(0), C.c_double(0.0)
-        _check(self._lib.spmv_cg(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, PRECOND_SYMGS if symgs else (PRECOND_JACOBI if jacobi else PRECOND_NONE), C.byref(it),
-                                 C.byref(res)))
+        pc = precond if precond is not None else (PRECOND_SYMGS if symgs else (PRECOND_JACOBI if jacobi else PRECOND_NONE))
+        _check(self._lib.spmv_cg(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, pc, C.byref(it), C.byref(res)))
         return it.value, res.value
 
     def cg_multi(self, A: "Matrix", B: "Vector", X: "Vector", k: int, max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
@@ -469,7 +496,8 @@ class Context:
     def bicgstab(self, A: "Matrix", b: "Vector", x: "Vector", max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
                  precond: int = 0):
         """A x = b for a square, not necessarily symmetric A by right-preconditioned BiCGSTAB on the device, from the x passed in: any
-        format, two forward products per iteration, no transposed state.  precond: PRECOND_NONE, or PRECOND_JACOBI on a CSR handle.
+        format, two forward products per iteration, no transposed state.  precond: PRECOND_NONE, or PRECOND_JACOBI or PRECOND_ILU0 (the
+        ILU(0) factors, set up on first use; two applications per iteration) on a CSR handle.
         Stops at ||r|| <= rel_tol * ||b||; returns (iterations, ||r|| / ||b||)"""
         it, res = C.c_int32(0), C.c_double(0.0)
         _check(self._lib.spmv_bicgstab(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))

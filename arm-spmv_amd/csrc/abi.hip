@@ -102,6 +102,7 @@ void mat_free(spmv_mat* m)
     ell_layouts_free(m);
     csr_layouts_free(m, kCsrAllLayouts);
     symgs_free(m);
+    ilu0_free(m);
     if (m->rowgrouped) mat_free(m->rowgrouped);
     coo_free_bins(m);
     delete m;
@@ -807,6 +808,11 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
         SPMV_REQUIRE(value == 0 || value == 1, "symgs_order: 0 (row order) or 1 (multicolour), got %lld", (long long)value);
         m->gs_order = (int32_t)value;
     }
+    else if (!strcmp(name, "ilu0_order"))  // 1 multicolour, 0 the matrix's own row order; takes effect at the next set-up / application
+    {
+        SPMV_REQUIRE(value == 0 || value == 1, "ilu0_order: 0 (row order) or 1 (multicolour), got %lld", (long long)value);
+        m->ilu_order = (int32_t)value;
+    }
     else if (!strcmp(name, "twophase_panel_cols"))  // takes effect at the next spmv_mat_set_kernel(TWOPHASE)
         m->tp_pcols_req = (int32_t)value;
     else if (!strcmp(name, "twophase_placement_budget_mb"))
@@ -894,6 +900,11 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
     if (!strncmp(name, "symgs_", 6))
     {
         SPMV_REQUIRE(symgs_info(m, name, value) == SPMV_OK, "unknown parameter '%s'", name);
+        return SPMV_OK;
+    }
+    if (!strncmp(name, "ilu0_", 5))
+    {
+        SPMV_REQUIRE(ilu0_info(m, name, value) == SPMV_OK, "unknown parameter '%s'", name);
         return SPMV_OK;
     }
     if (transpose_get_param(m, name, value)) return SPMV_OK;  // "transpose_ready", "transpose_bytes", "transpose_kernel", ...
@@ -1290,8 +1301,9 @@ int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, in
                  (long long)b->n, (long long)x->n, A->nrow);
     SPMV_REQUIRE(b->d != x->d || x->n == 0, "spmv_cg: b and x must not alias");
     SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_cg: max_iter=%d rel_tol=%g", max_iter, rel_tol);
-    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS,
+    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
                  "spmv_cg: unknown preconditioner %d", precond);
+    if (precond == SPMV_PRECOND_ILU0) SPMV_TRY(ilu0_check_handle(A, "spmv_cg"));
     SPMV_TRY(use_device(ctx));
     return cg_solve(ctx, A, b->d, x->d, max_iter, rel_tol, check_every, precond, iters, rel_resid);
 }
@@ -1308,12 +1320,14 @@ int spmv_cg_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* B
                  "spmv_cg_multi: B has %lld and X %lld entries, nrow * k = %d * %d", (long long)B->n, (long long)X->n, A->nrow, k);
     SPMV_REQUIRE(B->n == 0 || X->n == 0 || B->d + B->n <= X->d || X->d + X->n <= B->d, "spmv_cg_multi: B and X must not overlap");
     SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_cg_multi: max_iter=%d rel_tol=%g", max_iter, rel_tol);
-    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS,
+    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
                  "spmv_cg_multi: unknown preconditioner %d", precond);
     if (A->format != SPMV_FMT_CSR && A->format != SPMV_FMT_ELL)
         SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: CSR and ELL handles only (format %d), as spmv_apply_multi", A->format);
     if (precond == SPMV_PRECOND_SYMGS)
         SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: the symmetric Gauss-Seidel preconditioner is not built for k columns");
+    if (precond == SPMV_PRECOND_ILU0)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: the ILU(0) preconditioner is not built for k columns");
     if (precond == SPMV_PRECOND_JACOBI && A->format != SPMV_FMT_CSR)
         SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: the Jacobi preconditioner reads the diagonal of a CSR handle");
     // the product reads the handle's own arrays: a CSR handle that released them (panel_keep_csr = 0) is refused here, on the host
@@ -1350,12 +1364,13 @@ int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec*
                  (long long)x->n, A->nrow);
     SPMV_REQUIRE(b->n == 0 || b->d + b->n <= x->d || x->d + x->n <= b->d, "spmv_bicgstab: b and x must not overlap");
     SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_bicgstab: max_iter=%d rel_tol=%g", max_iter, rel_tol);
-    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS,
+    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
                  "spmv_bicgstab: unknown preconditioner %d", precond);
     if (precond == SPMV_PRECOND_SYMGS)
         SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_bicgstab: the symmetric Gauss-Seidel preconditioner is not built for this solver");
     if (precond == SPMV_PRECOND_JACOBI && A->format != SPMV_FMT_CSR)
         SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_bicgstab: the Jacobi preconditioner reads the diagonal of a CSR handle");
+    if (precond == SPMV_PRECOND_ILU0) SPMV_TRY(ilu0_check_handle(A, "spmv_bicgstab"));
     // Jacobi reads the handle's own arrays; the plain solve needs the forward product alone and takes such a handle
     SPMV_REQUIRE(!(precond == SPMV_PRECOND_JACOBI && A->nnz > 0 && (!A->b || !A->v)),
                  "spmv_bicgstab: this handle gave up its CSR arrays (panel_keep_csr = 0): no diagonal for the Jacobi preconditioner");
@@ -1393,6 +1408,53 @@ int spmv_symgs(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32
     SPMV_TRY(symgs_setup(A));  // first call: split, levels, schedule (synchronous); later calls: nothing
     for (int k = 0; k < sweeps; ++k) SPMV_TRY(symgs_sweep(ctx, A, b->d, x->d, /*zero_guess=*/false));
     return SPMV_OK;
+}
+
+// ILU(0) (ilu0.hip).  Every check is made before the device is touched, so that they hold (and are tested) on a machine without one.
+int spmv_ilu0_setup(spmv_ctx* ctx, spmv_mat* A)
+{
+    SPMV_REQUIRE(ctx && A, "spmv_ilu0_setup: null argument");
+    SPMV_REQUIRE(A->ctx == ctx, "spmv_ilu0_setup: the matrix belongs to another context");
+    SPMV_TRY(ilu0_check_handle(A, "spmv_ilu0_setup"));
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return ilu0_setup(A);
+}
+
+int spmv_ilu0_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z)
+{
+    SPMV_REQUIRE(ctx && A && r && z, "spmv_ilu0_solve: null argument");
+    SPMV_REQUIRE(A->ctx == ctx, "spmv_ilu0_solve: the matrix belongs to another context");
+    SPMV_TRY(ilu0_check_handle(A, "spmv_ilu0_solve"));
+    SPMV_REQUIRE(r->n == A->nrow && z->n == A->nrow, "spmv_ilu0_solve: r has %lld and z %lld entries, the matrix %d rows", (long long)r->n,
+                 (long long)z->n, A->nrow);
+    SPMV_REQUIRE(r->n == 0 || r->d + r->n <= z->d || z->d + z->n <= r->d, "spmv_ilu0_solve: r and z must not overlap");
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    SPMV_TRY(ilu0_setup(const_cast<spmv_mat*>(A)));  // first call: order, symbolic, numeric (synchronous); later calls: nothing
+    return ilu0_apply(ctx, A, r->d, z->d);
+}
+
+int spmv_ilu0_factors(spmv_ctx* ctx, const spmv_mat* A, double* values_host)
+{
+    SPMV_REQUIRE(ctx && A && (values_host || A->nnz == 0), "spmv_ilu0_factors: null argument");
+    SPMV_REQUIRE(A->ctx == ctx, "spmv_ilu0_factors: the matrix belongs to another context");
+    SPMV_TRY(ilu0_check_handle(A, "spmv_ilu0_factors"));
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    SPMV_TRY(ilu0_setup(const_cast<spmv_mat*>(A)));
+    return ilu0_factor_values(A, values_host);
+}
+
+int spmv_ilu0_order(spmv_ctx* ctx, const spmv_mat* A, int32_t* order_host)
+{
+    SPMV_REQUIRE(ctx && A && (order_host || A->nrow == 0), "spmv_ilu0_order: null argument");
+    SPMV_REQUIRE(A->ctx == ctx, "spmv_ilu0_order: the matrix belongs to another context");
+    SPMV_TRY(ilu0_check_handle(A, "spmv_ilu0_order"));
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    SPMV_TRY(ilu0_setup(const_cast<spmv_mat*>(A)));
+    return ilu0_sequence(A, order_host);
 }
 
 // ---- conversions ------------------------------------------------------------------------------------------

@@ -141,6 +141,7 @@ struct spmv_ctx
 namespace spmv
 {
 struct symgs_plan;
+struct ilu0_plan;
 struct transpose_state;
 // ---- plans (plan.hip): the decisions a handle's set-up made - by model or by timing - as plain data ------------------------------
 // One node per handle, children by index (the row-grouped copy of a COO / CSC / ELL handle or the short-row copy of a split,
@@ -352,6 +353,11 @@ struct spmv_mat
     struct spmv::symgs_plan* gs = nullptr;
     int32_t                  gs_order = 1;  // sweep order: 1 multicolour (default), 0 the matrix's own row order
 
+    // ILU(0) (ilu0.hip): the factors L and U in sweep order, rows by level, launch schedules; built by ilu0_setup, no part of the
+    // forward state (kernel, copies, plan) or of the transposed state
+    struct spmv::ilu0_plan* ilu = nullptr;
+    int32_t                 ilu_order = 1;  // "ilu0_order": 1 multicolour (default), 0 the matrix's own row order
+
     // the transposed product (transpose.hip): a companion handle of A^T over A's arrays, or the DIA transposed kernel's set-up;
     // built by spmv_mat_transpose_setup, no part of the forward state (kernel, copies, device_bytes, plan)
     struct spmv::transpose_state* tr            = nullptr;
@@ -460,7 +466,7 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
 // solver_cgls.hip: CGLS for min ||b - A x||^2 + damp^2 ||x||^2 over the forward and the transposed product of any handle
 int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                double damp, int* iters, double* rel_normal_resid, double* rel_resid);
-// solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle (precond: NONE, JACOBI)
+// solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle (precond: NONE, JACOBI, ILU0)
 int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                    int precond, int* iters, double* rel_resid);
 // kernels_ell.hip (what a product launches: ell_settings.hpp)
@@ -519,6 +525,14 @@ void symgs_free(spmv_mat* m);
 int  symgs_sweep(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, bool zero_guess);
 int  symgs_info(const spmv_mat* m, const char* what, int64_t* value);
 int  symgs_sequence(const spmv_mat* m, int32_t* out);
+// ilu0.hip: ILU(0) of a CSR handle in sweep order and its application z = U^-1 L^-1 r (SPMV_PRECOND_ILU0)
+int  ilu0_check_handle(const spmv_mat* m, const char* who);  // on the host: UNSUPPORTED (not CSR) / INVALID (a shard, not square, arrays released)
+int  ilu0_setup(spmv_mat* m);                                 // order, symbolic and numeric set-up (synchronous; once per handle and order)
+void ilu0_free(spmv_mat* m);
+int  ilu0_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z);  // asynchronous; r and z must not overlap
+int  ilu0_factor_values(const spmv_mat* m, double* out);      // aligned to the handle's own entries, to the host
+int  ilu0_sequence(const spmv_mat* m, int32_t* out);
+int  ilu0_info(const spmv_mat* m, const char* what, int64_t* value);
 // convert_sort.hip
 int sort_ids_by_key(spmv_ctx* ctx, const int32_t* keys, int64_t n, int bits, int32_t* out_ids);
 int coo_place_by_stable_sort(spmv_ctx* ctx, int64_t nnz, int32_t nrow, const int32_t* row, const int32_t* col, const double* val,

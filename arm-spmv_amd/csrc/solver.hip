@@ -373,6 +373,13 @@ int csr_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, int* de
     return SPMV_OK;
 }
 
+// z = M^-1 r for the preconditioners that are launch sequences of their own, between the product and the updates: one symmetric
+// Gauss-Seidel sweep from z = 0 (symgs.hip) or the two triangular solves of ILU(0) (ilu0.hip)
+static int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const double* r, double* z)
+{
+    return precond == SPMV_PRECOND_ILU0 ? ilu0_apply(ctx, A, r, z) : symgs_sweep(ctx, A, r, z, true);
+}
+
 int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
              int precond, int* iters, double* rel_resid)
 {
@@ -393,10 +400,11 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
         if (s) (void)hipFree(s);
         if (dinv) (void)hipFree(dinv);
     };
-    if (precond == SPMV_PRECOND_SYMGS)
+    if (precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0)
     {
-        // one symmetric Gauss-Seidel sweep from z = 0 per iteration (symgs.hip); the plan is built once and stays in the handle
-        SPMV_TRY(symgs_setup(const_cast<spmv_mat*>(A)));
+        // one symmetric Gauss-Seidel sweep from z = 0 per iteration (symgs.hip), or z = U^-1 L^-1 r with the ILU(0) factors (ilu0.hip:
+        // L U = L D L^T for a symmetric A); either state is built once and stays in the handle
+        SPMV_TRY(precond == SPMV_PRECOND_ILU0 ? ilu0_setup(const_cast<spmv_mat*>(A)) : symgs_setup(const_cast<spmv_mat*>(A)));
         if (hipMalloc(&z, sizeof(double) * (size_t)n) != hipSuccess)
             SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg: out of device memory for the preconditioned residual (%lld entries)", (long long)n);
     }
@@ -420,8 +428,8 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
         release();
         SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg: out of device memory for three work vectors of %lld entries", (long long)n);
     }
-    // Two launches per iteration (cg_fused_kernel) unless a sweep stands between the product and the updates (symmetric
-    // Gauss-Seidel) or SPMV_CG_THREE_LAUNCHES=1 asks for the textbook arrangement (A/B; read once per solve).
+    // Two launches per iteration (cg_fused_kernel) unless an application stands between the product and the updates (symmetric
+    // Gauss-Seidel, ILU(0)) or SPMV_CG_THREE_LAUNCHES=1 asks for the textbook arrangement (A/B; read once per solve).
     const char* e_three = getenv("SPMV_CG_THREE_LAUNCHES");
     const bool  fused   = !z && !(e_three && e_three[0] == '1');
     if (fused && (hipMalloc(&sv, sizeof(double) * (size_t)n) != hipSuccess || (dinv && hipMalloc(&u, sizeof(double) * (size_t)n) != hipSuccess)))
@@ -466,7 +474,7 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
         if (z)
         {
             // z_0 = M^-1 r_0, rz_0 = r_0 . z_0, p_0 = z_0
-            if ((rc = symgs_sweep(ctx, A, r, z, true)) != SPMV_OK) break;
+            if ((rc = apply_preconditioner(ctx, A, precond, r, z)) != SPMV_OK) break;
             if ((rc = vec_dot_accumulate(ctx, r, z, n, s->rz[0])) != SPMV_OK) break;
             if (hipMemcpyAsync(p, z, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess)
             {
@@ -546,7 +554,7 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
             if (z)
             {
                 SPMV_CG_UPDATE(Z::given, false, grid);
-                SPMV_TRY(symgs_sweep(ctx, A, r, z, true));
+                SPMV_TRY(apply_preconditioner(ctx, A, precond, r, z));
                 SPMV_TRY(vec_dot_accumulate(ctx, r, z, n, s->rz[(kk + 1) & 3]));
                 SPMV_CG_DIRECTION(Z::given, false, grid, z);
             }

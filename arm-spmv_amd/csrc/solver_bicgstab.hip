@@ -14,7 +14,10 @@
 //     p = r + beta (p - omega v);  rho = rho'
 //
 // M = I for SPMV_PRECOND_NONE: phat and shat are p and s themselves, no copies.  M = diag(A) of a CSR handle for
-// SPMV_PRECOND_JACOBI.  Right preconditioning: r is the residual of A x = b itself, so the stopping rule is on the true system.
+// SPMV_PRECOND_JACOBI.  M = L U, the ILU(0) factors of a CSR handle (ilu0.hip), for SPMV_PRECOND_ILU0: phat = M^-1 p and
+// shat = M^-1 s are two applications (ilu0_apply: the level launches of two triangular solves each) in front of the two products,
+// behind the plain flavours of the direction and half-step kernels; eight work vectors.  Right preconditioning: r is the
+// residual of A x = b itself, so the stopping rule is on the true system.
 //
 // Seven launches per iteration:
 //   1  mat_apply_ex              v = A phat (overwrite)
@@ -330,11 +333,12 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
     *rel_resid = 0.0;
     if (n == 0) return SPMV_OK;
     hipStream_t st  = ctx->stream;
-    const bool  pre = precond == SPMV_PRECOND_JACOBI;
-    // r, rhat, p, v, s, t (Jacobi: dinv, phat, shat) and the partial sums of two quantities: one allocation, every piece on a
+    const bool  pre = precond == SPMV_PRECOND_JACOBI, ilu = precond == SPMV_PRECOND_ILU0;
+    if (ilu) SPMV_TRY(ilu0_setup(const_cast<spmv_mat*>(A)));  // once per handle and order; stays in the handle
+    // r, rhat, p, v, s, t (Jacobi: dinv, phat, shat; ILU(0): phat, shat) and the partial sums of two quantities: one allocation, every piece on a
     // 256-byte boundary
     const size_t sn   = ((size_t)n + 31) & ~(size_t)31;
-    const int    nvec = pre ? 9 : 6;
+    const int    nvec = pre ? 9 : (ilu ? 8 : 6);
     double*      work = nullptr;
     BicgScalars* s    = nullptr;
     auto         release = [&]() {
@@ -347,7 +351,8 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
         SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_bicgstab: out of device memory for the work vectors (%d x %lld entries)", nvec, (long long)n);
     }
     double *r = work, *rhat = work + sn, *p = work + 2 * sn, *v = work + 3 * sn, *sv = work + 4 * sn, *t = work + 5 * sn;
-    double *dinv = pre ? work + 6 * sn : nullptr, *phat = pre ? work + 7 * sn : p, *shat = pre ? work + 8 * sn : sv;
+    double *dinv = pre ? work + 6 * sn : nullptr, *phat = pre ? work + 7 * sn : (ilu ? work + 6 * sn : p),
+           *shat = pre ? work + 8 * sn : (ilu ? work + 7 * sn : sv);
     double* part = work + (size_t)nvec * sn;
     if (pre)
     {
@@ -363,14 +368,17 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
     const int   grid_x = wide_x ? grid : stream_grid(n), grid_b = wide_b ? grid : stream_grid(n);
     apply_extra over;
     over.overwrite = true;
-    // the seven launches of an iteration
+    // the seven launches of an iteration (ILU(0): and the two applications phat = M^-1 p, shat = M^-1 s; in a quiet iteration they
+    // run on the p and s that stand, which the update kernel then does not read)
     auto iteration = [&]() -> int {
+        if (ilu) SPMV_TRY(ilu0_apply(ctx, A, p, phat));
         SPMV_TRY(mat_apply_ex(ctx, A, phat, v, over));
         hipLaunchKernelGGL(bicg_dot_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)rhat, (const double*)v, &s->rhv, part, s);
         if (pre)
             hipLaunchKernelGGL(bicg_half_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)r, (const double*)v, (const double*)dinv, sv, shat, s);
         else
             hipLaunchKernelGGL(bicg_half_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)r, (const double*)v, (const double*)dinv, sv, shat, s);
+        if (ilu) SPMV_TRY(ilu0_apply(ctx, A, sv, shat));
         SPMV_TRY(mat_apply_ex(ctx, A, shat, t, over));
         hipLaunchKernelGGL(bicg_dot_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)t, (const double*)sv, &s->ts, part, s);
         if (wide_x)

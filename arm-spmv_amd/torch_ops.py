@@ -68,7 +68,8 @@ class SparseOperator:
 
     def solve(self, b: torch.Tensor, x0: torch.Tensor | None = None, **kw) -> torch.Tensor:
         """x with A x = b for a square A by capi.Context.bicgstab from x0 (default 0), into a fresh tensor; kw: max_iter, rel_tol,
-        check_every, precond.  (iterations, residual) of the solve are left in self.last_solve.  No autograd through the solve"""
+        check_every, precond.  (iterations, residual) of the solve are left in self.last_solve.  No autograd through the solve.
+        precond=capi.PRECOND_ILU0 preconditions with the ILU(0) factors of a CSR operator (set up on the first solve)"""
         nrow, ncol = self.shape
         if nrow != ncol:
             raise ValueError(f"solve: the operator is {nrow} x {ncol}, not square (lstsq takes any shape)")

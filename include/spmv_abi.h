@@ -342,6 +342,7 @@ int spmv_mat_set_flags(spmv_mat* m, uint32_t flags);
  *                    built, 8 bytes per entry more.  Needs fewer than 2^31 - 131072 entries.  A row is spread over up to that
  *                    many runs, each ending in an atomic on y: results differ from the scan in place by rounding only.
  *   "symgs_order"    sweep order of spmv_symgs / SPMV_PRECOND_SYMGS: 1 multicolour (default), 0 the matrix's own row order
+ *   "ilu0_order"     sweep order of the ILU(0) factorisation (spmv_ilu0_setup / SPMV_PRECOND_ILU0), with the same meaning and default
  *   "panel_two_per_cu"   0 = never two workgroups per CU (default 1: two when their accumulators fit the LDS twice) */
 int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
 /* What is in effect: "panel_rows", "panel_width", "panel_sort", "panel_groups", "panel_layout", "panel_unroll",
@@ -359,7 +360,8 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
  * configuration that does not hold up there is dropped for the pieces as built, so never < 1000), "twophase_pieces_exchanged", "ell_diagonal_slots" (1: the slots of an ELL
  * handle were found to be diagonals and conforming rows read no column index), "symgs_order", "symgs_colours",
  * "symgs_levels_forward", "symgs_levels_backward", "symgs_launches", "symgs_bytes", "symgs_fused" (1: the colouring is proper and
- * the sweep takes one launch per colour). */
+ * the sweep takes one launch per colour), "ilu0_order", "ilu0_ready", "ilu0_colours", "ilu0_levels_forward", "ilu0_levels_backward",
+ * "ilu0_launches" (per application), "ilu0_bytes". */
 int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value);
 /* ---- plans: a handle's set-up decisions as plain data (plan.hip) ------------------------------------------------------------
  * AUTO is a measurement (spmv_mat_set_kernel above): which kernel a handle runs, in which layout, with which chunk size,
@@ -492,8 +494,10 @@ enum spmv_precond
 {
     SPMV_PRECOND_NONE   = 0,
     SPMV_PRECOND_JACOBI = 1, /* z = D^-1 r, D = diag(A) read from a CSR handle (zero diagonal: SPMV_ERR_INVALID) */
-    SPMV_PRECOND_SYMGS  = 2  /* z = one symmetric Gauss-Seidel sweep on A z = r from z = 0 (spmv_symgs below; the handle is
+    SPMV_PRECOND_SYMGS  = 2, /* z = one symmetric Gauss-Seidel sweep on A z = r from z = 0 (spmv_symgs below; the handle is
                                 set up on first use although it is passed as const) */
+    SPMV_PRECOND_ILU0   = 3  /* z = U^-1 L^-1 r with the ILU(0) factors of a CSR handle (spmv_ilu0_setup below; set up on first use
+                                in the same way).  spmv_cg and spmv_bicgstab; spmv_cg_multi: SPMV_ERR_UNSUPPORTED */
 };
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter,
             double rel_tol, int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
@@ -559,6 +563,8 @@ int spmv_cgls(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, 
  *   precond: SPMV_PRECOND_NONE (M = I: phat and shat are p and s, no copies) or SPMV_PRECOND_JACOBI (M = diag(A) of a CSR handle,
  *   duplicates summed; a zero or missing diagonal entry: SPMV_ERR_INVALID).  The preconditioner is applied on the right, so r is
  *   the residual of A x = b itself.  SPMV_PRECOND_SYMGS and Jacobi on a non-CSR handle: SPMV_ERR_UNSUPPORTED (out of scope here).
+ *   SPMV_PRECOND_ILU0 (M = L U of spmv_ilu0_setup; the handles that takes): phat and shat are two applications of spmv_ilu0_solve
+ *   behind the plain direction and half-step kernels, 7 launches plus twice "ilu0_launches" per iteration, eight work vectors.
  *   Seven launches per iteration (the two products, two dot kernels, three vector kernels); alpha, omega, beta, rho and the dots
  *   stay on the device; the host reads r.r and a status word every check_every iterations (>= 1) and after the last one.
  *   Stopping: r.r <= rel_tol^2 * b.b on the recurrence's r, or max_iter iterations.  *iters = iterations run, *rel_resid =
@@ -601,6 +607,36 @@ int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec*
 int spmv_symgs_setup(spmv_ctx* ctx, spmv_mat* A);
 int spmv_symgs_order(spmv_ctx* ctx, const spmv_mat* A, int32_t* order /* host, nrow entries */);
 int spmv_symgs(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t sweeps);
+/* ILU(0): the incomplete LU factorisation without fill of a CSR handle, computed on the device, and z = U^-1 L^-1 r by two
+ *   level-scheduled triangular solves (ilu0.hip).  A: a CSR handle that holds the whole square matrix and still has
+ *   its arrays; symmetric or not; every row needs a stored diagonal entry.
+ *   Definition.  pos[i] is the position of row i in the sweep order - spmv_mat_set_param "ilu0_order": 1 (default) the multicolour
+ *   order of spmv_symgs (the same greedy colouring, colour by colour, ascending row index inside a colour), 0 the matrix's own row
+ *   order.  The pattern P is the set of (i, j) with at least one stored entry; duplicates are summed first.  The factors are those
+ *   of the IKJ elimination restricted to P, rows taken in sweep order:  for k in row i with pos[k] < pos[i], ascending pos[k]:
+ *   l_ik = a_ik / u_kk;  for j in row k with pos[j] > pos[k] and (i, j) in P:  a_ij = fma(-l_ik, u_kj, a_ij);  then u_ij = a_ij for
+ *   pos[j] >= pos[i].  L is unit lower triangular in sweep order, U upper triangular with the diagonal.  Every entry receives its
+ *   subtractions in ascending pos[k]: two set-ups of one matrix give the same bits, and two applications the same z.
+ *   spmv_ilu0_setup: order, symbolic set-up (a working copy with every row sorted by pos and split into L, D, U; dependency levels
+ *   and launch schedules of both triangles) and the numeric factorisation, level by level.  Synchronous, idempotent; rebuilds when
+ *   "ilu0_order" changed since.  A row without a diagonal entry, or a pivot that is zero or not finite: SPMV_ERR_INVALID - the
+ *   message names the offending row with the smallest sweep position - and nothing is left in the handle.  SPMV_ERR_UNSUPPORTED
+ *   if a dependency chain exceeds 2^18 rows.  Re-factorising after the values of a wrapped handle changed is not offered.
+ *   spmv_ilu0_solve: z = U^-1 L^-1 r, asynchronous; vectors in the matrix's own numbering; r and z must not overlap.  Sets the
+ *   handle up on first use although it is passed as const.  One launch per large level, one workgroup per run of small levels.
+ *   spmv_ilu0_factors: the factor values aligned to the handle's own nnz entries, as an in-place csrilu0 would leave them: l_ik in
+ *   the entries of L, u_ij in the diagonal and upper ones; of a set of duplicates the first stored one carries the value, the
+ *   others hold 0.0.  spmv_ilu0_order: order[k] = the k-th row of the sweep (nrow entries).  Both set the handle up if need be.
+ *   Refused on the host, before any device use: a handle that is not CSR (SPMV_ERR_UNSUPPORTED); a shard or a non-square matrix, a
+ *   handle whose arrays were released (panel_keep_csr 0), null pointers, vectors of other than nrow entries, another context's
+ *   handle (SPMV_ERR_INVALID).  nrow = 0: SPMV_OK, nothing is launched.
+ *   The state lives in the handle (spmv_mat_get_param "ilu0_ready", "ilu0_colours", "ilu0_levels_forward", "ilu0_levels_backward",
+ *   "ilu0_launches" per application, "ilu0_bytes", "ilu0_order"), is counted in device_bytes and freed with the handle; the forward
+ *   kernel, the copies, the transposed state and the plan stay as they were. */
+int spmv_ilu0_setup(spmv_ctx* ctx, spmv_mat* A);
+int spmv_ilu0_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z);
+int spmv_ilu0_factors(spmv_ctx* ctx, const spmv_mat* A, double* values_host /* nnz entries */);
+int spmv_ilu0_order(spmv_ctx* ctx, const spmv_mat* A, int32_t* order_host /* nrow entries */);
 
 /* ---- format conversion on the device (src/matrix.cpp:115-154, :450-500) -------------------------- */
 /* Both keep the COO order of the entries inside each row (stable), like the reference's backward
