@@ -104,6 +104,7 @@ SIGNATURES = {
     "spmv_cg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_cgls": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_double, C.POINTER(C.c_int32), _f64p, _f64p]),
     "spmv_bicgstab": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
+    "spmv_gmres": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_symgs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32]),
     "spmv_symgs_setup": (C.c_int, [_vp, _vp]),
     "spmv_symgs_order": (C.c_int, [_vp, _vp, _i32p]),
@@ -501,6 +502,17 @@ class Context:
         Stops at ||r|| <= rel_tol * ||b||; returns (iterations, ||r|| / ||b||)"""
         it, res = C.c_int32(0), C.c_double(0.0)
         _check(self._lib.spmv_bicgstab(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def gmres(self, A: "Matrix", b: "Vector", x: "Vector", restart: int = 30, max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
+              precond: int = 0):
+        """A x = b for a square, not necessarily symmetric A by right-preconditioned restarted GMRES(restart) on the device, from the x
+        passed in: any format, one forward product and one preconditioner application per iteration, classical Gram-Schmidt twice
+        against a basis of restart + 1 work vectors (restart: 1 .. 64; 0: 30).  precond: PRECOND_NONE, or PRECOND_JACOBI or
+        PRECOND_ILU0 (the ILU(0) factors, set up on first use) on a CSR handle.  Does not break down where BiCGSTAB does; stagnation
+        (GMRES(1) on a rotation) is no error.  Stops at ||r|| <= rel_tol * ||b||; returns (iterations, ||r|| / ||b||)"""
+        it, res = C.c_int32(0), C.c_double(0.0)
+        _check(self._lib.spmv_gmres(self.h, A.h, b.h, x.h, restart, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))
         return it.value, res.value
 
     def coo_to_csr(self, coo: "Matrix") -> "Matrix":

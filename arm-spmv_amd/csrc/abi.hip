@@ -1381,6 +1381,35 @@ int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec*
     return bicgstab_solve(ctx, A, b->d, x->d, max_iter, rel_tol, check_every, precond, iters, rel_resid);
 }
 
+// nonsymmetric square systems by restarted GMRES over one forward product per iteration (solver_gmres.hip).  Every check is made
+// before the device is touched.
+int spmv_gmres(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t restart, int32_t max_iter, double rel_tol,
+               int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
+{
+    SPMV_REQUIRE(ctx && A && b && x && iters && rel_resid, "spmv_gmres: null argument");
+    SPMV_REQUIRE(A->nrow == A->ncol, "spmv_gmres: the matrix (shard) is %d x %d, not square", A->nrow, A->ncol);
+    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "spmv_gmres: b has %lld and x %lld entries, the matrix %d rows", (long long)b->n,
+                 (long long)x->n, A->nrow);
+    SPMV_REQUIRE(b->n == 0 || b->d + b->n <= x->d || x->d + x->n <= b->d, "spmv_gmres: b and x must not overlap");
+    SPMV_REQUIRE(restart >= 0 && restart <= 64, "spmv_gmres: restart=%d, must be 1 .. 64 (0: 30)", restart);
+    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_gmres: max_iter=%d rel_tol=%g", max_iter, rel_tol);
+    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
+                 "spmv_gmres: unknown preconditioner %d", precond);
+    if (precond == SPMV_PRECOND_SYMGS)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_gmres: the symmetric Gauss-Seidel preconditioner is not built for this solver");
+    if (precond == SPMV_PRECOND_JACOBI && A->format != SPMV_FMT_CSR)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_gmres: the Jacobi preconditioner reads the diagonal of a CSR handle");
+    if (precond == SPMV_PRECOND_ILU0) SPMV_TRY(ilu0_check_handle(A, "spmv_gmres"));
+    // Jacobi reads the handle's own arrays; the plain solve needs the forward product alone and takes such a handle
+    SPMV_REQUIRE(!(precond == SPMV_PRECOND_JACOBI && A->nnz > 0 && (!A->b || !A->v)),
+                 "spmv_gmres: this handle gave up its CSR arrays (panel_keep_csr = 0): no diagonal for the Jacobi preconditioner");
+    *iters     = 0;
+    *rel_resid = 0.0;
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return gmres_solve(ctx, A, b->d, x->d, restart == 0 ? 30 : restart, max_iter, rel_tol, check_every, precond, iters, rel_resid);
+}
+
 int spmv_symgs_setup(spmv_ctx* ctx, spmv_mat* A)
 {
     SPMV_REQUIRE(ctx && A, "spmv_symgs_setup: null argument");

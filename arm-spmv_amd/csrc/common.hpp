@@ -469,6 +469,10 @@ int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int
 // solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle (precond: NONE, JACOBI, ILU0)
 int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                    int precond, int* iters, double* rel_resid);
+// solver_gmres.hip: right-preconditioned restarted GMRES(restart) for square A over one forward product of any handle per iteration
+// (restart: 1 .. 64; precond: NONE, JACOBI, ILU0)
+int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int restart, int max_iter, double rel_tol, int check_every,
+                int precond, int* iters, double* rel_resid);
 // kernels_ell.hip (what a product launches: ell_settings.hpp)
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int ell_analyse(spmv_mat* m);

@@ -66,10 +66,15 @@ class SparseOperator:
         return x
 
 
-    def solve(self, b: torch.Tensor, x0: torch.Tensor | None = None, **kw) -> torch.Tensor:
-        """x with A x = b for a square A by capi.Context.bicgstab from x0 (default 0), into a fresh tensor; kw: max_iter, rel_tol,
-        check_every, precond.  (iterations, residual) of the solve are left in self.last_solve.  No autograd through the solve.
+    def solve(self, b: torch.Tensor, x0: torch.Tensor | None = None, method: str = "bicgstab", **kw) -> torch.Tensor:
+        """x with A x = b for a square A from x0 (default 0), into a fresh tensor, by capi.Context.bicgstab (method="bicgstab", the
+        default) or capi.Context.gmres (method="gmres"; kw: restart as well); kw: max_iter, rel_tol, check_every, precond.
+        (iterations, residual) of the solve are left in self.last_solve.  No autograd through the solve.
         precond=capi.PRECOND_ILU0 preconditions with the ILU(0) factors of a CSR operator (set up on the first solve)"""
+        if method not in ("bicgstab", "gmres"):
+            raise ValueError(f"solve: method {method!r}, expected 'bicgstab' or 'gmres'")
+        if method == "bicgstab" and "restart" in kw:
+            raise ValueError("solve: restart belongs to method='gmres'")
         nrow, ncol = self.shape
         if nrow != ncol:
             raise ValueError(f"solve: the operator is {nrow} x {ncol}, not square (lstsq takes any shape)")
@@ -79,7 +84,8 @@ class SparseOperator:
         else:
             self._check(x0, ncol, "solve x0")
             x = x0.detach().clone()
-        self.last_solve = self.ctx.bicgstab(self.A, self.ctx.wrap_vector(b.detach()), self.ctx.wrap_vector(x), **kw)
+        run = self.ctx.gmres if method == "gmres" else self.ctx.bicgstab
+        self.last_solve = run(self.A, self.ctx.wrap_vector(b.detach()), self.ctx.wrap_vector(x), **kw)
         return x
 
 class _SpMV(torch.autograd.Function):

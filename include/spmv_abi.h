@@ -497,7 +497,7 @@ enum spmv_precond
     SPMV_PRECOND_SYMGS  = 2, /* z = one symmetric Gauss-Seidel sweep on A z = r from z = 0 (spmv_symgs below; the handle is
                                 set up on first use although it is passed as const) */
     SPMV_PRECOND_ILU0   = 3  /* z = U^-1 L^-1 r with the ILU(0) factors of a CSR handle (spmv_ilu0_setup below; set up on first use
-                                in the same way).  spmv_cg and spmv_bicgstab; spmv_cg_multi: SPMV_ERR_UNSUPPORTED */
+                                in the same way).  spmv_cg, spmv_bicgstab and spmv_gmres; spmv_cg_multi: SPMV_ERR_UNSUPPORTED */
 };
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter,
             double rel_tol, int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
@@ -585,6 +585,46 @@ int spmv_cgls(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, 
  *   on every path. */
 int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
                   int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
+/* spmv_gmres: A x = b for a square A that need not be symmetric, by right-preconditioned restarted GMRES(restart), starting from the
+ *   x passed in (solver_gmres.hip).  b and x have nrow entries.  A is any handle spmv_bicgstab takes: all five formats,
+ *   uploaded, wrapped, or a shard that holds a square matrix.  Synchronous.  One forward product through the handle's own kernel and
+ *   one preconditioner application per iteration (spmv_bicgstab: two of each); no transposed state is built, and the handle's kernel,
+ *   copies, device_bytes and plan stay as they were.  It does not break down where BiCGSTAB does (the rotation [[0, 1], [-1, 0]]).
+ *   restart = m: 1 .. 64; 0 means 30; anything else is SPMV_ERR_INVALID.
+ *   Recurrence:  r = b - A x;  beta = ||r||;  v_0 = r / beta;  g = (beta, 0, ...);  then for column j = 0 .. m-1 of a cycle
+ *   z = M^-1 v_j;  w = A z;  twice (classical Gram-Schmidt): c_i = v_i . w for i = 0..j, all against the same w, w -= sum_i c_i v_i,
+ *   h_i += c_i;  h_{j+1} = ||w||;  v_{j+1} = w / h_{j+1};  the rotations 0..j-1 applied to h;  d = sqrt(h_j^2 + h_{j+1}^2);
+ *   (cs_j, sn_j) = (h_j, h_{j+1}) / d;  h_j = d;  g_{j+1} = -sn_j g_j;  g_j = cs_j g_j.  The recurrence's residual is |g_{j+1}|.  A
+ *   cycle ends at j = m, at a stop, at max_iter or when it landed:  y = R^-1 g;  x += M^-1 (sum_i y_i v_i);  and if the solve goes on,
+ *   r = b - A x is computed again.
+ *   precond: spmv_bicgstab's set with the same codes - SPMV_PRECOND_NONE (z is v_j, no copy), SPMV_PRECOND_JACOBI (M = diag(A) of a
+ *   CSR handle, duplicates summed; a zero or missing diagonal entry: SPMV_ERR_INVALID), SPMV_PRECOND_ILU0 (M = L U of
+ *   spmv_ilu0_setup; the handles that takes; one application per iteration and one at a cycle's end); SPMV_PRECOND_SYMGS and Jacobi
+ *   on a non-CSR handle: SPMV_ERR_UNSUPPORTED.  The preconditioner is applied on the right, so r is the residual of A x = b itself.
+ *   Six launches per iteration (the product, two dots kernels that take all j + 1 dots of a pass in one sweep, two updates, the
+ *   normalisation; ILU(0): and "ilu0_launches"); R, cs, sn, g and y stay on the device; the host reads the residual, the column count
+ *   and a status word every check_every iterations (>= 1), after the last one and behind every restart.
+ *   Stopping: |g_{j+1}| <= rel_tol * ||b|| at a look; behind a restart the recomputed ||r|| is compared instead; or max_iter
+ *   iterations.  *iters = iterations run, *rel_resid = that ratio at the last look.  max_iter = k with rel_tol = 0 runs exactly k
+ *   iterations and leaves the GMRES iterate x_k, formed from the columns that stand, in x.  b.b = 0: *iters = 0, *rel_resid = 0, x
+ *   untouched.  A start within the tolerance, or max_iter = 0: no iteration, *rel_resid is that of x0.  An iteration that starts with
+ *   |g_j| at or below 1e-14 ||b|| passes quietly (its kernels write nothing: no vector is divided by a norm that is rounding noise;
+ *   h_{j+1} = 0, the lucky breakdown, is such a case); the host ends the cycle at its next look with the columns that stand, and an
+ *   exact 0 ends the solve.  Stagnation is no error: GMRES(1) on the rotation keeps |g| = ||b|| until max_iter and returns SPMV_OK.
+ *   Breakdown - d = 0 (at or below 2^-44 times the norm of the new column) while the residual is above that floor: the Krylov space
+ *   is exhausted and A is singular - or a non-finite b.b, beta, h or g: SPMV_ERR_INVALID, and spmv_last_error() names the quantity
+ *   and "at or before iteration k"; x then holds the iterate of the last completed cycle.
+ *   Refused before any device use with SPMV_ERR_INVALID: null pointers, nrow != ncol, b or x with other than nrow entries, b and x
+ *   overlapping, restart outside 0 .. 64, max_iter < 0, rel_tol < 0, an unknown precond, Jacobi on a CSR handle without its arrays
+ *   (panel_keep_csr 0; the plain solve takes such a handle).  nrow = 0: SPMV_OK, *iters = 0, nothing is launched.
+ *   Deterministic dot products (per-workgroup partial sums per dot, added in a fixed order by the workgroup that finishes last): a
+ *   solve is exactly as reproducible as the product its handle runs.  x and b need only be 8-byte aligned; where they are 16-byte
+ *   aligned the vector kernels use 16-byte accesses on them.
+ *   Device memory: restart + 2 work vectors of nrow doubles (ILU(0): + 3, Jacobi: + 4), the partial sums of restart + 2 quantities
+ *   and a 36 KB block for the small problem for the duration of the call, released on every path; running out is SPMV_ERR_ALLOC with
+ *   the size in the message. */
+int spmv_gmres(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t restart, int32_t max_iter, double rel_tol,
+               int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
 /* spmv_symgs: `sweeps` symmetric Gauss-Seidel sweeps on A*x = b, x updated in place: forward over the rows in sweep
  *   order with the newest x, then backward — the sweep the reference's `diagonal // for SymGS` fields were reserved
  *   for (include/matrix.h:36,81) and that it never wrote.  A: CSR handle holding the whole square matrix with a non-zero

@@ -1,0 +1,527 @@
+"""spmv_gmres - restarted GMRES over one forward product per iteration - iterate by iterate against the extended-precision
+recurrence (`pytest -m gpu`).
+
+spmv_gmres(max_iter = k, rel_tol = 0) runs exactly k iterations from the x passed in and leaves the GMRES iterate formed from the
+columns that stand.  For the k of (1, 2, 3, 4, 5, 8, 9, 13) that the drop rule of tests/bicgstab_ref.py leaves, under m = 4 (restarts
+inside 13 iterations) and m = 30 (none), with the host looking every iteration and every fourth, x_k and the returned
+|g_{j+1}| / ||b|| are held to right-preconditioned GMRES(m) with classical Gram-Schmidt twice in np.longdouble (tests/gmres_ref.py).
+The gate at step k is F = 8 times the largest deviation from that reference of any float64 twin of the recurrence (three dot
+orders x two orders of a row's products), measured on the reference's own arithmetic and floored at 2^-50.  What the gate catches -
+old rotations not applied, y from the unrotated g, a column left out, a restart that keeps v_m, M^-1 on the wrong side or
+missing, an element of x left out - is checked on the CPU in tests/test_gmres_ref.py.
+
+Problems: 1 x 1, 2 x 2, 3 x 3 dense; 33 x 33 and 4097 x 4097 random with a dominant diagonal; a 4099 x 4099 band of seven diagonals;
+one whose size is odd and beyond two sweeps of the vector kernels' largest grid (csrc/common.hpp: 2 * kMaxGrid * kBlock); and the
+wide basis, a 4099-row tridiagonal matrix far from converged after 66 iterations, at m = 64 (k = 16, 17, 33: the edges of the dots
+kernel's tiles of 8 vectors; 64, 65, 66: a full basis and the restart behind it), m = 8 and m = 1.  CSR under AUTO, plain and with
+Jacobi, and forced VECTOR, SCALAR and PANEL; COO (entries shuffled), CSC, ELL and DIA handles of the band; x and b 256-byte aligned
+(the 16-byte kernels) and 8 bytes past a 16-byte boundary (the 8-byte kernels); a random start and x0 = 0.  Then the rotation that
+breaks BiCGSTAB down, the stopping rules and special cases, refusals, convergence to 1e-10 against the true residual, ILU(0) in
+both orders against the twins' iteration counts, reproducibility bit for bit, the handle's state and the device memory before and
+after, and the torch operator.  test_every_case_ran asserts at the end that all of it ran; with SPMV_GMRES_RATIOS=<file> it also
+writes the largest GPU deviation over twin envelope per problem (profiles/gmres_steps_gpu_vs_twin_envelope.txt).
+"""
+import collections
+import os
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import gmres_ref as gr
+import ilu0_ref as ir
+import oracle_lib as ol
+
+pytestmark = pytest.mark.gpu
+AUTO, VECTOR, SCALAR, PANEL = 0, 1, 3, 4
+NONE, JACOBI, SYMGS, ILU0 = 0, 1, 2, 3
+INVALID, UNSUPPORTED = -1, -5
+CHECK_EVERY = (1, 4)
+PRECOND_NAME = {NONE: None, JACOBI: "jacobi"}
+ALL_PROBLEMS = gr.PROBLEMS + (gr.WIDE,)
+RUNS = collections.Counter()
+RATIO = {}  # problem -> {"x" | "residual": (largest deviation / twin envelope, where)}
+_MAT = {}
+_ENV = {}
+
+
+def _grid_constants():
+    """kBlock and kMaxGrid as csrc/common.hpp defines them"""
+    text = (Path(__file__).resolve().parent.parent / "arm-spmv_amd" / "csrc" / "common.hpp").read_text()
+    vals = {}
+    for name, expr in re.findall(r"constexpr int (k\w+)\s*=\s*([^;]+);", text):
+        try:
+            vals[name] = int(eval(expr, {"__builtins__": {}}, dict(vals)))
+        except Exception:
+            pass
+    return vals["kBlock"], vals["kMaxGrid"]
+
+
+def _big_n():
+    block, max_grid = _grid_constants()
+    return 2 * max_grid * block + 2051  # odd, and beyond two sweeps of the one- and of the two-element grids
+
+
+def _problem(name):
+    if name not in _MAT:
+        n, ent, b, x0, ks = gr.problem(name, _big_n() if name == "big" else None)
+        _MAT[name] = (n, ent, b, x0, ks, gr.csr_arrays(n, *ent))
+    return _MAT[name]
+
+
+def _ks(name, m):
+    if name == gr.WIDE:
+        return gr.WIDE_KS[m]
+    ks = _problem(name)[4]
+    return tuple(k for k in ks if k <= 5) if name == "big" else ks
+
+
+def _envelope(name, m, precond, zero_start=False):
+    """the reference iterates and twin envelopes of one problem under GMRES(m) (computed once and shared)"""
+    key = (name, m, precond, zero_start)
+    if key not in _ENV:
+        n, ent, b, x0, _, _ = _problem(name)
+        why = gr.available(n)
+        if why:
+            pytest.skip(why)
+        _ENV[key] = gr.Envelope(ent, n, b, np.zeros_like(x0) if zero_start else x0, _ks(name, m), m, PRECOND_NAME[precond])
+    return _ENV[key]
+
+
+def _device_vector(ctx, host, aligned):
+    """host on the device, 256-byte aligned (spmv_vec_create) or 8 bytes past a 16-byte boundary (a wrapped pointer into a vector
+    of n + 1: an ordinary, legal double*)"""
+    n = len(host)
+    if aligned:
+        v = ctx.vector_from(host)
+        assert v.device_ptr % 16 == 0
+        return v, None
+    base = ctx.vector(n + 1)
+    base.fill(0.0)
+    ptr = base.device_ptr + 8
+    assert ptr % 16 == 8
+    v = ctx.wrap_vector(ptr, n)
+    v.upload(host)
+    return v, base
+
+
+def _note(name, kind, ratio, where):
+    old = RATIO.setdefault(name, {})
+    if kind not in old or ratio > old[kind][0]:
+        old[kind] = (ratio, where)
+
+
+def _steps(ctx, A, name, m, precond, aligned, what, zero_start=False):
+    """every k the problem keeps with check_every 1 and 4: iters, x_k and the residual against the reference"""
+    n, ent, b, x0, _, _ = _problem(name)
+    env = _envelope(name, m, precond, zero_start)
+    start = np.zeros_like(x0) if zero_start else x0
+    db, keep_b = _device_vector(ctx, b, aligned)
+    misses = []
+    for k in env.ks:
+        for check_every in CHECK_EVERY:
+            x, keep_x = _device_vector(ctx, start, aligned)
+            iters, res = ctx.gmres(A, db, x, restart=m, max_iter=k, rel_tol=0.0, check_every=check_every, precond=precond)
+            got = x.download()
+            del x, keep_x
+            tag = f"{name} {what} m={m} precond={precond} {'aligned' if aligned else 'offset'}{' x0=0' if zero_start else ''} k={k} check_every={check_every}"
+            assert iters == k, (tag, iters)
+            dev, rdev = env.x_dev(k, got), env.resid_dev(k, res)
+            print(f"{tag}: x deviation {dev:.2e} (twins {env.envelope(k):.2e}, gate {env.gate(k):.2e}); residual {res:.6e} deviation {rdev:.2e} "
+                  f"(gate {env.gate_resid(k):.2e})")
+            _note(name, "x", dev / env.envelope(k), tag)
+            _note(name, "residual", rdev / env.envelope(k, 1), tag)
+            if not dev <= env.gate(k):
+                misses.append(f"{tag}: max|x_k - ref_k| / max|ref_k| = {dev:.3e} > gate {env.gate(k):.3e}")
+            if not rdev <= env.gate_resid(k):
+                misses.append(f"{tag}: rel_resid {res!r} against {env.ref_resid[k]!r}: {rdev:.3e} > gate {env.gate_resid(k):.3e}")
+    del db, keep_b
+    return misses
+
+
+def _csr(ctx, name):
+    n, _, _, _, _, (rp, cc, cv) = _problem(name)
+    return ctx.csr(n, n, rp, cc, cv)
+
+
+# ---- 1. every problem as a CSR handle under AUTO: m = 4 and m = 30, both alignments, plain and Jacobi, both starts ----------------------
+CSR_CASES = [(name, m, precond) for name in gr.PROBLEMS[:-1] for m in gr.RESTARTS for precond in (NONE, JACOBI)] + [("big", 4, JACOBI)]
+
+
+@pytest.mark.parametrize("name,m,precond", CSR_CASES, ids=lambda v: str(v))
+def test_gmres_iterates_match_the_extended_precision_recurrence(ctx, pkg, name, m, precond):
+    A = _csr(ctx, name)
+    misses = []
+    if name == "big":
+        misses += _steps(ctx, A, name, m, precond, False, "csr auto")
+    else:
+        for aligned in (True, False):
+            for zero_start in (False, True):
+                misses += _steps(ctx, A, name, m, precond, aligned, "csr auto", zero_start)
+    assert not misses, "\n".join(misses)
+    RUNS["csr"] += 1
+
+
+# ---- 2. the wide basis ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("m", sorted(gr.WIDE_KS))
+def test_gmres_iterates_with_a_wide_basis(ctx, pkg, m):
+    A = _csr(ctx, gr.WIDE)
+    misses = []
+    for aligned in (True, False):
+        misses += _steps(ctx, A, gr.WIDE, m, NONE, aligned, "csr auto")
+    assert not misses, "\n".join(misses)
+    RUNS["wide"] += 1
+
+
+# ---- 3. forced product kernels and the other formats -----------------------------------------------------------------------------------
+KERNEL_CASES = [("r4097", label, kid) for label, kid in (("vector", VECTOR), ("scalar", SCALAR), ("panel", PANEL))]
+
+
+@pytest.mark.parametrize("name,label,kid", KERNEL_CASES, ids=lambda v: str(v))
+def test_gmres_iterates_under_forced_csr_kernels(ctx, pkg, name, label, kid):
+    A = _csr(ctx, name)
+    A.set_kernel(kid)
+    assert A.info.kernel == kid
+    misses = []
+    for m in gr.RESTARTS:
+        for precond, aligned in ((NONE, False), (JACOBI, True)):
+            misses += _steps(ctx, A, name, m, precond, aligned, f"csr {label}")
+    assert not misses, "\n".join(misses)
+    assert A.info.kernel == kid
+    RUNS["kernels"] += 1
+
+
+def _band_handle(ctx, orc, fmt):
+    n, (row, col, val), _, _, _, (rp, cc, cv) = _problem("band4099")
+    if fmt == "csr":
+        return ctx.csr(n, n, rp, cc, cv)
+    if fmt == "coo":
+        o = np.random.default_rng(5).permutation(len(row))
+        return ctx.coo(n, n, ol.i32(row[o]), ol.i32(col[o]), ol.f64(val[o]))
+    if fmt == "csc":
+        cp, cri, ccv = ol.coo_to_csc(orc, n, ol.i32(row), ol.i32(col), ol.f64(val))
+        return ctx.csc(n, n, cp, cri, ccv)
+    if fmt == "ell":
+        k, ec, ev = ol.coo_to_ell(orc, n, ol.i32(row), ol.i32(col), ol.f64(val))
+        return ctx.ell(n, n, k, len(val), ec, ev)
+    offsets, dval = ol.csr_to_dia(orc, n, n, rp, cc, cv)
+    assert len(offsets) == len(gr.br.BAND_OFFSETS)
+    return ctx.dia(n, n, offsets, dval)
+
+
+FORMATS = ("coo", "csc", "ell", "dia")
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_gmres_iterates_on_every_format(ctx, orc, pkg, fmt):
+    A = _band_handle(ctx, orc, fmt)
+    misses = []
+    for m, aligned in ((4, True), (30, False)):
+        misses += _steps(ctx, A, "band4099", m, NONE, aligned, fmt)
+    assert not misses, "\n".join(misses)
+    RUNS["formats"] += 1
+
+
+# ---- 4. the rotation --------------------------------------------------------------------------------------------------------------------
+def test_gmres_solves_the_rotation_bicgstab_breaks_down_on(ctx, pkg):
+    capi = pkg.capi
+    rot_ent = (np.array([0, 1]), np.array([1, 0]), np.array([1.0, -1.0]))
+    rot = ctx.csr(2, 2, np.array([0, 1, 2], np.int32), np.array([1, 0], np.int32), np.array([1.0, -1.0]))
+    b = np.array([1.0, 2.0])
+    db = ctx.vector_from(b)
+    x = ctx.vector_from(np.zeros(2))
+    with pytest.raises(capi.SpmvError) as e:
+        ctx.bicgstab(rot, db, x)
+    assert e.value.code == INVALID and "rhat.v" in str(e.value), e.value
+    # GMRES(30): two iterations, x = A^-1 b = (-2, 1)
+    env = gr.Envelope(rot_ent, 2, b, np.zeros(2), (2,), 30)  # (x_1 is 0: nothing to measure a relative deviation against)
+    assert env.ks == (2,) and np.allclose(np.asarray(env.ref_x[2], dtype=np.float64), [-2.0, 1.0], rtol=0, atol=1e-15)
+    x = ctx.vector_from(np.zeros(2))
+    iters, res = ctx.gmres(rot, db, x, restart=30)
+    got = x.download()
+    print(f"rotation m=30: {iters} iterations, residual {res:.3e}, x = {got!r} (deviation {env.x_dev(2, got):.2e}, gate {env.gate(2):.2e})")
+    assert iters == 2 and res <= 1e-8, (iters, res)
+    assert env.x_dev(2, got) <= env.gate(2), (got, env.gate(2))
+    # GMRES(1) stagnates: |g| stays ||b||, no error, x stays
+    with np.errstate(invalid="ignore"):  # (the reference's x_6 is 0: the twins' relative deviation of x is 0 / 0, and is not used)
+        env1 = gr.Envelope(rot_ent, 2, b, np.zeros(2), (6,), 1)
+    assert env1.ref_resid[6] == 1.0
+    x = ctx.vector_from(np.zeros(2))
+    iters, res = ctx.gmres(rot, db, x, restart=1, max_iter=6)
+    print(f"rotation m=1: {iters} iterations, residual {res!r} (deviation {env1.resid_dev(6, res):.2e}, gate {env1.gate_resid(6):.2e})")
+    assert iters == 6 and env1.resid_dev(6, res) <= env1.gate_resid(6), (iters, res)
+    assert np.max(np.abs(x.download())) <= gr.F * gr.FLOOR * 2.0, "GMRES(1) on the rotation moved x (the reference's x_6 is 0)"
+    RUNS["rotation"] += 1
+
+
+# ---- 5. stopping rules and special cases -------------------------------------------------------------------------------------------------
+def test_stopping_rules_and_special_cases(ctx, pkg):
+    capi = pkg.capi
+    name = "r33"
+    n, ent, b, x0, ks, _ = _problem(name)
+    A = _csr(ctx, name)
+    for aligned in (True, False):
+        # b = 0: nothing to do, x stays
+        db, kb = _device_vector(ctx, np.zeros(n), aligned)
+        x, kx = _device_vector(ctx, x0, aligned)
+        assert ctx.gmres(A, db, x, max_iter=50, precond=JACOBI) == (0, 0.0)
+        assert x.download().tobytes() == x0.tobytes(), "b = 0: x was written"
+        # max_iter = 0: x stays, the residual is that of x0
+        db, kb = _device_vector(ctx, b, aligned)
+        for precond in (NONE, JACOBI):
+            env0 = gr.Envelope(ent, n, b, x0, (0,), 30, PRECOND_NAME[precond])
+            iters, res = ctx.gmres(A, db, x, max_iter=0, rel_tol=0.0, precond=precond)
+            assert iters == 0 and x.download().tobytes() == x0.tobytes()
+            assert env0.resid_dev(0, res) <= env0.gate_resid(0), (res, env0.ref_resid)
+        # a start that is already within the tolerance: no iteration either
+        iters, res = ctx.gmres(A, db, x, max_iter=50, rel_tol=1e3)
+        assert iters == 0 and x.download().tobytes() == x0.tobytes() and 0.0 < res <= 1e3
+        del db, kb, x, kx
+    # the lucky breakdown: the 5 x 5 identity from x0 = 0 ends after one iteration with x = b up to the rounding of b / beta * beta
+    eye = ctx.csr(5, 5, np.arange(6, dtype=np.int32), np.arange(5, dtype=np.int32), np.ones(5))
+    bd = np.array([0.5, -1.25, 2.0, 0.75, -3.0])
+    x = ctx.vector_from(np.zeros(5))
+    iters, res = ctx.gmres(eye, ctx.vector_from(bd), x)
+    assert iters == 1 and res <= 1e-15, (iters, res)
+    assert np.max(np.abs(x.download() - bd)) <= 8 * 2.0**-50 * 3.0
+    # ... and with max_iter beyond it and rel_tol = 0 the later iterations pass quietly: x stays what iteration 1 left
+    x2 = ctx.vector_from(np.zeros(5))
+    iters, res = ctx.gmres(eye, ctx.vector_from(bd), x2, max_iter=7, rel_tol=0.0, check_every=4)
+    assert iters <= 7 and res <= 1e-15 and np.max(np.abs(x2.download() - bd)) <= 8 * 2.0**-50 * 3.0, (iters, res, x2.download())
+    # the singular breakdown: the Krylov space of ([[0, 0], [0, 1]], (1, 1)) is exhausted at iteration 2 and b is not in its image
+    sing = ctx.csr(2, 2, np.array([0, 0, 1], np.int32), np.array([1], np.int32), np.array([1.0]))
+    x = ctx.vector_from(np.zeros(2))
+    with pytest.raises(capi.SpmvError) as e:
+        ctx.gmres(sing, ctx.vector_from(np.array([1.0, 1.0])), x)
+    msg = str(e.value)
+    assert e.value.code == INVALID and "spmv_gmres" in msg and "breakdown" in msg and "d = sqrt" in msg and "iteration 2" in msg, e.value
+    assert x.download().tobytes() == np.zeros(2).tobytes(), "x is not the iterate of the last completed cycle"
+    # a NaN in b: read by the host in b.b, an error and no fault
+    bn = b.copy()
+    bn[7] = np.nan
+    with pytest.raises(capi.SpmvError) as e:
+        ctx.gmres(A, ctx.vector_from(bn), ctx.vector_from(x0), max_iter=5)
+    assert e.value.code == INVALID and "spmv_gmres" in str(e.value) and "b.b" in str(e.value), e.value
+    # an empty matrix: nothing is launched
+    E = ctx.csr(0, 0, np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0))
+    assert ctx.gmres(E, ctx.vector(0), ctx.vector(0), max_iter=5) == (0, 0.0)
+    RUNS["stopping"] += 1
+
+
+def test_refusals_are_made_on_the_host(ctx, orc, pkg):
+    capi = pkg.capi
+    n, ent, b, x0, ks, _ = _problem("r33")
+    A = _csr(ctx, "r33")
+    db, dx = ctx.vector_from(b), ctx.vector_from(x0)
+
+    def expect(fn, word="spmv_gmres", code=INVALID):
+        with pytest.raises(capi.SpmvError) as e:
+            fn()
+        assert e.value.code == code and "spmv_gmres" in str(e.value) and word in str(e.value), e.value
+
+    expect(lambda: ctx.gmres(A, ctx.vector(n + 1), dx))
+    expect(lambda: ctx.gmres(A, db, ctx.vector(n - 1)))
+    big = ctx.vector(3 * n)
+    expect(lambda: ctx.gmres(A, ctx.wrap_vector(big.device_ptr, n), ctx.wrap_vector(big.device_ptr + 8 * 5, n)), "overlap")
+    expect(lambda: ctx.gmres(A, db, dx, restart=65), "restart")
+    expect(lambda: ctx.gmres(A, db, dx, restart=-1), "restart")
+    expect(lambda: ctx.gmres(A, db, dx, max_iter=-1))
+    expect(lambda: ctx.gmres(A, db, dx, rel_tol=-1e-8))
+    expect(lambda: ctx.gmres(A, db, dx, precond=7), "unknown preconditioner")
+    expect(lambda: ctx.gmres(A, db, dx, precond=SYMGS), "Gauss-Seidel", UNSUPPORTED)
+    rp, cc, cv = gr.csr_arrays(33, *gr.br.rect(33, 17, 6, 7))
+    R = ctx.csr(33, 17, rp, cc, cv)
+    expect(lambda: ctx.gmres(R, db, ctx.vector(17)), "square")
+    expect(lambda: ctx.gmres(R, db, dx), "square")
+    nb = _problem("band4099")[0]
+    L = _band_handle(ctx, orc, "ell")
+    expect(lambda: ctx.gmres(L, ctx.vector(nb), ctx.vector(nb), precond=JACOBI), "Jacobi", UNSUPPORTED)
+    expect(lambda: ctx.gmres(L, ctx.vector(nb), ctx.vector(nb), precond=ILU0), "CSR", UNSUPPORTED)
+    assert dx.download().tobytes() == x0.tobytes()
+    # restart = 0 is 30
+    xs = []
+    for restart in (0, 30):
+        x = ctx.vector_from(x0)
+        assert ctx.gmres(A, db, x, restart=restart, max_iter=9, rel_tol=0.0)[0] == 9
+        xs.append(x.download().tobytes())
+    assert xs[0] == xs[1]
+    # a PANEL handle that released its CSR arrays (panel_keep_csr = 0): no diagonal to read, but the forward product is all a plain
+    # solve needs
+    nb = 1_000_000
+    P = ctx.gen_csr_uniform(0, nb, nb, 16, seed=31)
+    P.set_kernel(capi.CSR_PANEL)
+    P.set_param("panel_keep_csr", 0)
+    assert P.get_param("panel_keep_csr") == 0
+    pb, px = ctx.gen_vector(nb, seed=5), ctx.vector(nb)
+    px.fill(0.0)
+    expect(lambda: ctx.gmres(P, pb, px, precond=JACOBI), "gave up")
+    assert not px.download().any()
+    iters, res = ctx.gmres(P, pb, px, restart=4, max_iter=2, rel_tol=0.0)
+    assert iters == 2 and np.isfinite(res) and px.download().any()
+    RUNS["refusals"] += 1
+
+
+# ---- 6. convergence and ILU(0) -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precond", (NONE, JACOBI))
+def test_gmres_converges_to_the_tolerance_it_reports(ctx, pkg, precond):
+    name, rel_tol, m = "r4097", 1e-10, 30
+    n, ent, b, x0, ks, _ = _problem(name)
+    why = gr.available(n)
+    if why:
+        pytest.skip(why)
+    A = _csr(ctx, name)
+    db, x = ctx.vector_from(b), ctx.vector_from(x0)
+    iters, res = ctx.gmres(A, db, x, restart=m, max_iter=500, rel_tol=rel_tol, precond=precond)
+    true = gr.true_residual(ent, n, b, x.download())
+    twin_x, twin_iters = gr.run_to_tolerance(ent, n, b, x0, m, PRECOND_NAME[precond], rel_tol, 500)
+    twin_true = gr.true_residual(ent, n, b, twin_x)
+    print(f"{name} precond {precond}: {iters} iterations (twin {twin_iters}), reported residual {res:.3e}, true {true:.3e} (twin's {twin_true:.3e})")
+    assert 0 < iters < 500 and res <= rel_tol, (iters, res)
+    assert true <= gr.F * max(rel_tol, twin_true), (true, twin_true)
+    RUNS["convergence"] += 1
+
+
+def _entries(n, rp, cc, cv):
+    return (np.repeat(np.arange(n), np.diff(rp)), np.asarray(cc, np.int64), np.asarray(cv))
+
+
+@pytest.mark.parametrize("order", [0, 1], ids=["row_order", "multicolour"])
+def test_ilu0_preconditioned_gmres_takes_the_iterations_of_the_twins(ctx, pkg, order):
+    """the twin is GMRES(30) over ilu0_ref.Ilu0's application in the engine's sweep order"""
+    system, m = "bicgstab_convdiff40", 30
+    _, n, rp, cc, cv, b_host = ir.solver_system(system)
+    ent = _entries(n, rp, cc, cv)
+    A = ctx.csr(n, n, rp, cc, cv)
+    A.set_param("ilu0_order", order)
+    b, x = ctx.vector_from(b_host), ctx.vector(n)
+    x.fill(0.0)
+    iters, res = ctx.gmres(A, b, x, restart=m, max_iter=500, rel_tol=ir.REL_TOL, precond=ILU0)
+    assert A.get_param("ilu0_ready") == 1
+    apply_m = ir.Ilu0(n, rp, cc, cv, ctx.ilu0_order(A)).apply
+    twins = {o: gr.run_to_tolerance(ent, n, b_host, np.zeros(n), m, apply_m, ir.REL_TOL, 500, dot_order=o) for o in gr.DOT_ORDERS}
+    lo, hi = min(t[1] for t in twins.values()), max(t[1] for t in twins.values())
+    true = gr.true_residual(ent, n, b_host, x.download())
+    twin_true = gr.true_residual(ent, n, b_host, twins["pairwise"][0])
+    x.fill(0.0)
+    plain = ctx.gmres(A, b, x, restart=m, max_iter=500, rel_tol=ir.REL_TOL)[0]
+    print(f"{system} order {order}: {iters} iterations (twins {lo}..{hi}), reported {res:.3e}, true {true:.3e} (twin's {twin_true:.3e}); {plain} without a preconditioner")
+    assert lo <= iters <= hi, (iters, lo, hi)
+    assert res <= ir.REL_TOL and true <= gr.F * max(ir.REL_TOL, twin_true), (res, true, twin_true)
+    assert iters < plain, (iters, plain)
+    # stopped by max_iter, a look every fourth iteration leaves the x of a look at every one: the same bits
+    xs = []
+    for every in (1, 4):
+        x.fill(0.0)
+        assert ctx.gmres(A, b, x, restart=m, max_iter=7, rel_tol=0.0, check_every=every, precond=ILU0)[0] == 7
+        xs.append(x.download().tobytes())
+    assert xs[0] == xs[1]
+    RUNS["ilu0"] += 1
+
+
+def test_an_exact_factorisation_ends_gmres_after_one_iteration(ctx, pkg):
+    n, rp, cc, cv = ir.tridiagonal_nonsym()
+    A = ctx.csr(n, n, rp, cc, cv)
+    A.set_param("ilu0_order", 0)
+    b_host = np.random.default_rng(31).uniform(-1, 1, n)
+    b, x = ctx.vector_from(b_host), ctx.vector(n)
+    x.fill(0.0)
+    iters, res = ctx.gmres(A, b, x, max_iter=50, rel_tol=1e-9, precond=ILU0)
+    true = np.linalg.norm(b_host - ir.csr_mv(n, rp, cc, cv, x.download())) / np.linalg.norm(b_host)
+    print(f"tridiagonal_nonsym: {iters} iteration(s), reported {res:.3e}, true {true:.3e}")
+    assert iters == 1 and res <= 1e-9 and true <= 1e-9, (iters, res, true)
+    RUNS["exact"] += 1
+
+
+# ---- 7. reproducibility, the handle's state, device memory -----------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", ("dia", "csr vector"))
+def test_two_solves_give_the_same_bits(ctx, orc, pkg, fmt):
+    """the DIA kernel and the row-parallel CSR kernel add in fixed orders, so what this tests is the dot reductions"""
+    n, _, b, x0, _, _ = _problem("band4099")
+    A = _band_handle(ctx, orc, fmt.split()[0])
+    if fmt == "csr vector":
+        A.set_kernel(VECTOR)
+    db = ctx.vector_from(b)
+    for precond in (NONE,) if fmt == "dia" else (NONE, JACOBI):
+        out = []
+        for _ in range(2):
+            x = ctx.vector_from(x0)
+            stats = ctx.gmres(A, db, x, restart=4, max_iter=13, rel_tol=0.0, check_every=4, precond=precond)
+            out.append((x.download().tobytes(), stats))
+        assert out[0][1][0] == 13 and out[0] == out[1], "two calls on the same data differ"
+    RUNS["bits"] += 1
+
+
+@pytest.mark.parametrize("fmt", ("csr",) + FORMATS)
+def test_a_solve_leaves_the_handle_alone(ctx, orc, pkg, fmt):
+    n, _, b, x0, _, _ = _problem("band4099")
+    A = _band_handle(ctx, orc, fmt)
+    plan, kernel, info_bytes, param_bytes = A.get_plan(), A.info.kernel, A.info.device_bytes, A.get_param("device_bytes")
+    assert A.get_param("transpose_ready") == 0
+    iters, res = ctx.gmres(A, ctx.vector_from(b), ctx.vector_from(x0), max_iter=300, rel_tol=1e-9, precond=JACOBI if fmt == "csr" else NONE)
+    assert 0 < iters < 300 and res <= 1e-9
+    assert A.get_param("transpose_ready") == 0, f"{fmt}: the solve built the transposed state"
+    assert A.get_plan() == plan, f"{fmt}: the solve changed the plan"
+    assert (A.info.kernel, A.info.device_bytes, A.get_param("device_bytes")) == (kernel, info_bytes, param_bytes), fmt
+    RUNS["state"] += 1
+
+
+def test_work_vectors_go_back_on_every_path(ctx, pkg):
+    """67 MB of basis and work vectors per Jacobi solve with m = 4 on the large problem: ten solves that end well and ten that end
+    in an error would leave far more than the suite's leak tolerance (tests/test_gpu_parity.py: 256 MiB) behind if a path kept them"""
+    import gc
+
+    capi = pkg.capi
+    n, _, b, x0, _, _ = _problem("big")
+    A = _csr(ctx, "big")
+    db, x = ctx.vector_from(b), ctx.vector_from(x0)
+    bn = b.copy()
+    bn[n // 2] = np.nan
+    dbn = ctx.vector_from(bn)
+    gc.collect()
+    ctx.sync()
+    free0, _ = ctx.mem_info()
+    for _ in range(10):
+        assert ctx.gmres(A, db, x, restart=4, max_iter=2, rel_tol=0.0, precond=JACOBI)[0] == 2
+        with pytest.raises(capi.SpmvError):
+            ctx.gmres(A, dbn, x, restart=4, max_iter=2, precond=JACOBI)
+    ctx.sync()
+    free1, _ = ctx.mem_info()
+    assert (4 + 4) * 8 * n * 10 > 256 << 20
+    assert abs(free0 - free1) < 256 << 20, f"{(free0 - free1) >> 20} MiB of device memory not returned"
+    RUNS["memory"] += 1
+
+
+# ---- 8. torch ------------------------------------------------------------------------------------------------------------------------------
+def test_torch_solve_is_the_engine_solve_bit_for_bit():
+    """tests/child_gmres_torch.py in a fresh process: torch initialises its HIP runtime before the engine's library is loaded"""
+    import subprocess
+    import sys
+
+    child = Path(__file__).with_name("child_gmres_torch.py")
+    r = subprocess.run([sys.executable, str(child)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "GMRES_TORCH_OK" in r.stdout, (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
+    RUNS["torch"] += 1
+
+
+# ---- 9. coverage ---------------------------------------------------------------------------------------------------------------------------
+def test_every_case_ran():
+    """every problem, kernel and format of the cases above ran, and no ratio lies above the gate"""
+    expect = {"csr": len(CSR_CASES), "wide": len(gr.WIDE_KS), "kernels": len(KERNEL_CASES), "formats": len(FORMATS), "rotation": 1, "stopping": 1,
+              "refusals": 1, "convergence": 2, "ilu0": 2, "exact": 1, "bits": 2, "state": 1 + len(FORMATS), "memory": 1, "torch": 1}
+    if any(RUNS[f] != c for f, c in expect.items()):
+        pytest.skip(f"the coverage check needs every test of this module (ran {dict(RUNS)}, expected {expect})")
+    assert set(RATIO) == set(ALL_PROBLEMS), sorted(set(ALL_PROBLEMS) - set(RATIO))
+    lines = ["# spmv_gmres iterate by iterate (tests/test_gpu_gmres.py): the largest deviation of the GPU's x_k and of its |g| / ||b||",
+             "# from the np.longdouble recurrence, in units of the float64 twins' own largest deviation at that k (the gate is 8).",
+             "# problem | x ratio | residual ratio | where the x ratio was largest"]
+    for name in ALL_PROBLEMS:
+        r = RATIO[name]
+        lines.append(f"{name:12s}  x {r['x'][0]:6.3f}  residual {r['residual'][0]:6.3f}  ({r['x'][1]})")
+    print("\n".join(lines))
+    out = os.environ.get("SPMV_GMRES_RATIOS")
+    if out:
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    for name in ALL_PROBLEMS:
+        assert all(RATIO[name][kind][0] <= gr.F for kind in RATIO[name]), (name, RATIO[name])
