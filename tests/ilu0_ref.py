@@ -368,3 +368,265 @@ def twin_iterations(name, order, precond="ilu0", max_iter=500):
         apply_m = lambda r: r.copy()
     run = run_bicgstab if solver == "bicgstab" else run_cg
     return {o: run(mv, apply_m, b, REL_TOL, max_iter, dot_order=o)[1] for o in DOT_ORDERS}
+
+
+# ---- matrices ILU(0) factorises EXACTLY: A = (I + L) U from small dyadic numbers on a pattern that takes no fill ------------------
+# L: multiples of 1/4 in [-3/4, 3/4]; U off its diagonal: integers in [-3, 3]; U's diagonal: +-{1/2, 1, 2, 4}, so every division
+# of the elimination and of the backward solve is by a power of two.  Every term l_ik u_kj is a multiple of 2^-2, A's entries are
+# sums of a handful of them, and a split entry is stored as two multiples of 2^-4 that sum to it: all of it on the grid 2^-EXACT_G,
+# orders of magnitude below the 2^53 budget (assert_exact_budget counts, in integers).  ILU(0) of such a matrix must return L and U
+# themselves and its application to r = A z, z integers, z itself - whatever the lanes, the tree or the order of a sum.
+EXACT_G, EXACT_G_L, EXACT_G_U = 4, 2, 0
+EXACT_G_DIAG = 1  # (U's diagonal alone is on the grid 2^-1)
+
+
+def _dyadic_lu_values(rng, shape_l, shape_u, shape_d):
+    l = rng.integers(-3, 4, shape_l) / 4.0
+    u = rng.integers(-3, 4, shape_u).astype(np.float64)
+    d = np.where(rng.random(shape_d) < 0.5, -1.0, 1.0) * np.ldexp(1.0, rng.integers(-1, 3, shape_d))
+    return l, u, d
+
+
+def _store_exact(rng, n, r, c, a, f, split=0.2):
+    """CSR of the entries (r, c, a) with their factor values f: about `split` of them stored as two duplicates whose dyadic parts sum
+    exactly, the entries of a row in random order; expected[e] = f for the first stored entry of a position, 0.0 for a later one"""
+    two = np.flatnonzero(rng.random(len(r)) < split)
+    part = rng.integers(-64, 65, len(two)) / 16.0  # (a zero part, and a zero rest, are stored zeros like any other)
+    v = a.copy()
+    v[two] = part
+    r, c, v, f = np.concatenate([r, r[two]]), np.concatenate([c, c[two]]), np.concatenate([v, a[two] - part]), np.concatenate([f, f[two]])
+    o = np.lexsort((rng.random(len(r)), r))
+    r, c, v, f = r[o], c[o], v[o], f[o]
+    firsts = np.zeros(len(r), bool)
+    firsts[np.unique(r.astype(np.int64) * n + c, return_index=True)[1]] = True
+    rp = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=n))]).astype(np.int32)
+    return n, rp, c.astype(np.int32), v, np.where(firsts, f, 0.0)
+
+
+def clique_rank(sizes, seed):
+    """(block of every row, its rank inside the block) of clique_blocks(sizes, seed): a random permutation deals the rows 0 .. n-1 out
+    to the blocks, a block's rows in ascending index.  Greedy colouring in row order gives a row its rank as colour."""
+    sizes = np.asarray(sizes, np.int64)
+    owner = np.random.default_rng(seed).permutation(np.repeat(np.arange(len(sizes)), sizes))
+    by_block = np.argsort(owner, kind="stable")
+    rank = np.empty(len(owner), np.int64)
+    rank[by_block] = np.arange(len(owner)) - np.repeat(np.cumsum(sizes) - sizes, sizes)
+    return owner, rank
+
+
+def clique_blocks(sizes, seed, split=0.2):
+    """(n, rp, cc, cv, expected factors): a block-diagonal matrix of dense blocks A_b = (I + L_b) U_b, the blocks' rows interleaved
+    (clique_rank), every position of a block stored, zeros included.  A dense block takes no fill in any order, and both sweep orders
+    eliminate a block in its construction order: exact in both."""
+    owner, rank = clique_rank(sizes, seed)
+    n = len(owner)
+    by_block = np.argsort(owner, kind="stable")
+    rng = np.random.default_rng([seed, 1])
+    rs, cs, vs, fs = [], [], [], []
+    start = 0
+    for s in np.asarray(sizes, np.int64).tolist():
+        idx = by_block[start:start + s]
+        start += s
+        l, u, d = _dyadic_lu_values(rng, (s, s), (s, s), s)
+        l, u = np.tril(l, -1), np.triu(u, 1) + np.diag(d)
+        a = (np.eye(s) + l) @ u  # (exact: every partial sum is a small multiple of 2^-3)
+        rs.append(np.repeat(idx, s))
+        cs.append(np.tile(idx, s))
+        vs.append(a.ravel())
+        fs.append((l + u).ravel())
+    cat = lambda x, t: np.concatenate(x).astype(t) if x else np.zeros(0, t)
+    return _store_exact(rng, n, cat(rs, np.int64), cat(cs, np.int64), cat(vs, np.float64), cat(fs, np.float64), split)
+
+
+def band_lu(n, p, q, seed, split=0.2):
+    """(n, rp, cc, cv, expected factors): A = (I + L) U with p sub-diagonals in L and q super-diagonals in U, the whole band
+    -p .. q stored (products that happen to be zero included): no fill in ROW ORDER, where ILU(0) is the LU factorisation.  Not
+    diagonally dominant: not for the multicolour order."""
+    rng = np.random.default_rng([seed, 2])
+    l, u, d = _dyadic_lu_values(rng, (p + 1, n), (q + 1, n), n)  # l[k][i] = L[i, i - k], u[e][i] = U[i, i + e]
+    l[0], u[0] = 1.0, d
+    i = np.arange(n)
+    for k in range(1, p + 1):
+        l[k][i < k] = 0.0
+    for e in range(1, q + 1):
+        u[e][i + e >= n] = 0.0
+    rs, cs, vs, fs = [], [], [], []
+    for off in range(-p, q + 1):
+        a = np.zeros(n)
+        for k in range(max(0, -off), p + 1):  # A[i, i + off] = sum_k L[i, i - k] U[i - k, i + off]
+            e = off + k
+            if e > q:
+                break
+            src = i - k
+            ok = src >= 0
+            a[ok] += l[k][ok] * u[e][src[ok]]
+        keep = (i + off >= 0) & (i + off < n)
+        rs.append(i[keep])
+        cs.append(i[keep] + off)
+        vs.append(a[keep])
+        fs.append((l[-off] if off < 0 else u[off])[keep])
+    return _store_exact(rng, n, np.concatenate(rs), np.concatenate(cs), np.concatenate(vs), np.concatenate(fs), split)
+
+
+def integer_vector(n, seed):
+    """z: integers in [-8, 8]"""
+    return np.random.default_rng([seed, 3]).integers(-8, 9, n).astype(np.float64)
+
+
+def _scaled(a, g, what):
+    s = np.ldexp(np.asarray(a, np.float64), g)
+    if not (np.all(np.isfinite(s)) and np.array_equal(s, np.round(s)) and (s.size == 0 or np.max(np.abs(s)) < 2.0**53)):
+        raise AssertionError(f"{what}: not on the grid 2^-{g}")
+    return s.astype(np.int64)
+
+
+def assert_exact_budget(n, rp, cc, cv, expected, order, z, g=EXACT_G, g_l=EXACT_G_L, g_u=EXACT_G_U, g_d=EXACT_G_DIAG):
+    """The conditions under which the elimination and both solves are exact in any order of any sum, checked in INTEGER arithmetic
+    (values scaled by 2^g; tests/exact.py does the same for the products): with the expected factors L (grid 2^-g_l), U (2^-g_u off
+    the diagonal, +- a power of two on it, grid 2^-g_d) and the stored values (2^-g),
+      - no fill: wherever (i, k) and (k, j) are in the pattern with k before i and j in the sweep, (i, j) is;
+      - the matrix is the product: sum of the stored duplicates of (i, j) = sum_k l_ik u_kj (+ u_ij), as integers, so the
+        elimination - which subtracts exactly these terms from exactly these sums, and divides by powers of two - ends at L and U;
+      - every term of it is a multiple of 2^-g and |stored parts| + sum |l_ik u_kj| stays below 2^(53 - g), so every partial sum is
+        a float64, whatever came first;
+      - the same for r = A z, the forward solve (r_i and the terms l_ik y_k, y = U z) and the backward one (y_i and u_ij z_j).
+    Returns the largest of those magnitudes as a number of bits (53 is the budget)."""
+    assert g >= g_l + max(g_u, g_d)
+    rp, cc, cv = np.asarray(rp, np.int64), np.asarray(cc, np.int64), np.asarray(cv, np.float64)
+    order = np.asarray(order, np.int64)
+    pos = np.empty(n, np.int64)
+    pos[order] = np.arange(n)
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    code, ia = rows * n + cc, _scaled(cv, g, "a stored value")
+    u_code, first, inv = np.unique(code, return_index=True, return_inverse=True)
+    firsts = np.zeros(len(cc), bool)
+    firsts[first] = True
+    assert np.all(np.asarray(expected)[~firsts] == 0.0), "a later duplicate carries a factor value"
+    a_sum, a_mag = np.zeros(len(u_code), np.int64), np.zeros(len(u_code), np.int64)
+    np.add.at(a_sum, inv, ia)
+    np.add.at(a_mag, inv, np.abs(ia))
+    mr, mc, f = u_code // n, u_code % n, np.asarray(expected, np.float64)[first]  # the merged pattern, row by row
+    kr, kc = pos[mr], pos[mc]
+    il = _scaled(np.where(kc < kr, f, 0.0), g_l, "an entry of L") << (g - g_l)  # on the grid 2^-g ...
+    iu = _scaled(np.where(kc > kr, f, 0.0), g_u, "an entry of U") << (g - g_l - g_u)  # ... and 2^-(g - g_l): l u is on 2^-g again
+    idg = _scaled(np.where(kc == kr, f, 0.0), g_d, "a pivot") << (g - g_l - g_d)
+    piv = np.abs(idg[kc == kr])
+    assert len(piv) == n and np.all(piv > 0) and np.all(piv & (piv - 1) == 0), "a pivot is not +- a power of two"
+    iu = iu + idg  # U with its diagonal, grid 2^-(g - g_l)
+    mptr = np.searchsorted(mr, np.arange(n + 1))
+    up_of = [None] * n  # row k: (columns, values) of its part on and after the diagonal
+    for k in range(n):
+        sel = np.arange(mptr[k], mptr[k + 1])
+        sel = sel[kc[sel] >= kr[sel]]
+        up_of[k] = (mc[sel], iu[sel])
+    slot = np.full(n, -1, np.int64)
+    worst = 1
+    for i in range(n):
+        b, e = mptr[i], mptr[i + 1]
+        slot[mc[b:e]] = np.arange(e - b)
+        acc = np.where(kc[b:e] >= kr[b:e], iu[b:e] << g_l, 0)  # the row of I times U
+        mag = a_mag[b:e] + 0
+        for t in np.flatnonzero(kc[b:e] < kr[b:e]).tolist():
+            cols, vals = up_of[mc[b + t]]
+            s = slot[cols]
+            assert np.all(s >= 0), f"fill: row {i} through row {int(mc[b + t])}"
+            term = (il[b + t] >> (g - g_l)) * vals  # l (grid 2^-g_l) times u (grid 2^-(g - g_l)): grid 2^-g
+            acc[s] += term
+            mag[s] += np.abs(term)
+        assert np.array_equal(acc, a_sum[b:e]), f"row {i}: the stored values are not those of (I + L) U"
+        worst = max(worst, int(mag.max()))
+        slot[mc[b:e]] = -1
+    # the solves: r = A z; L y = r with y = U z; U z = y
+    iz = _scaled(z, 0, "z")
+    t = np.abs(ia * iz[cc])
+    r_mag = np.zeros(n, np.int64)
+    np.add.at(r_mag, rows, t)
+    iy = np.zeros(n, np.int64)  # y = U z on the grid 2^-(g - g_l)
+    np.add.at(iy, mr, iu * iz[mc])
+    ir = np.zeros(n, np.int64)
+    np.add.at(ir, rows, ia * iz[cc])
+    fwd, bwd = np.abs(ir), np.abs(iy) << g_l
+    ly = np.zeros(n, np.int64)
+    np.add.at(ly, mr, (il >> (g - g_l)) * iy[mc])
+    np.add.at(fwd, mr, np.abs((il >> (g - g_l)) * iy[mc]))
+    np.add.at(bwd, mr, np.abs(np.where(kc > kr, iu, 0) * iz[mc]) << g_l)
+    assert np.array_equal(ir, ly + (iy << g_l)), "r = A z is not (I + L) (U z)"
+    worst = max(worst, int(r_mag.max(initial=0)), int(fwd.max(initial=0)), int(bwd.max(initial=0)))
+    assert worst < 2**53, f"a sum needs {math.log2(worst):.1f} bits on the grid 2^-{g} (budget 53)"
+    return math.log2(worst)
+
+
+# ---- the levels and launches tri_levels.hpp must find ------------------------------------------------------------------------------
+SMALL_LEVEL, LANE_STEPS = 4096, ((2.5, 1), (12.0, 4))  # csrc/tri_levels.hpp: kSmallLevel; lanes 1 / 4 / 16 by entries per row
+
+
+def level_sizes(n, rp, cc, order, merged=True):
+    """The dependency levels of both triangles in a sweep order and the schedule csrc/tri_levels.hpp's rule makes of them:
+    level(i) = 1 + the largest level among the rows that row i's triangle names (0 without any); lanes per row 1, 4 or 16 for up to
+    2.5, up to 12 and more entries per row on average (merged: duplicates counted once, as ILU(0) stores its triangles; the
+    Gauss-Seidel sweep keeps them); levels of up to 4096 lanes are folded, run by run, into one launch, every other level is a launch
+    of its own.  Returns {"lower" / "upper": rows per level, "lanes": (lower, upper), "schedule": ([(first level, levels)], same),
+    "launches": of one application}"""
+    rp, cc, order = np.asarray(rp, np.int64), np.asarray(cc, np.int64), np.asarray(order, np.int64)
+    pos = np.empty(n, np.int64)
+    pos[order] = np.arange(n)
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    if merged:
+        code = np.unique(rows * max(n, 1) + cc)
+        rows, cc = code // max(n, 1), code % max(n, 1)
+    out = {"lanes": [], "schedule": [], "launches": 0}
+    for name, sel, sweep in (("lower", pos[cc] < pos[rows], order), ("upper", pos[cc] > pos[rows], order[::-1])):
+        r, c = rows[sel], cc[sel]
+        ptr = np.searchsorted(r, np.arange(n + 1)).tolist()  # (rows ascends)
+        cl, lev = c.tolist(), [0] * n
+        for i in sweep.tolist():
+            a, b = ptr[i], ptr[i + 1]
+            if b > a:
+                lev[i] = 1 + max(lev[j] for j in cl[a:b])
+        hist = np.bincount(np.asarray(lev, np.int64), minlength=1) if n else np.zeros(0, np.int64)
+        avg = len(r) / n if n else 0.0
+        lanes = next((w for bound, w in LANE_STEPS if avg <= bound), 16)
+        sched, lv = [], 0
+        while lv < len(hist):
+            end = lv
+            while end < len(hist) and hist[end] * lanes <= SMALL_LEVEL:
+                end += 1
+            end = max(end, lv + 1)  # (a level above the bound: alone)
+            sched.append((lv, end - lv))
+            lv = end
+        out[name] = hist
+        out["lanes"].append(lanes)
+        out["schedule"].append(sched)
+        out["launches"] += len(sched)
+    out["lanes"] = tuple(out["lanes"])
+    return out
+
+
+# ---- the exact cases tests/test_gpu_ilu0_exact.py runs on the GPU and tests/test_ilu0_ref.py checks on the CPU --------------------
+def _mixed_sizes(count, top, seed, extra=()):
+    return np.random.default_rng([seed, 4]).integers(1, top + 1, count).tolist() + list(extra)
+
+
+EXACT_CLIQUES = {  # name: (block sizes, seed)
+    "cliques_130": ([1, 2, 27, 65, 130], 130),
+    "cliques_mixed": (_mixed_sizes(1500, 6, 131, [130, 70]), 131),
+    "cliques_12": ([12] * 60 + [1] * 5, 132),
+    "cliques_tiny": (_mixed_sizes(6000, 3, 133), 133),
+}
+EXACT_BANDS = {  # name: (n, sub-diagonals of L, super-diagonals of U, seed); row order only
+    "band_1_20": (5000, 1, 20, 140),
+    "band_20_1": (5000, 20, 1, 141),
+    "band_3_3": (3000, 3, 3, 142),
+}
+EXACT_CASES = [(name, order) for name in EXACT_CLIQUES for order in (0, 1)] + [(name, 0) for name in EXACT_BANDS]
+
+
+def exact_case(name):
+    """(n, rp, cc, cv, expected factors, z)"""
+    if name in EXACT_CLIQUES:
+        sizes, seed = EXACT_CLIQUES[name]
+        m = clique_blocks(sizes, seed)
+    else:
+        n, p, q, seed = EXACT_BANDS[name]
+        m = band_lu(n, p, q, seed)
+    return m + (integer_vector(m[0], seed),)

@@ -296,6 +296,69 @@ def test_random_systems_through_the_gauss_seidel_sweep(ctx, orc, pkg, seed):
         assert err <= ol.REL_TOL, (seed, n, k, order, sweeps, err)
 
 
+@pytest.mark.parametrize("seed", range(12))
+def test_random_systems_through_ilu0(ctx, orc, pkg, seed):
+    """the systems of the sweep fuzzer above - strictly diagonally dominant, so H-matrices: ILU(0) exists in any order - with what
+    the symbolic phase has to merge: off-diagonal duplicates in both triangles, stored zeros, the diagonal sometimes split; both
+    sweep orders against the NumPy reference (tests/ilu0_ref.py) over the sequence the engine reports: the factors entry by entry,
+    0.0 in every later duplicate, one application; the multicolour sequence against the oracle's sequential greedy colouring"""
+    import ilu0_ref as ir
+
+    rng = np.random.default_rng(BASE + 6500 + seed)
+    n = int(rng.choice([1, 2, 65, 1000, 20_000]))
+    k = int(rng.integers(0, 9))
+    cols = rng.integers(0, n, (n, k))
+    if rng.uniform() < 0.5 and k:  # local couplings: long dependency chains in row order
+        cols = (np.arange(n)[:, None] + rng.integers(-3, 4, (n, k))) % n
+    vals = rng.uniform(-1, 1, (n, k))
+    vals[rng.uniform(size=(n, k)) < 0.1] = 0.0  # stored zeros: in the pattern all the same
+    rows = np.repeat(np.arange(n), k).reshape(n, k)
+    vals[cols == rows] = 0.0
+    r, c, v = rows.ravel(), cols.ravel(), vals.ravel()
+    if rng.uniform() < 0.5:  # symmetric pattern
+        r, c, v = np.concatenate([r, c]), np.concatenate([c, r]), np.concatenate([v, v])
+    again = np.flatnonzero((rng.uniform(size=len(r)) < 0.15) & (r != c))  # duplicates off the diagonal, wherever they fall
+    r, c, v = np.concatenate([r, r[again]]), np.concatenate([c, c[again]]), np.concatenate([v, rng.uniform(-1, 1, len(again))])
+    dom = np.zeros(n)
+    np.add.at(dom, r, np.abs(v))
+    dom += 1.0
+    split = rng.uniform() < 0.5
+    dr = np.arange(n)
+    r = np.concatenate([r, dr] + ([dr] if split else []))
+    c = np.concatenate([c, dr] + ([dr] if split else []))
+    v = np.concatenate([v, dom * (0.6 if split else 1.0)] + ([dom * 0.4] if split else []))
+    o = np.lexsort((rng.uniform(size=len(r)), r))  # rows together, entries inside a row in random order
+    r, c, v = r[o], c[o], v[o]
+    rp = np.zeros(n + 1, np.int64)
+    np.add.at(rp, r + 1, 1)
+    rp, cc = np.cumsum(rp).astype(np.int32), c.astype(np.int32)
+    firsts = np.zeros(len(cc), bool)
+    firsts[np.unique(r.astype(np.int64) * n + c, return_index=True)[1]] = True
+    A = ctx.csr(n, n, rp, cc, v)
+    r_host = rng.uniform(-1, 1, n)
+    rv = ctx.vector_from(r_host)
+    for order in (1, 0):
+        A.set_param("ilu0_order", order)
+        seq = ctx.ilu0_order(A)
+        if order == 1:
+            ncol, _, want_seq = ol.greedy_colour_order(orc, rp, cc)
+            assert np.array_equal(seq, want_seq) and A.get_param("ilu0_colours") == ncol
+        else:
+            assert np.array_equal(seq, np.arange(n)) and A.get_param("ilu0_colours") == 0
+        ref = ir.Ilu0(n, rp, cc, v, seq)
+        fac = ctx.ilu0_factors(A)
+        err = np.max(np.abs(fac - ref.values)) / max(np.max(np.abs(ref.values)), 1e-300)
+        assert err <= ol.REL_TOL, (seed, n, k, order, "factors", err)
+        assert np.all(fac[~firsts] == 0.0), (seed, n, k, order, "a later duplicate holds a value")
+        z = ctx.vector(n)
+        z.fill(7.0)
+        ctx.ilu0_solve(A, rv, z)
+        ctx.sync()
+        want = ref.apply(r_host)
+        err = np.max(np.abs(z.download() - want)) / max(np.max(np.abs(want)), 1e-300)
+        assert err <= ol.REL_TOL, (seed, n, k, order, "application", err)
+
+
 @pytest.mark.parametrize("seed", range(10))
 def test_random_blas1(ctx, orc, seed):
     """dot and the axpby branches on random lengths and coefficients (0, 1, -1 and general), w aliasing x or y"""

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import cases
+import ilu0_ref as ir
 import oracle_lib as ol
 from conftest import golden
 from test_gpu_parity import _csr_of, _scale
@@ -315,7 +316,7 @@ def _symgs_close(got, want, what):
 
 
 @pytest.mark.parametrize("order", [0, 1], ids=["row_order", "multicolour"])
-@pytest.mark.parametrize("problem", ["tridiagonal_8", "laplacian_3d", "random_pattern", "lower_triangular"])
+@pytest.mark.parametrize("problem", ["tridiagonal_8", "laplacian_3d", "random_pattern", "lower_triangular", "cliques_130", "band33"])
 def test_symgs_matches_the_sweep_in_the_same_order(ctx, orc, pkg, problem, order):
     """spmv_symgs against oracle/spmv_oracle.c: orc_symgs_ordered (the textbook sweep; nothing in the reference to pin it
     to), in the matrix's own row order and in the multicolour order the engine reports: 1, 2 and 3 sweeps from a random
@@ -336,6 +337,21 @@ def test_symgs_matches_the_sweep_in_the_same_order(ctx, orc, pkg, problem, order
     elif problem == "random_pattern":
         n, rp, cc, cv = _dominant_random(30_000, 7, 4)
         levels = colours = None
+    elif problem == "cliques_130":
+        # the pattern of tests/test_gpu_ilu0_exact.py's case - dense blocks of 1, 2, 27, 65 and 130 interleaved rows, a fifth of the
+        # entries stored twice, rows unsorted - with strictly diagonally dominant values: 130 colours (three windows of the
+        # colouring's 64-colour loop), about 58 stored entries per triangle row (the 16-lane solve in row order)
+        n, rp, cc, cv = ir.exact_case("cliques_130")[:4]
+        rows = np.repeat(np.arange(n), np.diff(rp))
+        on = cc == rows
+        cv = np.where(on, 0.0, rng.uniform(-1, 1, len(cc)))
+        dom = np.bincount(rows, np.abs(cv), minlength=n) + 1.0
+        cv[on] = (dom / np.bincount(rows[on], minlength=n))[rows[on]]  # (a split diagonal entry: two halves)
+        assert (len(cc) - n) / 2 / n > 12 and np.bincount(rows[on], minlength=n).max() == 2
+        levels, colours = (130, 130), 130  # a block of 130 is a chain of 130 in either order
+    elif problem == "band33":
+        n, rp, cc, cv = ir.band33()  # 33 diagonals, the main one 32 + 2^-10 against 32 entries below 1: 16 lanes in both triangles
+        levels, colours = (n, n), 17  # every row waits for the one before it; colour = i mod 17
     else:
         n, rp, cc, cv = _dominant_random(5_000, 5, 6)
         rows = np.repeat(np.arange(n), np.diff(rp))
@@ -373,8 +389,10 @@ def test_symgs_matches_the_sweep_in_the_same_order(ctx, orc, pkg, problem, order
         assert bool(fused) == (proper and (lf, lb) == (ncol, ncol)), (problem, fused, proper, lf, lb, ncol)
         if fused:
             assert A.get_param("symgs_launches") == 2 * ncol - 1
-        if problem in ("tridiagonal_8", "laplacian_3d"):
+        if problem in ("tridiagonal_8", "laplacian_3d", "cliques_130", "band33"):
             assert fused == 1
+        if problem == "cliques_130":
+            assert A.get_param("symgs_colours") == 130
         if problem == "random_pattern":
             assert fused == 0  # a_ij without a_ji: two coupled rows can share a colour
     else:
