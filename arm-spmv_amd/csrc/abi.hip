@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "solver_host.hpp"
 
 namespace spmv
 {
@@ -1292,24 +1293,23 @@ int spmv_apply_dot(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec
     return SPMV_OK;
 }
 
+// The five solves.  Every check is made before the device is touched, so that they hold (and are tested) on a machine without one;
+// the checks they share and what each solver's refusals depend on (solver_rules) are solver_host.hpp's.
+static const solver_rules kCgRules       = {"spmv_cg", "the matrix", true, nullptr, nullptr, solver_rules::jacobi_arrays_unsupported};
+static const solver_rules kCgMultiRules  = {"spmv_cg_multi", "the matrix", false, "k columns", "k columns", solver_rules::jacobi_arrays_elsewhere};
+static const solver_rules kBicgstabRules = {"spmv_bicgstab", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid};
+static const solver_rules kGmresRules    = {"spmv_gmres", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid};
+
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
             int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
 {
-    SPMV_REQUIRE(ctx && A && b && x && iters && rel_resid, "spmv_cg: null argument");
-    SPMV_REQUIRE(A->nrow == A->ncol, "spmv_cg: the matrix is %d x %d, not square", A->nrow, A->ncol);
-    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "spmv_cg: b has %lld and x %lld entries, the matrix %d rows",
-                 (long long)b->n, (long long)x->n, A->nrow);
-    SPMV_REQUIRE(b->d != x->d || x->n == 0, "spmv_cg: b and x must not alias");
-    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_cg: max_iter=%d rel_tol=%g", max_iter, rel_tol);
-    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
-                 "spmv_cg: unknown preconditioner %d", precond);
-    if (precond == SPMV_PRECOND_ILU0) SPMV_TRY(ilu0_check_handle(A, "spmv_cg"));
+    SPMV_TRY(check_square_solve(kCgRules, ctx, A, b, x, max_iter, rel_tol, precond, iters, rel_resid));
+    SPMV_TRY(check_preconditioner(kCgRules, A, precond));
     SPMV_TRY(use_device(ctx));
     return cg_solve(ctx, A, b->d, x->d, max_iter, rel_tol, check_every, precond, iters, rel_resid);
 }
 
-// k right-hand sides at once (solver_multi.hip).  Every check is made before the device is touched, so that they hold (and are
-// tested) on a machine without one.
+// k right-hand sides at once (solver_multi.hip)
 int spmv_cg_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* B, spmv_vec* X, int32_t max_iter, double rel_tol,
                   int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
 {
@@ -1318,18 +1318,12 @@ int spmv_cg_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* B
     SPMV_REQUIRE(A->nrow == A->ncol, "spmv_cg_multi: the matrix is %d x %d, not square", A->nrow, A->ncol);
     SPMV_REQUIRE(B->n == (int64_t)A->nrow * k && X->n == (int64_t)A->nrow * k,
                  "spmv_cg_multi: B has %lld and X %lld entries, nrow * k = %d * %d", (long long)B->n, (long long)X->n, A->nrow, k);
-    SPMV_REQUIRE(B->n == 0 || X->n == 0 || B->d + B->n <= X->d || X->d + X->n <= B->d, "spmv_cg_multi: B and X must not overlap");
-    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_cg_multi: max_iter=%d rel_tol=%g", max_iter, rel_tol);
-    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
-                 "spmv_cg_multi: unknown preconditioner %d", precond);
+    SPMV_REQUIRE(vectors_disjoint(B, X), "spmv_cg_multi: B and X must not overlap");
+    SPMV_TRY(check_limits("spmv_cg_multi", max_iter, rel_tol));
+    SPMV_TRY(check_known_preconditioner("spmv_cg_multi", precond));
     if (A->format != SPMV_FMT_CSR && A->format != SPMV_FMT_ELL)
         SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: CSR and ELL handles only (format %d), as spmv_apply_multi", A->format);
-    if (precond == SPMV_PRECOND_SYMGS)
-        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: the symmetric Gauss-Seidel preconditioner is not built for k columns");
-    if (precond == SPMV_PRECOND_ILU0)
-        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: the ILU(0) preconditioner is not built for k columns");
-    if (precond == SPMV_PRECOND_JACOBI && A->format != SPMV_FMT_CSR)
-        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg_multi: the Jacobi preconditioner reads the diagonal of a CSR handle");
+    SPMV_TRY(check_preconditioner(kCgMultiRules, A, precond));
     // the product reads the handle's own arrays: a CSR handle that released them (panel_keep_csr = 0) is refused here, on the host
     const int64_t entries = A->format == SPMV_FMT_CSR ? A->nnz : (int64_t)A->nrow * A->k;
     SPMV_REQUIRE(entries == 0 || (A->b && A->v), "spmv_cg_multi: this handle gave up its CSR arrays (panel_keep_csr = 0)");
@@ -1337,15 +1331,15 @@ int spmv_cg_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* B
     return cg_multi_solve(ctx, A, k, B->d, X->d, max_iter, rel_tol, check_every, precond, iters, rel_resid);
 }
 
-// least squares over A and A^T (solver_cgls.hip).  Every check is made before the device is touched.
+// least squares over A and A^T (solver_cgls.hip)
 int spmv_cgls(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol, int32_t check_every,
               double damp, int32_t* iters, double* rel_normal_resid, double* rel_resid)
 {
     SPMV_REQUIRE(ctx && A && b && x && iters && rel_normal_resid && rel_resid, "spmv_cgls: null argument");
     SPMV_REQUIRE(b->n == A->nrow, "spmv_cgls: b has %lld entries, the matrix (shard) %d rows", (long long)b->n, A->nrow);
     SPMV_REQUIRE(x->n == A->ncol, "spmv_cgls: x has %lld entries, the matrix %d columns", (long long)x->n, A->ncol);
-    SPMV_REQUIRE(b->n == 0 || x->n == 0 || b->d + b->n <= x->d || x->d + x->n <= b->d, "spmv_cgls: b and x must not overlap");
-    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_cgls: max_iter=%d rel_tol=%g", max_iter, rel_tol);
+    SPMV_REQUIRE(vectors_disjoint(b, x), "spmv_cgls: b and x must not overlap");
+    SPMV_TRY(check_limits("spmv_cgls", max_iter, rel_tol));
     SPMV_REQUIRE(damp >= 0.0 && std::isfinite(damp), "spmv_cgls: damp=%g, must be finite and not negative", damp);
     // the transposed product reads the handle's own arrays the other way round: a CSR handle that released them is refused here
     SPMV_REQUIRE(!(A->format == SPMV_FMT_CSR && A->nnz > 0 && (!A->b || !A->v)),
@@ -1354,26 +1348,12 @@ int spmv_cgls(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, 
     return cgls_solve(ctx, A, b->d, x->d, max_iter, rel_tol, check_every, damp, iters, rel_normal_resid, rel_resid);
 }
 
-// nonsymmetric square systems over two forward products (solver_bicgstab.hip).  Every check is made before the device is touched.
+// nonsymmetric square systems over two forward products (solver_bicgstab.hip)
 int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol, int32_t check_every,
                   int32_t precond, int32_t* iters, double* rel_resid)
 {
-    SPMV_REQUIRE(ctx && A && b && x && iters && rel_resid, "spmv_bicgstab: null argument");
-    SPMV_REQUIRE(A->nrow == A->ncol, "spmv_bicgstab: the matrix (shard) is %d x %d, not square", A->nrow, A->ncol);
-    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "spmv_bicgstab: b has %lld and x %lld entries, the matrix %d rows", (long long)b->n,
-                 (long long)x->n, A->nrow);
-    SPMV_REQUIRE(b->n == 0 || b->d + b->n <= x->d || x->d + x->n <= b->d, "spmv_bicgstab: b and x must not overlap");
-    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_bicgstab: max_iter=%d rel_tol=%g", max_iter, rel_tol);
-    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
-                 "spmv_bicgstab: unknown preconditioner %d", precond);
-    if (precond == SPMV_PRECOND_SYMGS)
-        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_bicgstab: the symmetric Gauss-Seidel preconditioner is not built for this solver");
-    if (precond == SPMV_PRECOND_JACOBI && A->format != SPMV_FMT_CSR)
-        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_bicgstab: the Jacobi preconditioner reads the diagonal of a CSR handle");
-    if (precond == SPMV_PRECOND_ILU0) SPMV_TRY(ilu0_check_handle(A, "spmv_bicgstab"));
-    // Jacobi reads the handle's own arrays; the plain solve needs the forward product alone and takes such a handle
-    SPMV_REQUIRE(!(precond == SPMV_PRECOND_JACOBI && A->nnz > 0 && (!A->b || !A->v)),
-                 "spmv_bicgstab: this handle gave up its CSR arrays (panel_keep_csr = 0): no diagonal for the Jacobi preconditioner");
+    SPMV_TRY(check_square_solve(kBicgstabRules, ctx, A, b, x, max_iter, rel_tol, precond, iters, rel_resid));
+    SPMV_TRY(check_preconditioner(kBicgstabRules, A, precond));
     *iters     = 0;
     *rel_resid = 0.0;
     if (A->nrow == 0) return SPMV_OK;
@@ -1381,28 +1361,13 @@ int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec*
     return bicgstab_solve(ctx, A, b->d, x->d, max_iter, rel_tol, check_every, precond, iters, rel_resid);
 }
 
-// nonsymmetric square systems by restarted GMRES over one forward product per iteration (solver_gmres.hip).  Every check is made
-// before the device is touched.
+// nonsymmetric square systems by restarted GMRES over one forward product per iteration (solver_gmres.hip)
 int spmv_gmres(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t restart, int32_t max_iter, double rel_tol,
                int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
 {
-    SPMV_REQUIRE(ctx && A && b && x && iters && rel_resid, "spmv_gmres: null argument");
-    SPMV_REQUIRE(A->nrow == A->ncol, "spmv_gmres: the matrix (shard) is %d x %d, not square", A->nrow, A->ncol);
-    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "spmv_gmres: b has %lld and x %lld entries, the matrix %d rows", (long long)b->n,
-                 (long long)x->n, A->nrow);
-    SPMV_REQUIRE(b->n == 0 || b->d + b->n <= x->d || x->d + x->n <= b->d, "spmv_gmres: b and x must not overlap");
+    SPMV_TRY(check_square_solve(kGmresRules, ctx, A, b, x, max_iter, rel_tol, precond, iters, rel_resid));
     SPMV_REQUIRE(restart >= 0 && restart <= 64, "spmv_gmres: restart=%d, must be 1 .. 64 (0: 30)", restart);
-    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "spmv_gmres: max_iter=%d rel_tol=%g", max_iter, rel_tol);
-    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
-                 "spmv_gmres: unknown preconditioner %d", precond);
-    if (precond == SPMV_PRECOND_SYMGS)
-        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_gmres: the symmetric Gauss-Seidel preconditioner is not built for this solver");
-    if (precond == SPMV_PRECOND_JACOBI && A->format != SPMV_FMT_CSR)
-        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_gmres: the Jacobi preconditioner reads the diagonal of a CSR handle");
-    if (precond == SPMV_PRECOND_ILU0) SPMV_TRY(ilu0_check_handle(A, "spmv_gmres"));
-    // Jacobi reads the handle's own arrays; the plain solve needs the forward product alone and takes such a handle
-    SPMV_REQUIRE(!(precond == SPMV_PRECOND_JACOBI && A->nnz > 0 && (!A->b || !A->v)),
-                 "spmv_gmres: this handle gave up its CSR arrays (panel_keep_csr = 0): no diagonal for the Jacobi preconditioner");
+    SPMV_TRY(check_preconditioner(kGmresRules, A, precond));
     *iters     = 0;
     *rel_resid = 0.0;
     if (A->nrow == 0) return SPMV_OK;

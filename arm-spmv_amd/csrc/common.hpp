@@ -455,11 +455,13 @@ int  mat_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, 
 int  csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex = apply_extra{});
 bool writes_row_sums_in_one_launch(const spmv_mat* A);  // the product can store sum_i instead of y_i + sum_i at no extra launch
 bool adds_into_y_with_atomics(const spmv_mat* A);       // global_atomic_add_f64 on y, by the kernel (of the handle or its copies) that runs
-// solver.hip
+// The five solves' drivers.  Each is entered from its ABI entry (abi.hip) behind the argument checks and use_device, zeroes its
+// outputs, returns at an empty system, and shares its host side - the workspace that owns its device memory, the preconditioner's
+// set-up and application, the looks at its scalars - with the others through solver_host.hpp.
+// solver.hip: conjugate gradients for a symmetric positive definite A (precond: NONE, JACOBI, SYMGS, ILU0)
 int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
              int precond, int* iters, double* rel_resid);
 int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t n, double* device_out);
-int csr_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, int* device_flag);  // 1 / a_ii (csr_inv_diag_kernel); flag != 0: a zero or missing one
 // solver_multi.hip: k independent solves A x_c = b_c in one loop, B and X row-major (n x k); iters and rel_resid: host arrays of k
 int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B, double* X, int max_iter, double rel_tol,
                    int check_every, int precond, int32_t* iters, double* rel_resid);

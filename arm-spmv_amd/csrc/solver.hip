@@ -18,14 +18,16 @@
 // (tests/solver_ref.py, tests/test_gpu_solver_steps.py); overwrite and the fused dot of mat_apply_ex bit for bit on exact inputs
 // (tests/test_gpu_exact.py); the solution through the oracle's product (tests/test_gpu_solver.py).
 //
-// The workgroup sum (block_sum), the Jacobi set-up and the host's read of the scalars are solver_common.hpp's, shared with
-// solver_multi.hip and solver_cgls.hip.  spmv_cg's own dots stay slotted atomic adds in arrival order (common.hpp: kDotSlots).
+// The workgroup sum (block_sum) is solver_common.hpp's; the workspace, the preconditioner's set-up and application and the host's
+// read of the scalars are solver_host.hpp's, shared with the other four solvers.  spmv_cg's own dots stay slotted atomic adds in
+// arrival order (common.hpp: kDotSlots).
 #include <cmath>
 #include <cstdlib>
 #include <vector>
 
 #include "common.hpp"
 #include "solver_common.hpp"
+#include "solver_host.hpp"
 #include "wave.hpp"
 
 namespace spmv
@@ -122,26 +124,6 @@ __global__ __launch_bounds__(kBlock) void cg_init_kernel(int64_t n, const double
         slot_add(s->bb, t_bb);
         if (PRE) slot_add(s->rz[0], t_rz);
     }
-}
-
-// 1 / a_ii of a CSR handle (duplicates of the diagonal entry are summed, as the product would); flag != 0: a zero or
-// missing diagonal entry
-__global__ __launch_bounds__(kBlock) void csr_inv_diag_kernel(int nrow, int64_t row_begin, const int32_t* __restrict__ row_ptr,
-                                                              const int32_t* __restrict__ col, const double* __restrict__ val,
-                                                              double* __restrict__ dinv, int* __restrict__ flag)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= nrow) return;
-    double    d   = 0.0;
-    const int end = row_ptr[i + 1];
-    for (int j = row_ptr[i]; j < end; ++j)
-        if ((int64_t)col[j] == row_begin + i) d += val[j];
-    if (d == 0.0)
-    {
-        atomicOr(flag, 1);
-        d = 1.0;
-    }
-    dinv[i] = 1.0 / d;
 }
 
 // ---- three launches per iteration: the product (with p . A p riding along), the update, the direction --------------------------
@@ -363,84 +345,38 @@ int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t 
     return SPMV_OK;
 }
 
-// dinv[i] = 1 / a_ii of a CSR handle: the one launch of csr_inv_diag_kernel (through jacobi_inverse_diagonal, solver_common.hpp)
-int csr_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, int* device_flag)
-{
-    if (A->nrow == 0) return SPMV_OK;
-    hipLaunchKernelGGL(csr_inv_diag_kernel, dim3((unsigned)ceil_div(A->nrow, kBlock)), dim3(kBlock), 0, ctx->stream, (int)A->nrow,
-                       A->row_begin, A->a, A->b, A->v, dinv, device_flag);
-    SPMV_HIP(hipGetLastError());
-    return SPMV_OK;
-}
-
-// z = M^-1 r for the preconditioners that are launch sequences of their own, between the product and the updates: one symmetric
-// Gauss-Seidel sweep from z = 0 (symgs.hip) or the two triangular solves of ILU(0) (ilu0.hip)
-static int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const double* r, double* z)
-{
-    return precond == SPMV_PRECOND_ILU0 ? ilu0_apply(ctx, A, r, z) : symgs_sweep(ctx, A, r, z, true);
-}
-
 int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
              int precond, int* iters, double* rel_resid)
 {
-    const int64_t n = A->nrow;
-    *iters          = 0;
-    *rel_resid      = 0.0;
+    const char* const who = "spmv_cg";
+    const int64_t     n   = A->nrow;
+    *iters                = 0;
+    *rel_resid            = 0.0;
     if (n == 0) return SPMV_OK;
     hipStream_t st = ctx->stream;
-    double *    r = nullptr, *p = nullptr, *q = nullptr, *dinv = nullptr, *z = nullptr, *sv = nullptr, *u = nullptr;
-    CgScalars*  s = nullptr;
-    auto        release = [&]() {
-        if (sv) (void)hipFree(sv);
-        if (u) (void)hipFree(u);
-        if (z) (void)hipFree(z);
-        if (r) (void)hipFree(r);
-        if (p) (void)hipFree(p);
-        if (q) (void)hipFree(q);
-        if (s) (void)hipFree(s);
-        if (dinv) (void)hipFree(dinv);
-    };
-    if (precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0)
-    {
-        // one symmetric Gauss-Seidel sweep from z = 0 per iteration (symgs.hip), or z = U^-1 L^-1 r with the ILU(0) factors (ilu0.hip:
-        // L U = L D L^T for a symmetric A); either state is built once and stays in the handle
-        SPMV_TRY(precond == SPMV_PRECOND_ILU0 ? ilu0_setup(const_cast<spmv_mat*>(A)) : symgs_setup(const_cast<spmv_mat*>(A)));
-        if (hipMalloc(&z, sizeof(double) * (size_t)n) != hipSuccess)
-            SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg: out of device memory for the preconditioned residual (%lld entries)", (long long)n);
-    }
-    else if (precond)
-    {
-        // Jacobi: the diagonal the reference's containers carry "for SymGS" (include/matrix.h:36); taken from the CSR arrays
-        if (A->format != SPMV_FMT_CSR || !A->b || !A->v)
-            SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_cg: the Jacobi preconditioner reads the diagonal of a CSR handle");
-        if (hipMalloc(&dinv, sizeof(double) * (size_t)n) != hipSuccess)
-            SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg: out of device memory for the diagonal (%lld entries)", (long long)n);
-        const int rc_d = jacobi_inverse_diagonal(ctx, A, dinv, "spmv_cg");
-        if (rc_d != SPMV_OK)
-        {
-            release();
-            return rc_d;
-        }
-    }
-    if (hipMalloc(&r, sizeof(double) * (size_t)n) != hipSuccess || hipMalloc(&p, sizeof(double) * (size_t)n) != hipSuccess ||
-        hipMalloc(&q, sizeof(double) * (size_t)n) != hipSuccess || hipMalloc(&s, sizeof(CgScalars)) != hipSuccess)
-    {
-        release();
-        SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg: out of device memory for three work vectors of %lld entries", (long long)n);
-    }
-    // Two launches per iteration (cg_fused_kernel) unless an application stands between the product and the updates (symmetric
-    // Gauss-Seidel, ILU(0)) or SPMV_CG_THREE_LAUNCHES=1 asks for the textbook arrangement (A/B; read once per solve).
+    // z = M^-1 r is a vector of its own where an application stands between the product and the updates: one symmetric Gauss-Seidel
+    // sweep from z = 0 per iteration (symgs.hip), or z = U^-1 L^-1 r with the ILU(0) factors (ilu0.hip: L U = L D L^T for a
+    // symmetric A).  Two launches per iteration (cg_fused_kernel) unless there is one, or SPMV_CG_THREE_LAUNCHES=1 asks for the
+    // textbook arrangement (A/B; read once per solve).
+    const bool  given   = precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0, jacobi = precond == SPMV_PRECOND_JACOBI;
     const char* e_three = getenv("SPMV_CG_THREE_LAUNCHES");
-    const bool  fused   = !z && !(e_three && e_three[0] == '1');
-    if (fused && (hipMalloc(&sv, sizeof(double) * (size_t)n) != hipSuccess || (dinv && hipMalloc(&u, sizeof(double) * (size_t)n) != hipSuccess)))
-    {
-        release();
-        SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg: out of device memory for the work vectors of %lld entries", (long long)n);
-    }
+    const bool  fused   = !given && !(e_three && e_three[0] == '1');
+    // the pieces a run does not need stay null, which is how the kernels and the launches below tell the arrangements apart
+    double *       r = nullptr, *p = nullptr, *q = nullptr, *dinv = nullptr, *z = nullptr, *sv = nullptr, *u = nullptr;
+    CgScalars*     s = nullptr;
+    SolveWorkspace ws(ctx, who);
+    ws.piece(r, n);
+    ws.piece(p, n);
+    ws.piece(q, n);
+    if (given) ws.piece(z, n);
+    if (jacobi) ws.piece(dinv, n);  // the diagonal the reference's containers carry "for SymGS" (include/matrix.h:36)
+    if (fused) ws.piece(sv, n);
+    if (fused && jacobi) ws.piece(u, n);
+    SPMV_TRY(ws.allocate((void**)&s, sizeof(CgScalars)));
+    SPMV_TRY(setup_preconditioner(ctx, A, precond, dinv, who));
     const int  grid  = stream_grid(n);
-    const int  grid2 = stream_grid(std::max<int64_t>(1, n / 2));
-    const bool wide  = (((uintptr_t)x) & 15) == 0 && n >= 2;  // r, p, q are fresh allocations (256-byte aligned)
-    int        rc    = SPMV_OK;
+    const int  grid2 = pair_grid(n);
+    const bool wide  = wide_ok(x, n);  // the work vectors are pieces of the workspace (256-byte aligned)
     std::vector<double> hbuf(sizeof(CgScalars) / sizeof(double));
     CgScalars&          h = *reinterpret_cast<CgScalars*>(hbuf.data());
     auto                host_sum = [](const double* acc) {
@@ -450,201 +386,170 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
     };
     // ring < 0: everything (once, after the set-up); else the r.r accumulator of that ring slot and the status word
     auto      fetch = [&](int ring) -> int {
-        if (ring < 0) return read_scalars(ctx, &h, s, sizeof(CgScalars), "spmv_cg");
+        if (ring < 0) return read_scalars(ctx, &h, s, sizeof(CgScalars), who);
         // the status word is queued ahead of the slot's read, so that one wait serves both: a second wait per look was measured at
         // 10-20 us (profiles/solver_helpers_ab.txt).  Should queueing it fail, read_scalars reads it and reports
         if (hipMemcpyAsync(&h.status, &s->status, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
-            SPMV_TRY(read_scalars(ctx, &h.status, &s->status, sizeof(double), "spmv_cg"));
-        return read_scalars(ctx, h.rr[ring], s->rr[ring], sizeof(double) * kDotDoubles, "spmv_cg");
+            SPMV_TRY(read_scalars(ctx, &h.status, &s->status, sizeof(double), who));
+        return read_scalars(ctx, h.rr[ring], s->rr[ring], sizeof(double) * kDotDoubles, who);
     };
-    do
+    apply_extra first;
+    first.overwrite = true;
+    SPMV_TRY(mat_apply_ex(ctx, A, x, q, first));  // q = A x0
+    if (dinv)
+        hipLaunchKernelGGL(cg_init_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, b, q, r, p, s, dinv);
+    else
+        hipLaunchKernelGGL(cg_init_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, b, q, r, p, s, dinv);
+    if (z)
     {
-        if (hipMemsetAsync(s, 0, sizeof(CgScalars), st) != hipSuccess)
-        {
-            rc = SPMV_ERR_HIP;
-            break;
-        }
-        apply_extra first;
-        first.overwrite = true;
-        if ((rc = mat_apply_ex(ctx, A, x, q, first)) != SPMV_OK) break;  // q = A x0
-        if (dinv)
-            hipLaunchKernelGGL(cg_init_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, b, q, r, p, s, dinv);
-        else
-            hipLaunchKernelGGL(cg_init_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, b, q, r, p, s, dinv);
-        if (z)
-        {
-            // z_0 = M^-1 r_0, rz_0 = r_0 . z_0, p_0 = z_0
-            if ((rc = apply_preconditioner(ctx, A, precond, r, z)) != SPMV_OK) break;
-            if ((rc = vec_dot_accumulate(ctx, r, z, n, s->rz[0])) != SPMV_OK) break;
-            if (hipMemcpyAsync(p, z, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess)
-            {
-                rc = SPMV_ERR_HIP;
-                break;
-            }
-        }
+        // z_0 = M^-1 r_0, rz_0 = r_0 . z_0, p_0 = z_0
+        SPMV_TRY(apply_preconditioner(ctx, A, precond, r, z));
+        SPMV_TRY(vec_dot_accumulate(ctx, r, z, n, s->rz[0]));
+        SPMV_TRY(hip_step(hipMemcpyAsync(p, z, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st), who, "copying z into p"));
+    }
+    if (fused)
+    {
+        // s = A p starts at 0 (beta_0 = 0 multiplies it); the preconditioned residual u_0 = z_0 is what init left in p
+        SPMV_TRY(hip_step(hipMemsetAsync(sv, 0, sizeof(double) * (size_t)n, st), who, "clearing s"));
+        if (u) SPMV_TRY(hip_step(hipMemcpyAsync(u, p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st), who, "copying p into u"));
+    }
+    SPMV_TRY(fetch(-1));
+    const double bb    = host_sum(h.bb);
+    const double limit = rel_tol * rel_tol * bb;  // compare squared norms
+    double       rr    = host_sum(h.rr[0]);
+    int          k     = 0, rc = SPMV_OK;
+    if (!std::isfinite(bb) || !std::isfinite(rr))
+        SPMV_FAIL(SPMV_ERR_INVALID, "spmv_cg: b.b = %g, r0.r0 = %g: b, x0 or the matrix hold non-finite numbers", bb, rr);
+    if (!(bb > 0.0) || rr <= limit)
+    {
+        *rel_resid = bb > 0.0 ? sqrt(rr / bb) : 0.0;  // b = 0: x0 solves it if r = 0 (else the caller sees iters = 0)
+        return SPMV_OK;
+    }
+    if (fused)
+    {
+        const double floor_rr = 1e-28 * bb;
+        SPMV_TRY(write_scalars(ctx, &s->noise_floor, &floor_rr, sizeof(double), who, "writing the noise floor"));
+    }
+    const int every = std::max(1, check_every);
+    // one iteration = two (fused) or three launches on the stream (k enters the kernels only through k & 3 and k > 0)
+    auto iteration = [&](int kk) -> int {
         if (fused)
         {
-            // s = A p starts at 0 (beta_0 = 0 multiplies it); the preconditioned residual u_0 = z_0 is what init left in p
-            if (hipMemsetAsync(sv, 0, sizeof(double) * (size_t)n, st) != hipSuccess ||
-                (u && hipMemcpyAsync(u, p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st) != hipSuccess))
-            {
-                rc = SPMV_ERR_HIP;
-                break;
-            }
-        }
-        if ((rc = fetch(-1)) != SPMV_OK) break;
-        const double bb    = host_sum(h.bb);
-        const double limit = rel_tol * rel_tol * bb;  // compare squared norms
-        double       rr    = host_sum(h.rr[0]);
-        int          k     = 0;
-        if (!std::isfinite(bb) || !std::isfinite(rr))
-        {
-            set_error("spmv_cg: b.b = %g, r0.r0 = %g: b, x0 or the matrix hold non-finite numbers", bb, rr);
-            rc = SPMV_ERR_INVALID;
-            break;
-        }
-        if (!(bb > 0.0) || rr <= limit)
-        {
-            *rel_resid = bb > 0.0 ? sqrt(rr / bb) : 0.0;  // b = 0: x0 solves it if r = 0 (else the caller sees iters = 0)
-            break;
-        }
-        if (fused)
-        {
-            const double floor_rr = 1e-28 * bb;
-            if (hipMemcpyAsync(&s->noise_floor, &floor_rr, sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            {
-                rc = SPMV_ERR_HIP;
-                break;
-            }
-        }
-        const int every = std::max(1, check_every);
-        // one iteration = two (fused) or three launches on the stream (k enters the kernels only through k & 3 and k > 0)
-        auto iteration = [&](int kk) -> int {
-            if (fused)
-            {
-                const double* in = u ? u : r;  // the product runs on the (preconditioned) residual
-                apply_extra   fx;
-                fx.overwrite = true;
-                fx.dot_w     = in;
-                fx.dot_out   = s->pq[kk & 3];
-                SPMV_TRY(mat_apply_ex(ctx, A, in, q, fx));  // w = A u, delta_k = u . w
-                const int kq = kk & 3;  // (k & 3 is all the kernel looks at: a captured graph of four iterations replays at any k % 4 == 0)
+            const double* in = u ? u : r;  // the product runs on the (preconditioned) residual
+            apply_extra   fx;
+            fx.overwrite = true;
+            fx.dot_w     = in;
+            fx.dot_out   = s->pq[kk & 3];
+            SPMV_TRY(mat_apply_ex(ctx, A, in, q, fx));  // w = A u, delta_k = u . w
+            const int kq = kk & 3;  // (k & 3 is all the kernel looks at: a captured graph of four iterations replays at any k % 4 == 0)
 #define SPMV_CG_FUSED(PRE, WIDE, GRID) \
     hipLaunchKernelGGL((cg_fused_kernel<PRE, WIDE>), dim3(GRID), dim3(kBlock), 0, st, n, kq, q, u, p, sv, x, r, s, dinv)
-                if (dinv)
-                {
-                    if (wide) SPMV_CG_FUSED(true, true, grid2); else SPMV_CG_FUSED(true, false, grid);
-                }
-                else
-                {
-                    if (wide) SPMV_CG_FUSED(false, true, grid2); else SPMV_CG_FUSED(false, false, grid);
-                }
-#undef SPMV_CG_FUSED
-                return SPMV_OK;
+            if (dinv)
+            {
+                if (wide) SPMV_CG_FUSED(true, true, grid2); else SPMV_CG_FUSED(true, false, grid);
             }
-            apply_extra ex;
-            ex.overwrite = true;
-            ex.dot_w     = p;
-            ex.dot_out   = s->pq[kk & 3];
-            SPMV_TRY(mat_apply_ex(ctx, A, p, q, ex));  // q = A p, pq_k = p . q
+            else
+            {
+                if (wide) SPMV_CG_FUSED(false, true, grid2); else SPMV_CG_FUSED(false, false, grid);
+            }
+#undef SPMV_CG_FUSED
+            return SPMV_OK;
+        }
+        apply_extra ex;
+        ex.overwrite = true;
+        ex.dot_w     = p;
+        ex.dot_out   = s->pq[kk & 3];
+        SPMV_TRY(mat_apply_ex(ctx, A, p, q, ex));  // q = A p, pq_k = p . q
 #define SPMV_CG_UPDATE(ZK, WIDE, GRID) \
     hipLaunchKernelGGL((cg_update_kernel<ZK, WIDE>), dim3(GRID), dim3(kBlock), 0, st, n, kk, p, q, x, r, s, dinv)
 #define SPMV_CG_DIRECTION(ZK, WIDE, GRID, ZVEC) \
     hipLaunchKernelGGL((cg_direction_kernel<ZK, WIDE>), dim3(GRID), dim3(kBlock), 0, st, n, kk, ZVEC, p, s, dinv)
-            if (z)
-            {
-                SPMV_CG_UPDATE(Z::given, false, grid);
-                SPMV_TRY(apply_preconditioner(ctx, A, precond, r, z));
-                SPMV_TRY(vec_dot_accumulate(ctx, r, z, n, s->rz[(kk + 1) & 3]));
-                SPMV_CG_DIRECTION(Z::given, false, grid, z);
-            }
-            else if (dinv)
-            {
-                SPMV_CG_UPDATE(Z::jacobi, false, grid);
-                SPMV_CG_DIRECTION(Z::jacobi, false, grid, r);
-            }
-            else if (wide)
-            {
-                SPMV_CG_UPDATE(Z::r, true, grid2);
-                SPMV_CG_DIRECTION(Z::r, true, grid2, r);
-            }
-            else
-            {
-                SPMV_CG_UPDATE(Z::r, false, grid);
-                SPMV_CG_DIRECTION(Z::r, false, grid, r);
-            }
+        if (z)
+        {
+            SPMV_CG_UPDATE(Z::given, false, grid);
+            SPMV_TRY(apply_preconditioner(ctx, A, precond, r, z));
+            SPMV_TRY(vec_dot_accumulate(ctx, r, z, n, s->rz[(kk + 1) & 3]));
+            SPMV_CG_DIRECTION(Z::given, false, grid, z);
+        }
+        else if (dinv)
+        {
+            SPMV_CG_UPDATE(Z::jacobi, false, grid);
+            SPMV_CG_DIRECTION(Z::jacobi, false, grid, r);
+        }
+        else if (wide)
+        {
+            SPMV_CG_UPDATE(Z::r, true, grid2);
+            SPMV_CG_DIRECTION(Z::r, true, grid2, r);
+        }
+        else
+        {
+            SPMV_CG_UPDATE(Z::r, false, grid);
+            SPMV_CG_DIRECTION(Z::r, false, grid, r);
+        }
 #undef SPMV_CG_UPDATE
 #undef SPMV_CG_DIRECTION
-            return SPMV_OK;
-        };
-        // Between two looks at the residual nothing depends on the host, and the scalar slots repeat with period 4, so
-        // four iterations can be captured once into a hipGraph and replayed with one launch.  MEASURED SLOWER than the
-        // plain stream of launches on ROCm 7.2 (profiles/r01_tune_cg_graph.txt: 61 vs 23 us per iteration at n = 10^4,
-        // 214 vs 168 us at n = 4M), so it is off unless SPMV_CG_GRAPH=1 asks for it.
-        hipGraph_t     graph = nullptr;
-        hipGraphExec_t exec  = nullptr;
-        const char*    want_graph = getenv("SPMV_CG_GRAPH");
-        if (want_graph && want_graph[0] == '1' && every >= 4 && max_iter >= 4 &&
-            hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess)
+        return SPMV_OK;
+    };
+    // Between two looks at the residual nothing depends on the host, and the scalar slots repeat with period 4, so
+    // four iterations can be captured once into a hipGraph and replayed with one launch.  MEASURED SLOWER than the
+    // plain stream of launches on ROCm 7.2 (profiles/r01_tune_cg_graph.txt: 61 vs 23 us per iteration at n = 10^4,
+    // 214 vs 168 us at n = 4M), so it is off unless SPMV_CG_GRAPH=1 asks for it.
+    hipGraph_t     graph = nullptr;
+    hipGraphExec_t exec  = nullptr;
+    const char*    want_graph = getenv("SPMV_CG_GRAPH");
+    if (want_graph && want_graph[0] == '1' && every >= 4 && max_iter >= 4 &&
+        hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess)
+    {
+        int crc = SPMV_OK;
+        for (int kk = 0; kk < 4 && crc == SPMV_OK; ++kk) crc = iteration(kk);
+        const hipError_t e_end = hipStreamEndCapture(st, &graph);
+        if (crc != SPMV_OK || e_end != hipSuccess || graph == nullptr ||
+            hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess)
         {
-            int crc = SPMV_OK;
-            for (int kk = 0; kk < 4 && crc == SPMV_OK; ++kk) crc = iteration(kk);
-            const hipError_t e_end = hipStreamEndCapture(st, &graph);
-            if (crc != SPMV_OK || e_end != hipSuccess || graph == nullptr ||
-                hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess)
-            {
-                exec = nullptr;
-                (void)hipGetLastError();
-            }
+            exec = nullptr;
+            (void)hipGetLastError();
         }
-        while (k < max_iter)
+    }
+    while (k < max_iter)
+    {
+        const int until = std::min(max_iter, (k / every + 1) * every);  // the next look at the residual
+        if (exec && (k & 3) == 0 && k + 4 <= until)
         {
-            const int until = std::min(max_iter, (k / every + 1) * every);  // the next look at the residual
-            if (exec && (k & 3) == 0 && k + 4 <= until)
-            {
-                if (hipGraphLaunch(exec, st) != hipSuccess)
-                {
-                    rc = SPMV_ERR_HIP;
-                    set_error("spmv_cg: hipGraphLaunch failed: %s", hipGetErrorString(hipGetLastError()));
-                    break;
-                }
-                k += 4;
-                ++ctx->cg_graph_replays;
-            }
-            else
-            {
-                if ((rc = iteration(k)) != SPMV_OK) break;
-                ++k;
-            }
-            if (k % every == 0 || k == max_iter)
-            {
-                if ((rc = fetch(k & 3)) != SPMV_OK) break;
-                rr = host_sum(h.rr[k & 3]);
-                // the status word is only set with r != 0 (an exactly solved system ends the queued iterations quietly, see
-                // the update kernels); it is looked at first because a breakdown leaves the next r.r at its cleared 0
-                if (h.status == 2.0 || !std::isfinite(rr))
-                {
-                    set_error("spmv_cg: the residual is not finite at or before iteration %d (non-finite numbers in b, x0 or the matrix, or overflow)", k);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
-                if (h.status != 0.0)
-                {
-                    set_error("spmv_cg: p.Ap <= 0 (or r.M^-1 r <= 0) at or before iteration %d: the matrix is not positive definite", k);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
-                if (rr <= limit) break;
-            }
+            if ((rc = hip_step(hipGraphLaunch(exec, st), who, "hipGraphLaunch")) != SPMV_OK) break;
+            k += 4;
+            ++ctx->cg_graph_replays;
         }
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (rc == SPMV_OK && hipGetLastError() != hipSuccess) rc = SPMV_ERR_HIP;
-        *iters     = k;
-        *rel_resid = sqrt(rr / bb);
-    } while (0);
-    (void)hipStreamSynchronize(st);
-    release();
-    return rc;
+        else
+        {
+            if ((rc = iteration(k)) != SPMV_OK) break;
+            ++k;
+        }
+        if (k % every == 0 || k == max_iter)
+        {
+            if ((rc = fetch(k & 3)) != SPMV_OK) break;
+            rr = host_sum(h.rr[k & 3]);
+            // the status word is only set with r != 0 (an exactly solved system ends the queued iterations quietly, see
+            // the update kernels); it is looked at first because a breakdown leaves the next r.r at its cleared 0
+            if (h.status == 2.0 || !std::isfinite(rr))
+            {
+                set_error("spmv_cg: the residual is not finite at or before iteration %d (non-finite numbers in b, x0 or the matrix, or overflow)", k);
+                rc = SPMV_ERR_INVALID;
+                break;
+            }
+            if (h.status != 0.0)
+            {
+                set_error("spmv_cg: p.Ap <= 0 (or r.M^-1 r <= 0) at or before iteration %d: the matrix is not positive definite", k);
+                rc = SPMV_ERR_INVALID;
+                break;
+            }
+            if (rr <= limit) break;
+        }
+    }
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (rc == SPMV_OK) rc = hip_step(hipGetLastError(), who, "a launch of the iteration");
+    *iters     = k;
+    *rel_resid = sqrt(rr / bb);
+    return rc;  // (the workspace waits for the stream and frees)
 }
 }  // namespace spmv

@@ -53,6 +53,7 @@
 
 #include "common.hpp"
 #include "solver_common.hpp"
+#include "solver_host.hpp"
 #include "wave.hpp"
 
 namespace spmv
@@ -328,57 +329,41 @@ __global__ __launch_bounds__(kBlock) void bicg_direction_kernel(int64_t n, const
 int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                    int precond, int* iters, double* rel_resid)
 {
-    const int64_t n = A->nrow;
-    *iters     = 0;
-    *rel_resid = 0.0;
+    const char* const who = "spmv_bicgstab";
+    const int64_t     n   = A->nrow;
+    *iters                = 0;
+    *rel_resid            = 0.0;
     if (n == 0) return SPMV_OK;
     hipStream_t st  = ctx->stream;
     const bool  pre = precond == SPMV_PRECOND_JACOBI, ilu = precond == SPMV_PRECOND_ILU0;
-    if (ilu) SPMV_TRY(ilu0_setup(const_cast<spmv_mat*>(A)));  // once per handle and order; stays in the handle
-    // r, rhat, p, v, s, t (Jacobi: dinv, phat, shat; ILU(0): phat, shat) and the partial sums of two quantities: one allocation, every piece on a
-    // 256-byte boundary
-    const size_t sn   = ((size_t)n + 31) & ~(size_t)31;
-    const int    nvec = pre ? 9 : (ilu ? 8 : 6);
-    double*      work = nullptr;
-    BicgScalars* s    = nullptr;
-    auto         release = [&]() {
-        if (work) (void)hipFree(work);
-        if (s) (void)hipFree(s);
-    };
-    if (hipMalloc(&work, sizeof(double) * ((size_t)nvec * sn + 2 * (size_t)kMaxGrid)) != hipSuccess || hipMalloc(&s, sizeof(BicgScalars)) != hipSuccess)
-    {
-        release();
-        SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_bicgstab: out of device memory for the work vectors (%d x %lld entries)", nvec, (long long)n);
-    }
-    double *r = work, *rhat = work + sn, *p = work + 2 * sn, *v = work + 3 * sn, *sv = work + 4 * sn, *t = work + 5 * sn;
-    double *dinv = pre ? work + 6 * sn : nullptr, *phat = pre ? work + 7 * sn : (ilu ? work + 6 * sn : p),
-           *shat = pre ? work + 8 * sn : (ilu ? work + 7 * sn : sv);
-    double* part = work + (size_t)nvec * sn;
-    if (pre)
-    {
-        const int rc_d = jacobi_inverse_diagonal(ctx, A, dinv, "spmv_bicgstab");
-        if (rc_d != SPMV_OK)
-        {
-            release();
-            return rc_d;
-        }
-    }
-    const bool  wide_x = (((uintptr_t)x) & 15) == 0 && n >= 2, wide_b = (((uintptr_t)b) & 15) == 0 && n >= 2;
-    const int   grid   = stream_grid(std::max<int64_t>(1, n / 2));
+    // r, rhat, p, v, s, t (Jacobi: dinv, phat, shat; ILU(0): phat, shat) and the partial sums of two quantities
+    double *r, *rhat, *p, *v, *sv, *t, *dinv = nullptr, *phat = nullptr, *shat = nullptr, *part;
+    BicgScalars*   s = nullptr;
+    SolveWorkspace ws(ctx, who);
+    for (double** piece : {&r, &rhat, &p, &v, &sv, &t}) ws.piece(*piece, n);
+    if (pre) ws.piece(dinv, n);
+    if (pre || ilu) ws.piece(phat, n);
+    if (pre || ilu) ws.piece(shat, n);
+    ws.piece(part, 2 * (size_t)kMaxGrid);
+    SPMV_TRY(ws.allocate((void**)&s, sizeof(BicgScalars)));
+    SPMV_TRY(setup_preconditioner(ctx, A, precond, dinv, who));
+    if (!phat) phat = p, shat = sv;  // M = I: phat and shat are p and s themselves
+    const bool  wide_x = wide_ok(x, n), wide_b = wide_ok(b, n);
+    const int   grid   = pair_grid(n);
     const int   grid_x = wide_x ? grid : stream_grid(n), grid_b = wide_b ? grid : stream_grid(n);
     apply_extra over;
     over.overwrite = true;
     // the seven launches of an iteration (ILU(0): and the two applications phat = M^-1 p, shat = M^-1 s; in a quiet iteration they
     // run on the p and s that stand, which the update kernel then does not read)
     auto iteration = [&]() -> int {
-        if (ilu) SPMV_TRY(ilu0_apply(ctx, A, p, phat));
+        if (ilu) SPMV_TRY(apply_preconditioner(ctx, A, precond, p, phat));
         SPMV_TRY(mat_apply_ex(ctx, A, phat, v, over));
         hipLaunchKernelGGL(bicg_dot_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)rhat, (const double*)v, &s->rhv, part, s);
         if (pre)
             hipLaunchKernelGGL(bicg_half_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)r, (const double*)v, (const double*)dinv, sv, shat, s);
         else
             hipLaunchKernelGGL(bicg_half_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)r, (const double*)v, (const double*)dinv, sv, shat, s);
-        if (ilu) SPMV_TRY(ilu0_apply(ctx, A, sv, shat));
+        if (ilu) SPMV_TRY(apply_preconditioner(ctx, A, precond, sv, shat));
         SPMV_TRY(mat_apply_ex(ctx, A, shat, t, over));
         hipLaunchKernelGGL(bicg_dot_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)t, (const double*)sv, &s->ts, part, s);
         if (wide_x)
@@ -396,87 +381,69 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
         return SPMV_OK;
     };
     BicgScalars h;
-    auto        fetch = [&]() { return read_scalars(ctx, &h, s, sizeof(BicgScalars), "spmv_bicgstab"); };
-    int rc = SPMV_OK;
-    do
-    {
-        // s (and shat) are read by the second product of a quiet iteration that never wrote them
-        if (hipMemsetAsync(s, 0, sizeof(BicgScalars), st) != hipSuccess || hipMemsetAsync(sv, 0, sizeof(double) * (size_t)n, st) != hipSuccess ||
-            (pre && hipMemsetAsync(shat, 0, sizeof(double) * (size_t)n, st) != hipSuccess))
-        {
-            rc = SPMV_ERR_HIP;
-            break;
-        }
-        if ((rc = mat_apply_ex(ctx, A, x, v, over)) != SPMV_OK) break;  // v = A x0
+    auto        fetch = [&]() { return read_scalars(ctx, &h, s, sizeof(BicgScalars), who); };
+    // s (and shat) are read by the second product of a quiet iteration that never wrote them
+    SPMV_TRY(hip_step(hipMemsetAsync(sv, 0, sizeof(double) * (size_t)n, st), who, "clearing s"));
+    if (pre) SPMV_TRY(hip_step(hipMemsetAsync(shat, 0, sizeof(double) * (size_t)n, st), who, "clearing shat"));
+    SPMV_TRY(mat_apply_ex(ctx, A, x, v, over));  // v = A x0
 #define SPMV_BICG_INIT(WIDE, PRE)                                                                                                                  \
     hipLaunchKernelGGL((bicg_init_kernel<WIDE, PRE>), dim3(grid_b), dim3(kBlock), 0, st, n, b, (const double*)v, (const double*)dinv, r, rhat, p, phat, \
                        part, s)
-        if (wide_b)
-        {
-            if (pre) SPMV_BICG_INIT(true, true); else SPMV_BICG_INIT(true, false);
-        }
-        else
-        {
-            if (pre) SPMV_BICG_INIT(false, true); else SPMV_BICG_INIT(false, false);
-        }
+    if (wide_b)
+    {
+        if (pre) SPMV_BICG_INIT(true, true); else SPMV_BICG_INIT(true, false);
+    }
+    else
+    {
+        if (pre) SPMV_BICG_INIT(false, true); else SPMV_BICG_INIT(false, false);
+    }
 #undef SPMV_BICG_INIT
-        if ((rc = fetch()) != SPMV_OK) break;
-        const double bb = h.bb;
-        double       rr = h.rr;
-        if (!std::isfinite(bb) || !std::isfinite(rr))
+    SPMV_TRY(fetch());
+    const double bb = h.bb;
+    double       rr = h.rr;
+    if (!std::isfinite(bb) || !std::isfinite(rr))
+        SPMV_FAIL(SPMV_ERR_INVALID, "spmv_bicgstab: b.b = %g, r0.r0 = %g: b, x0 or the matrix hold non-finite numbers", bb, rr);
+    if (!(bb > 0.0)) return SPMV_OK;  // b = 0: x0 stays, as spmv_cg leaves it
+    const double limit = rel_tol * rel_tol * bb;  // squared norms are compared
+    int          k = 0, rc = SPMV_OK;
+    if (rr > limit && rr > 0.0 && max_iter > 0)
+    {
+        const double floor_rr = 1e-28 * bb;
+        SPMV_TRY(write_scalars(ctx, &s->floor_rr, &floor_rr, sizeof(double), who, "writing the noise floor"));
+        const int every = std::max(1, check_every);
+        while (k < max_iter)
         {
-            set_error("spmv_bicgstab: b.b = %g, r0.r0 = %g: b, x0 or the matrix hold non-finite numbers", bb, rr);
-            rc = SPMV_ERR_INVALID;
-            break;
-        }
-        if (!(bb > 0.0)) break;  // b = 0: x0 stays, as spmv_cg leaves it
-        const double limit = rel_tol * rel_tol * bb;  // squared norms are compared
-        int          k     = 0;
-        if (rr > limit && rr > 0.0 && max_iter > 0)
-        {
-            const double floor_rr = 1e-28 * bb;
-            if (hipMemcpyAsync(&s->floor_rr, &floor_rr, sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            if ((rc = iteration()) != SPMV_OK) break;
+            ++k;
+            if (k % every != 0 && k != max_iter) continue;
+            if ((rc = fetch()) != SPMV_OK) break;
+            rr = h.rr;
+            if (!std::isfinite(rr))
             {
-                rc = SPMV_ERR_HIP;
+                set_error("spmv_bicgstab: r.r is not finite at or before iteration %d (non-finite numbers in the matrix, or overflow)", k);
+                rc = SPMV_ERR_INVALID;
                 break;
             }
-            const int every = std::max(1, check_every);
-            while (k < max_iter)
+            // (a breakdown behind an iterate that is within the tolerance is no error: x holds that iterate)
+            if (rr <= limit || rr == 0.0) break;
+            if (h.status != 0)
             {
-                if ((rc = iteration()) != SPMV_OK) break;
-                ++k;
-                if (k % every != 0 && k != max_iter) continue;
-                if ((rc = fetch()) != SPMV_OK) break;
-                rr = h.rr;
-                if (!std::isfinite(rr))
-                {
-                    set_error("spmv_bicgstab: r.r is not finite at or before iteration %d (non-finite numbers in the matrix, or overflow)", k);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
-                // (a breakdown behind an iterate that is within the tolerance is no error: x holds that iterate)
-                if (rr <= limit || rr == 0.0) break;
-                if (h.status != 0)
-                {
-                    const char* what = h.status == kBicgRho ? "rho = rhat.r" : h.status == kBicgRhatV ? "rhat.v" : "omega = t.s / t.t";
-                    set_error("spmv_bicgstab: breakdown: %s is zero (or not finite) at or before iteration %d with a residual to speak of", what, k);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
-                if (!std::isfinite(h.rho))
-                {
-                    set_error("spmv_bicgstab: rho = rhat.r is not finite at or before iteration %d (overflow)", k);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
+                const char* what = h.status == kBicgRho ? "rho = rhat.r" : h.status == kBicgRhatV ? "rhat.v" : "omega = t.s / t.t";
+                set_error("spmv_bicgstab: breakdown: %s is zero (or not finite) at or before iteration %d with a residual to speak of", what, k);
+                rc = SPMV_ERR_INVALID;
+                break;
             }
-            if (rc == SPMV_OK && hipGetLastError() != hipSuccess) rc = SPMV_ERR_HIP;
+            if (!std::isfinite(h.rho))
+            {
+                set_error("spmv_bicgstab: rho = rhat.r is not finite at or before iteration %d (overflow)", k);
+                rc = SPMV_ERR_INVALID;
+                break;
+            }
         }
-        *iters     = k;
-        *rel_resid = sqrt(rr / bb);
-    } while (0);
-    (void)hipStreamSynchronize(st);
-    release();
-    return rc;
+        if (rc == SPMV_OK) rc = hip_step(hipGetLastError(), who, "a launch of the iteration");
+    }
+    *iters     = k;
+    *rel_resid = sqrt(rr / bb);
+    return rc;  // (the workspace waits for the stream and frees)
 }
 }  // namespace spmv

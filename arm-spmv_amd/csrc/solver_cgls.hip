@@ -43,6 +43,7 @@
 
 #include "common.hpp"
 #include "solver_common.hpp"
+#include "solver_host.hpp"
 #include "wave.hpp"
 
 namespace spmv
@@ -288,32 +289,28 @@ __global__ __launch_bounds__(kBlock) void cgls_direction_kernel(int64_t n, const
 int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                double damp, int* iters, double* rel_normal_resid, double* rel_resid)
 {
-    const int64_t nr = A->nrow, nc = A->ncol;
+    const char* const who = "spmv_cgls";
+    const int64_t     nr = A->nrow, nc = A->ncol;
     *iters            = 0;
     *rel_normal_resid = 0.0;
     *rel_resid        = 0.0;
     if (nr == 0 || nc == 0) return SPMV_OK;
     SPMV_TRY(transpose_setup(const_cast<spmv_mat*>(A)));  // (once; the transposed state is no part of the forward one)
     hipStream_t st = ctx->stream;
-    // r, q (nrow), p, s (ncol) and the partial sums of two quantities: one allocation, every piece on a 256-byte boundary
-    const size_t sr = ((size_t)nr + 31) & ~(size_t)31, sc = ((size_t)nc + 31) & ~(size_t)31;
-    double*      work = nullptr;
-    CglsScalars* s    = nullptr;
-    auto         release = [&]() {
-        if (work) (void)hipFree(work);
-        if (s) (void)hipFree(s);
-    };
-    if (hipMalloc(&work, sizeof(double) * (2 * sr + 2 * sc + 2 * (size_t)kMaxGrid)) != hipSuccess || hipMalloc(&s, sizeof(CglsScalars)) != hipSuccess)
-    {
-        release();
-        SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cgls: out of device memory for the work vectors (2 x %lld and 2 x %lld entries)", (long long)nr,
-                  (long long)nc);
-    }
-    double *r = work, *q = work + sr, *p = work + 2 * sr, *sv = work + 2 * sr + sc, *part = work + 2 * sr + 2 * sc;
-    const bool   wide_x = (((uintptr_t)x) & 15) == 0 && nc >= 2, wide_b = (((uintptr_t)b) & 15) == 0 && nr >= 2;
+    // r, q (nrow), p, s (ncol) and the partial sums of two quantities
+    double *       r, *q, *p, *sv, *part;
+    CglsScalars*   s = nullptr;
+    SolveWorkspace ws(ctx, who);
+    ws.piece(r, nr);
+    ws.piece(q, nr);
+    ws.piece(p, nc);
+    ws.piece(sv, nc);
+    ws.piece(part, 2 * (size_t)kMaxGrid);
+    SPMV_TRY(ws.allocate((void**)&s, sizeof(CglsScalars)));
+    const bool   wide_x = wide_ok(x, nc), wide_b = wide_ok(b, nr);
     const bool   damped = damp > 0.0;
     const double damp2  = damp * damp;
-    const int    grid_r = stream_grid(std::max<int64_t>(1, nr / 2)), grid_c = stream_grid(std::max<int64_t>(1, nc / 2));
+    const int    grid_r = pair_grid(nr), grid_c = pair_grid(nc);
     const int    grid_u = wide_x ? std::max(grid_r, grid_c) : std::max(grid_r, stream_grid(nc));
     apply_extra  over;
     over.overwrite = true;
@@ -342,85 +339,66 @@ int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int
         return SPMV_OK;
     };
     CglsScalars h;
-    auto        fetch = [&]() { return read_scalars(ctx, &h, s, sizeof(CglsScalars), "spmv_cgls"); };
-    int rc = SPMV_OK;
-    do
+    auto        fetch = [&]() { return read_scalars(ctx, &h, s, sizeof(CglsScalars), who); };
+    SPMV_TRY(hip_step(hipMemsetAsync(sv, 0, sizeof(double) * (size_t)nc, st), who, "clearing s"));
+    SPMV_TRY(transpose_apply(ctx, A, b, sv));  // s = A^T b
+    dot(nc, sv, &s->atb2);
+    SPMV_TRY(mat_apply_ex(ctx, A, x, q, over));  // q = A x0
+    if (wide_b)
+        hipLaunchKernelGGL(cgls_init_kernel<true>, dim3(grid_r), dim3(kBlock), 0, st, nr, b, (const double*)q, r, part, s);
+    else
+        hipLaunchKernelGGL(cgls_init_kernel<false>, dim3(stream_grid(nr)), dim3(kBlock), 0, st, nr, b, (const double*)q, r, part, s);
+    SPMV_TRY(behind_the_product());  // gamma = 0: s = A^T r0 - damp^2 x0, p = s, x and r as they are
+    SPMV_TRY(fetch());
+    const double bb = h.bb, atb2 = h.atb2;
+    double       gamma = h.gamma, rr = h.rr;
+    if (!std::isfinite(bb) || !std::isfinite(atb2) || !std::isfinite(gamma) || !std::isfinite(rr))
+        SPMV_FAIL(SPMV_ERR_INVALID, "spmv_cgls: b.b = %g, ||A^T b||^2 = %g, gamma_0 = %g, r0.r0 = %g: b, x0 or the matrix hold non-finite numbers", bb,
+                  atb2, gamma, rr);
+    if (!(atb2 > 0.0)) return SPMV_OK;  // A^T b = 0 (b = 0 among it): x0 stays, as spmv_cg leaves it at b.b = 0
+    const double limit = rel_tol * rel_tol * atb2;  // squared norms are compared
+    int          k = 0, rc = SPMV_OK;
+    if (gamma > limit && gamma > 0.0 && max_iter > 0)
     {
-        if (hipMemsetAsync(s, 0, sizeof(CglsScalars), st) != hipSuccess || hipMemsetAsync(sv, 0, sizeof(double) * (size_t)nc, st) != hipSuccess)
+        const double floor_gamma = 1e-28 * atb2;
+        SPMV_TRY(write_scalars(ctx, &s->floor_gamma, &floor_gamma, sizeof(double), who, "writing the noise floor"));
+        const int every = std::max(1, check_every);
+        while (k < max_iter)
         {
-            rc = SPMV_ERR_HIP;
-            break;
-        }
-        if ((rc = transpose_apply(ctx, A, b, sv)) != SPMV_OK) break;  // s = A^T b
-        dot(nc, sv, &s->atb2);
-        if ((rc = mat_apply_ex(ctx, A, x, q, over)) != SPMV_OK) break;  // q = A x0
-        if (wide_b)
-            hipLaunchKernelGGL(cgls_init_kernel<true>, dim3(grid_r), dim3(kBlock), 0, st, nr, b, (const double*)q, r, part, s);
-        else
-            hipLaunchKernelGGL(cgls_init_kernel<false>, dim3(stream_grid(nr)), dim3(kBlock), 0, st, nr, b, (const double*)q, r, part, s);
-        if ((rc = behind_the_product()) != SPMV_OK) break;  // gamma = 0: s = A^T r0 - damp^2 x0, p = s, x and r as they are
-        if ((rc = fetch()) != SPMV_OK) break;
-        const double bb = h.bb, atb2 = h.atb2;
-        double       gamma = h.gamma, rr = h.rr;
-        if (!std::isfinite(bb) || !std::isfinite(atb2) || !std::isfinite(gamma) || !std::isfinite(rr))
-        {
-            set_error("spmv_cgls: b.b = %g, ||A^T b||^2 = %g, gamma_0 = %g, r0.r0 = %g: b, x0 or the matrix hold non-finite numbers", bb, atb2,
-                      gamma, rr);
-            rc = SPMV_ERR_INVALID;
-            break;
-        }
-        if (!(atb2 > 0.0)) break;  // A^T b = 0 (b = 0 among it): x0 stays, as spmv_cg leaves it at b.b = 0
-        const double limit = rel_tol * rel_tol * atb2;  // squared norms are compared
-        int          k     = 0;
-        if (gamma > limit && gamma > 0.0 && max_iter > 0)
-        {
-            const double floor_gamma = 1e-28 * atb2;
-            if (hipMemcpyAsync(&s->floor_gamma, &floor_gamma, sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess)
+            if ((rc = mat_apply_ex(ctx, A, p, q, over)) != SPMV_OK) break;  // q = A p
+            dot(nr, q, &s->qq);
+            if ((rc = behind_the_product()) != SPMV_OK) break;
+            ++k;
+            if (k % every != 0 && k != max_iter) continue;
+            if ((rc = fetch()) != SPMV_OK) break;
+            gamma = h.gamma;
+            rr    = h.rr;
+            // the status word is set only with a gradient above the floor; it is looked at first
+            if (h.status == 2 || !std::isfinite(gamma))
             {
-                rc = SPMV_ERR_HIP;
+                set_error("spmv_cgls: gamma = s.s is not finite at or before iteration %d (non-finite numbers in b, x0 or the matrix, or overflow)", k);
+                rc = SPMV_ERR_INVALID;
                 break;
             }
-            const int every = std::max(1, check_every);
-            while (k < max_iter)
+            if (h.status != 0)
             {
-                if ((rc = mat_apply_ex(ctx, A, p, q, over)) != SPMV_OK) break;  // q = A p
-                dot(nr, q, &s->qq);
-                if ((rc = behind_the_product()) != SPMV_OK) break;
-                ++k;
-                if (k % every != 0 && k != max_iter) continue;
-                if ((rc = fetch()) != SPMV_OK) break;
-                gamma = h.gamma;
-                rr    = h.rr;
-                // the status word is set only with a gradient above the floor; it is looked at first
-                if (h.status == 2 || !std::isfinite(gamma))
-                {
-                    set_error("spmv_cgls: gamma = s.s is not finite at or before iteration %d (non-finite numbers in b, x0 or the matrix, or overflow)", k);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
-                if (h.status != 0)
-                {
-                    set_error("spmv_cgls: delta = q.q + damp^2 p.p <= 0 (or not finite) at or before iteration %d with a gradient to speak of", k);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
-                if (!std::isfinite(rr))
-                {
-                    set_error("spmv_cgls: r.r is not finite at or before iteration %d (overflow)", k);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
-                if (gamma <= limit || gamma == 0.0) break;
+                set_error("spmv_cgls: delta = q.q + damp^2 p.p <= 0 (or not finite) at or before iteration %d with a gradient to speak of", k);
+                rc = SPMV_ERR_INVALID;
+                break;
             }
-            if (rc == SPMV_OK && hipGetLastError() != hipSuccess) rc = SPMV_ERR_HIP;
+            if (!std::isfinite(rr))
+            {
+                set_error("spmv_cgls: r.r is not finite at or before iteration %d (overflow)", k);
+                rc = SPMV_ERR_INVALID;
+                break;
+            }
+            if (gamma <= limit || gamma == 0.0) break;
         }
-        *iters            = k;
-        *rel_normal_resid = sqrt(gamma / atb2);
-        *rel_resid        = sqrt(rr / bb);
-    } while (0);
-    (void)hipStreamSynchronize(st);
-    release();
-    return rc;
+        if (rc == SPMV_OK) rc = hip_step(hipGetLastError(), who, "a launch of the iteration");
+    }
+    *iters            = k;
+    *rel_normal_resid = sqrt(gamma / atb2);
+    *rel_resid        = sqrt(rr / bb);
+    return rc;  // (the workspace waits for the stream and frees)
 }
 }  // namespace spmv

@@ -1,5 +1,6 @@
-// solver_common.hpp — what spmv_cg (solver.hip), spmv_cg_multi (solver_multi.hip) and spmv_cgls (solver_cgls.hip) share: the sums
-// over a workgroup, the deterministic sum over a grid (the last-ticket pattern) and two host-side steps of every solve.
+// solver_common.hpp — the device side of what the five solvers share (spmv_cg in solver.hip, spmv_cg_multi in solver_multi.hip,
+// spmv_cgls in solver_cgls.hip, spmv_bicgstab in solver_bicgstab.hip, spmv_gmres in solver_gmres.hip): the sums over a workgroup
+// and the deterministic sum over a grid (the last-ticket pattern).  The host side they share is solver_host.hpp.
 #pragma once
 
 #include "common.hpp"
@@ -94,32 +95,5 @@ static __device__ __forceinline__ bool grid_totals(const double (&val)[NQ], doub
         total[q] = block_sum_all(acc, s_part);
     }
     return true;
-}
-
-// ---- host side -----------------------------------------------------------------------------------------------------------------
-// dinv[i] = 1 / a_ii of a CSR handle (csr_inverse_diagonal, solver.hip), synchronous; a zero or missing diagonal entry is `who`'s
-// error.  The flag is the first word of the context's scratch.
-inline int jacobi_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, const char* who)
-{
-    SPMV_TRY(ensure_scratch(ctx, 64));
-    int* flag   = (int*)ctx->scratch;
-    int  h_flag = 0;
-    (void)hipMemsetAsync(flag, 0, sizeof(int), ctx->stream);
-    SPMV_TRY(csr_inverse_diagonal(ctx, A, dinv, flag));
-    if (hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess || h_flag != 0)
-        SPMV_FAIL(SPMV_ERR_INVALID, "%s: the matrix has a zero or missing diagonal entry (Jacobi preconditioner)", who);
-    return SPMV_OK;
-}
-
-// the host's look at a solve's scalars on the device: copies `bytes` and waits for the stream
-inline int read_scalars(spmv_ctx* ctx, void* host, const void* dev, size_t bytes, const char* who)
-{
-    if (hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-    {
-        set_error("%s: reading the iteration scalars failed: %s", who, hipGetErrorString(hipGetLastError()));
-        return SPMV_ERR_HIP;
-    }
-    return SPMV_OK;
 }
 }  // namespace spmv

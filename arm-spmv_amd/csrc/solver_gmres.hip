@@ -66,6 +66,7 @@
 
 #include "common.hpp"
 #include "solver_common.hpp"
+#include "solver_host.hpp"
 #include "wave.hpp"
 
 namespace spmv
@@ -430,46 +431,28 @@ __global__ __launch_bounds__(kBlock) void gmres_xadd_kernel(int64_t n, const dou
 int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int restart, int max_iter, double rel_tol, int check_every,
                 int precond, int* iters, double* rel_resid)
 {
-    const int64_t n = A->nrow;
-    *iters     = 0;
-    *rel_resid = 0.0;
+    const char* const who = "spmv_gmres";
+    const int64_t     n   = A->nrow;
+    *iters                = 0;
+    *rel_resid            = 0.0;
     if (n == 0) return SPMV_OK;
     const int   m  = restart;
     hipStream_t st = ctx->stream;
     const bool  pre = precond == SPMV_PRECOND_JACOBI, ilu = precond == SPMV_PRECOND_ILU0;
-    if (ilu) SPMV_TRY(ilu0_setup(const_cast<spmv_mat*>(A)));  // once per handle and order; stays in the handle
-    // the basis (m + 1 vectors), w, z (Jacobi, ILU(0)), dinv (Jacobi) and the partial sums of m + 2 quantities: one allocation, every
-    // piece on a 256-byte boundary
-    const size_t sn   = ((size_t)n + 31) & ~(size_t)31;
-    const int    nvec = m + 2 + (pre ? 2 : (ilu ? 1 : 0));
-    const size_t work_bytes = sizeof(double) * ((size_t)nvec * sn + (size_t)(m + 2) * (size_t)kMaxGrid);
-    double*      work = nullptr;
-    GmresState*  s    = nullptr;
-    auto         release = [&]() {
-        if (work) (void)hipFree(work);
-        if (s) (void)hipFree(s);
-    };
-    if (hipMalloc(&work, work_bytes) != hipSuccess || hipMalloc(&s, sizeof(GmresState)) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        release();
-        SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_gmres: out of device memory for the basis and work vectors (%d x %lld entries, %zu bytes)", nvec,
-                  (long long)n, work_bytes);
-    }
-    double *V = work, *w = work + (size_t)(m + 1) * sn;
-    double *z = (pre || ilu) ? w + sn : nullptr, *dinv = pre ? w + 2 * sn : nullptr;
-    double* part = work + (size_t)nvec * sn;
-    if (pre)
-    {
-        const int rc_d = jacobi_inverse_diagonal(ctx, A, dinv, "spmv_gmres");
-        if (rc_d != SPMV_OK)
-        {
-            release();
-            return rc_d;
-        }
-    }
-    const bool  wide_x = (((uintptr_t)x) & 15) == 0 && n >= 2, wide_b = (((uintptr_t)b) & 15) == 0 && n >= 2;
-    const int   grid   = stream_grid(std::max<int64_t>(1, n / 2));
+    // the basis (m + 1 vectors, a padded vector apart), w, z (Jacobi, ILU(0)), dinv (Jacobi) and the partial sums of m + 2 quantities
+    const size_t   sn = SolveWorkspace::padded((size_t)n);
+    double *       V, *w, *z = nullptr, *dinv = nullptr, *part;
+    GmresState*    s = nullptr;
+    SolveWorkspace ws(ctx, who);
+    ws.piece(V, (size_t)(m + 1) * sn);
+    ws.piece(w, n);
+    if (pre || ilu) ws.piece(z, n);
+    if (pre) ws.piece(dinv, n);
+    ws.piece(part, (size_t)(m + 2) * (size_t)kMaxGrid);
+    SPMV_TRY(ws.allocate((void**)&s, sizeof(GmresState)));
+    SPMV_TRY(setup_preconditioner(ctx, A, precond, dinv, who));
+    const bool  wide_x = wide_ok(x, n), wide_b = wide_ok(b, n);
+    const int   grid   = pair_grid(n);
     const int   grid_x = wide_x ? grid : stream_grid(n), grid_b = wide_b ? grid : stream_grid(n);
     const int64_t vs   = (int64_t)sn;
     apply_extra over;
@@ -502,7 +485,7 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
     // quiet too).  last: no later column of this cycle reads v_{j+1}
     auto iteration = [&](int j, bool last) -> int {
         const double* vj = V + (size_t)j * sn;
-        if (ilu) SPMV_TRY(ilu0_apply(ctx, A, vj, z));
+        if (ilu) SPMV_TRY(apply_preconditioner(ctx, A, precond, vj, z));
         SPMV_TRY(mat_apply_ex(ctx, A, (pre || ilu) ? (const double*)z : vj, w, over));
         hipLaunchKernelGGL(gmres_dots_kernel, dim3(grid), dim3(kBlock), 0, st, n, vs, (const double*)V, (const double*)w, 1, part, s);
         hipLaunchKernelGGL(gmres_update_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, vs, (const double*)V, w, part, s);
@@ -519,7 +502,7 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
         if (ilu)
         {
             SPMV_GMRES_XUPDATE(true, 2, grid, w);
-            SPMV_TRY(ilu0_apply(ctx, A, w, z));
+            SPMV_TRY(apply_preconditioner(ctx, A, precond, w, z));
             if (wide_x)
                 hipLaunchKernelGGL(gmres_xadd_kernel<true>, dim3(grid_x), dim3(kBlock), 0, st, n, (const double*)z, x);
             else
@@ -539,91 +522,78 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
     GmresState* h = nullptr;  // the head alone is read
     alignas(GmresState) unsigned char h_bytes[kGmresHeadBytes];
     h = reinterpret_cast<GmresState*>(h_bytes);
-    auto fetch = [&]() { return read_scalars(ctx, h_bytes, s, kGmresHeadBytes, "spmv_gmres"); };
-    int rc = SPMV_OK;
-    do
+    auto fetch = [&]() { return read_scalars(ctx, h_bytes, s, kGmresHeadBytes, who); };
+    // the basis, w and z lie behind one another from V on; the product of a quiet iteration reads a basis vector or z that no launch
+    // of the cycle wrote
+    SPMV_TRY(hip_step(hipMemsetAsync(V, 0, sizeof(double) * (size_t)(m + 2 + (pre || ilu ? 1 : 0)) * sn, st), who, "clearing the basis"));
+    SPMV_TRY(start_cycle(true));
+    SPMV_TRY(fetch());
+    const double bb = h->bb;
+    double       res = h->res;
+    if (!std::isfinite(bb) || !std::isfinite(res))
+        SPMV_FAIL(SPMV_ERR_INVALID, "spmv_gmres: b.b = %g, beta = ||b - A x0|| = %g: b, x0 or the matrix hold non-finite numbers", bb, res);
+    if (!(bb > 0.0)) return SPMV_OK;  // b = 0: x0 stays, as spmv_cg leaves it
+    const double bnorm = sqrt(bb), limit = rel_tol * bnorm, floor_res = 1e-14 * bnorm;
+    int          k = 0, rc = SPMV_OK;
+    if (res > limit && res > 0.0 && max_iter > 0)
     {
-        // (the product of a quiet iteration reads a basis vector or z that no launch of the cycle wrote)
-        if (hipMemsetAsync(s, 0, sizeof(GmresState), st) != hipSuccess || hipMemsetAsync(work, 0, sizeof(double) * (size_t)(m + 2 + (pre || ilu ? 1 : 0)) * sn, st) != hipSuccess)
+        const int every = std::max(1, check_every);
+        int       j     = 0;
+        while (k < max_iter)
         {
-            rc = SPMV_ERR_HIP;
-            break;
-        }
-        if ((rc = start_cycle(true)) != SPMV_OK) break;
-        if ((rc = fetch()) != SPMV_OK) break;
-        const double bb = h->bb;
-        double       res = h->res;
-        if (!std::isfinite(bb) || !std::isfinite(res))
-        {
-            set_error("spmv_gmres: b.b = %g, beta = ||b - A x0|| = %g: b, x0 or the matrix hold non-finite numbers", bb, res);
-            rc = SPMV_ERR_INVALID;
-            break;
-        }
-        if (!(bb > 0.0)) break;  // b = 0: x0 stays, as spmv_cg leaves it
-        const double bnorm = sqrt(bb), limit = rel_tol * bnorm, floor_res = 1e-14 * bnorm;
-        int          k     = 0;
-        if (res > limit && res > 0.0 && max_iter > 0)
-        {
-            const int every = std::max(1, check_every);
-            int       j     = 0;
-            while (k < max_iter)
+            if ((rc = iteration(j, j + 1 == m || k + 1 == max_iter)) != SPMV_OK) break;
+            ++k;
+            ++j;
+            bool stop = false, landed = false;
+            if (k % every == 0 || k == max_iter)
             {
-                if ((rc = iteration(j, j + 1 == m || k + 1 == max_iter)) != SPMV_OK) break;
-                ++k;
-                ++j;
-                bool stop = false, landed = false;
-                if (k % every == 0 || k == max_iter)
+                if ((rc = fetch()) != SPMV_OK) break;
+                res = h->res;
+                if (h->status == kGmresNotFinite || !std::isfinite(res))
                 {
-                    if ((rc = fetch()) != SPMV_OK) break;
-                    res = h->res;
-                    if (h->status == kGmresNotFinite || !std::isfinite(res))
-                    {
-                        set_error("spmv_gmres: h or g is not finite at or before iteration %d (non-finite numbers in the matrix, or overflow)", k);
-                        rc = SPMV_ERR_INVALID;
-                        break;
-                    }
-                    // (a breakdown behind an iterate that is within the tolerance is no error)
-                    if (res <= limit || res == 0.0)
-                        stop = true;
-                    else if (h->status != 0)
-                    {
-                        set_error("spmv_gmres: breakdown: d = sqrt(h_j^2 + h_{j+1}^2) is zero at or before iteration %d with a residual to speak of "
-                                  "(the Krylov space is exhausted and the matrix is singular)", k);
-                        rc = SPMV_ERR_INVALID;
-                        break;
-                    }
-                    else if (k == max_iter)
-                        stop = true;
-                    else
-                        landed = res <= floor_res;  // the cycle ends here with the columns that stand
-                }
-                if (stop)
-                {
-                    rc = end_cycle();
+                    set_error("spmv_gmres: h or g is not finite at or before iteration %d (non-finite numbers in the matrix, or overflow)", k);
+                    rc = SPMV_ERR_INVALID;
                     break;
                 }
-                if (j == m || landed)
+                // (a breakdown behind an iterate that is within the tolerance is no error)
+                if (res <= limit || res == 0.0)
+                    stop = true;
+                else if (h->status != 0)
                 {
-                    // a restart: the recomputed ||r|| is what is compared
-                    if ((rc = end_cycle()) != SPMV_OK || (rc = start_cycle(false)) != SPMV_OK || (rc = fetch()) != SPMV_OK) break;
-                    j   = 0;
-                    res = h->res;
-                    if (!std::isfinite(res))
-                    {
-                        set_error("spmv_gmres: beta = ||b - A x|| is not finite at the restart behind iteration %d (overflow)", k);
-                        rc = SPMV_ERR_INVALID;
-                        break;
-                    }
-                    if (res <= limit || res == 0.0) break;
+                    set_error("spmv_gmres: breakdown: d = sqrt(h_j^2 + h_{j+1}^2) is zero at or before iteration %d with a residual to speak of "
+                              "(the Krylov space is exhausted and the matrix is singular)", k);
+                    rc = SPMV_ERR_INVALID;
+                    break;
                 }
+                else if (k == max_iter)
+                    stop = true;
+                else
+                    landed = res <= floor_res;  // the cycle ends here with the columns that stand
             }
-            if (rc == SPMV_OK && hipGetLastError() != hipSuccess) rc = SPMV_ERR_HIP;
+            if (stop)
+            {
+                rc = end_cycle();
+                break;
+            }
+            if (j == m || landed)
+            {
+                // a restart: the recomputed ||r|| is what is compared
+                if ((rc = end_cycle()) != SPMV_OK || (rc = start_cycle(false)) != SPMV_OK || (rc = fetch()) != SPMV_OK) break;
+                j   = 0;
+                res = h->res;
+                if (!std::isfinite(res))
+                {
+                    set_error("spmv_gmres: beta = ||b - A x|| is not finite at the restart behind iteration %d (overflow)", k);
+                    rc = SPMV_ERR_INVALID;
+                    break;
+                }
+                if (res <= limit || res == 0.0) break;
+            }
         }
-        *iters     = k;
-        *rel_resid = res / bnorm;
-    } while (0);
-    (void)hipStreamSynchronize(st);
-    release();
-    return rc;
+        if (rc == SPMV_OK) rc = hip_step(hipGetLastError(), who, "a launch of the iteration");
+    }
+    *iters     = k;
+    *rel_resid = res / bnorm;
+    return rc;  // (the workspace waits for the stream and frees)
 }
 }  // namespace spmv

@@ -1,0 +1,170 @@
+// solver_host.hip — the host side that the five solves share (solver_host.hpp): argument checks, the workspace, the preconditioner's
+// set-up and application.  One kernel: the inverse diagonal of a CSR handle, for Jacobi.
+#include "solver_host.hpp"
+
+namespace spmv
+{
+namespace
+{
+// 1 / a_ii of a CSR handle (duplicates of the diagonal entry are summed, as the product would); flag != 0: a zero or
+// missing diagonal entry
+__global__ __launch_bounds__(kBlock) void csr_inv_diag_kernel(int nrow, int64_t row_begin, const int32_t* __restrict__ row_ptr,
+                                                              const int32_t* __restrict__ col, const double* __restrict__ val,
+                                                              double* __restrict__ dinv, int* __restrict__ flag)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nrow) return;
+    double    d   = 0.0;
+    const int end = row_ptr[i + 1];
+    for (int j = row_ptr[i]; j < end; ++j)
+        if ((int64_t)col[j] == row_begin + i) d += val[j];
+    if (d == 0.0)
+    {
+        atomicOr(flag, 1);
+        d = 1.0;
+    }
+    dinv[i] = 1.0 / d;
+}
+
+// dinv[i] = 1 / a_ii; the flag is the first word of the context's scratch
+int jacobi_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, const char* who)
+{
+    SPMV_TRY(ensure_scratch(ctx, 64));
+    int* flag   = (int*)ctx->scratch;
+    int  h_flag = 0;
+    (void)hipMemsetAsync(flag, 0, sizeof(int), ctx->stream);
+    hipLaunchKernelGGL(csr_inv_diag_kernel, dim3((unsigned)ceil_div(A->nrow, kBlock)), dim3(kBlock), 0, ctx->stream, (int)A->nrow,
+                       A->row_begin, A->a, A->b, A->v, dinv, flag);
+    SPMV_HIP(hipGetLastError());
+    if (hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess || h_flag != 0)
+        SPMV_FAIL(SPMV_ERR_INVALID, "%s: the matrix has a zero or missing diagonal entry (Jacobi preconditioner)", who);
+    return SPMV_OK;
+}
+}  // namespace
+
+// ---- argument checks -----------------------------------------------------------------------------------------------------------
+bool vectors_disjoint(const spmv_vec* b, const spmv_vec* x)
+{
+    return b->n == 0 || x->n == 0 || b->d + b->n <= x->d || x->d + x->n <= b->d;
+}
+
+int check_limits(const char* who, int max_iter, double rel_tol)
+{
+    SPMV_REQUIRE(max_iter >= 0 && rel_tol >= 0.0, "%s: max_iter=%d rel_tol=%g", who, max_iter, rel_tol);
+    return SPMV_OK;
+}
+
+int check_known_preconditioner(const char* who, int precond)
+{
+    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
+                 "%s: unknown preconditioner %d", who, precond);
+    return SPMV_OK;
+}
+
+int check_square_solve(const solver_rules& S, const spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, const spmv_vec* x, int max_iter,
+                       double rel_tol, int precond, const int32_t* iters, const double* rel_resid)
+{
+    SPMV_REQUIRE(ctx && A && b && x && iters && rel_resid, "%s: null argument", S.who);
+    SPMV_REQUIRE(A->nrow == A->ncol, "%s: %s is %d x %d, not square", S.who, S.matrix, A->nrow, A->ncol);
+    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "%s: b has %lld and x %lld entries, the matrix %d rows", S.who, (long long)b->n,
+                 (long long)x->n, A->nrow);
+    if (S.alias_only)
+        SPMV_REQUIRE(b->d != x->d || x->n == 0, "%s: b and x must not alias", S.who);
+    else
+        SPMV_REQUIRE(vectors_disjoint(b, x), "%s: b and x must not overlap", S.who);
+    SPMV_TRY(check_limits(S.who, max_iter, rel_tol));
+    return check_known_preconditioner(S.who, precond);
+}
+
+int check_preconditioner(const solver_rules& S, const spmv_mat* A, int precond)
+{
+    if (precond == SPMV_PRECOND_SYMGS && S.symgs_not_built_for)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the symmetric Gauss-Seidel preconditioner is not built for %s", S.who, S.symgs_not_built_for);
+    if (precond == SPMV_PRECOND_ILU0)
+    {
+        if (S.ilu0_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the ILU(0) preconditioner is not built for %s", S.who, S.ilu0_not_built_for);
+        return ilu0_check_handle(A, S.who);
+    }
+    if (precond != SPMV_PRECOND_JACOBI) return SPMV_OK;
+    // Jacobi reads the diagonal from the handle's own CSR arrays (the plain solve needs the product alone and takes a handle that
+    // released them)
+    const bool gone = !A->b || !A->v;
+    if (A->format != SPMV_FMT_CSR || (S.jacobi_arrays == solver_rules::jacobi_arrays_unsupported && gone))
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the Jacobi preconditioner reads the diagonal of a CSR handle", S.who);
+    SPMV_REQUIRE(!(S.jacobi_arrays == solver_rules::jacobi_arrays_invalid && A->nnz > 0 && gone),
+                 "%s: this handle gave up its CSR arrays (panel_keep_csr = 0): no diagonal for the Jacobi preconditioner", S.who);
+    return SPMV_OK;
+}
+
+// ---- errors carry text ---------------------------------------------------------------------------------------------------------
+int hip_step(hipError_t e, const char* who, const char* step)
+{
+    if (e == hipSuccess) return SPMV_OK;
+    SPMV_FAIL(SPMV_ERR_HIP, "%s: %s failed: %s", who, step, hipGetErrorString(e));
+}
+
+int read_scalars(spmv_ctx* ctx, void* host, const void* dev, size_t bytes, const char* who)
+{
+    hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return hip_step(e, who, "reading the iteration scalars");
+}
+
+int write_scalars(spmv_ctx* ctx, void* dev, const void* host, size_t bytes, const char* who, const char* step)
+{
+    hipError_t e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return hip_step(e, who, step);
+}
+
+// ---- the workspace -------------------------------------------------------------------------------------------------------------
+void SolveWorkspace::piece(double*& p, size_t doubles)
+{
+    if (npieces_ < kMaxPieces)
+    {
+        where_[npieces_] = &p;
+        at_[npieces_]    = doubles_;
+    }
+    ++npieces_;  // (one too many is allocate()'s error)
+    doubles_ += padded(doubles);
+}
+
+int SolveWorkspace::allocate(void** scalars, size_t scalar_bytes)
+{
+    SPMV_REQUIRE(npieces_ <= kMaxPieces, "%s: %d pieces of work memory, the workspace holds %d", who_, npieces_, kMaxPieces);
+    const size_t bytes = sizeof(double) * doubles_;
+    if (hipMalloc(&slab_, bytes) != hipSuccess || hipMalloc(&scalars_, scalar_bytes) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        SPMV_FAIL(SPMV_ERR_ALLOC, "%s: out of device memory for the work vectors and scalars (%zu + %zu bytes)", who_, bytes, scalar_bytes);
+    }
+    for (int i = 0; i < npieces_; ++i) *where_[i] = slab_ + at_[i];
+    *scalars = scalars_;
+    return hip_step(hipMemsetAsync(scalars_, 0, scalar_bytes, ctx_->stream), who_, "clearing the iteration scalars");
+}
+
+SolveWorkspace::~SolveWorkspace()
+{
+    (void)hipStreamSynchronize(ctx_->stream);
+    if (slab_) (void)hipFree(slab_);
+    if (scalars_) (void)hipFree(scalars_);
+}
+
+// ---- the preconditioner --------------------------------------------------------------------------------------------------------
+int setup_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, double* dinv, const char* who)
+{
+    switch (precond)
+    {
+        case SPMV_PRECOND_JACOBI: return jacobi_inverse_diagonal(ctx, A, dinv, who);
+        case SPMV_PRECOND_SYMGS: return symgs_setup(const_cast<spmv_mat*>(A));
+        case SPMV_PRECOND_ILU0: return ilu0_setup(const_cast<spmv_mat*>(A));
+        default: return SPMV_OK;
+    }
+}
+
+int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const double* r, double* z)
+{
+    return precond == SPMV_PRECOND_ILU0 ? ilu0_apply(ctx, A, r, z) : symgs_sweep(ctx, A, r, z, true);
+}
+}  // namespace spmv

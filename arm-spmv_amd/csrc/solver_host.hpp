@@ -1,0 +1,87 @@
+// solver_host.hpp — the host side that the five solves share (spmv_cg, spmv_cg_multi, spmv_cgls, spmv_bicgstab, spmv_gmres): the
+// argument checks of their ABI entries, the owner of a solve's device memory, the preconditioner's set-up and application, and the
+// small questions every driver asks about a vector (may it go in 16-byte accesses, how many workgroups).  Defined in
+// solver_host.hip; the device side of what the solvers share is solver_common.hpp.
+#pragma once
+
+#include "common.hpp"
+
+namespace spmv
+{
+// ---- argument checks: on the host, before the device is touched (abi.hip) ------------------------------------------------------
+// What a solver's refusals depend on.  Every message starts with `who`.
+struct solver_rules
+{
+    const char* who;
+    const char* matrix;               // the noun of "is %d x %d, not square": "the matrix" or "the matrix (shard)"
+    bool        alias_only;           // b and x are refused where they start at the same address (spmv_cg), not where their ranges overlap
+    const char* symgs_not_built_for;  // nullptr: symmetric Gauss-Seidel is built; else the end of the refusal
+    const char* ilu0_not_built_for;   // nullptr: ILU(0) is built (ilu0_check_handle decides on the handle); else the end of the refusal
+    enum
+    {
+        jacobi_arrays_elsewhere,    // the entry checks the handle's arrays itself, for its product
+        jacobi_arrays_unsupported,  // arrays gone: UNSUPPORTED, as a handle that is not CSR (spmv_cg)
+        jacobi_arrays_invalid       // arrays gone: INVALID, "gave up its CSR arrays"
+    } jacobi_arrays;
+};
+
+bool vectors_disjoint(const spmv_vec* b, const spmv_vec* x);  // an empty vector overlaps nothing
+int  check_limits(const char* who, int max_iter, double rel_tol);
+int  check_known_preconditioner(const char* who, int precond);
+// the square single-vector solvers: null arguments, square, the lengths of b and x, alias / overlap, limits, a known preconditioner
+int check_square_solve(const solver_rules& S, const spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, const spmv_vec* x, int max_iter,
+                       double rel_tol, int precond, const int32_t* iters, const double* rel_resid);
+// a known preconditioner that this solver does not take, or not on this handle
+int check_preconditioner(const solver_rules& S, const spmv_mat* A, int precond);
+
+// ---- errors carry text ---------------------------------------------------------------------------------------------------------
+// SPMV_OK, or SPMV_ERR_HIP with "<who>: <step> failed: <HIP's words>" as the last error
+int hip_step(hipError_t e, const char* who, const char* step);
+// the host's look at a solve's scalars on the device: copies `bytes` and waits for the stream
+int read_scalars(spmv_ctx* ctx, void* host, const void* dev, size_t bytes, const char* who);
+// the host's word to the device between two looks (`step` names it): copies `bytes` and waits for the stream
+int write_scalars(spmv_ctx* ctx, void* dev, const void* host, size_t bytes, const char* who, const char* step);
+
+// ---- the workspace: one owner of a solve's device memory -----------------------------------------------------------------------
+// A driver names its pieces (piece), then allocate() makes one slab and the solver's scalars struct (cleared on the stream) and
+// points every piece into the slab, in the order named, each on a 256-byte boundary.  However the solve returns, the destructor
+// waits for the stream and frees both.  A piece that was never named stays the nullptr its pointer was.
+struct SolveWorkspace
+{
+    SolveWorkspace(spmv_ctx* ctx, const char* who) : ctx_(ctx), who_(who) {}
+    SolveWorkspace(const SolveWorkspace&)            = delete;
+    SolveWorkspace& operator=(const SolveWorkspace&) = delete;
+    ~SolveWorkspace();
+
+    // doubles from one piece's start to the next one's: the stride of vectors that share a piece
+    static size_t padded(size_t doubles) { return (doubles + 31) & ~(size_t)31; }
+    void          piece(double*& p, size_t doubles);
+    int           allocate(void** scalars, size_t scalar_bytes);
+
+private:
+    static constexpr int kMaxPieces = 12;
+    spmv_ctx*   ctx_;
+    const char* who_;
+    double**    where_[kMaxPieces];
+    size_t      at_[kMaxPieces];
+    int         npieces_ = 0;
+    size_t      doubles_ = 0;
+    double*     slab_    = nullptr;
+    void*       scalars_ = nullptr;
+};
+
+// ---- the preconditioner --------------------------------------------------------------------------------------------------------
+// Before a solve's first launch: the state that stays in the handle (symgs_setup, ilu0_setup: built once), or dinv[i] = 1 / a_ii of
+// a CSR handle for Jacobi (synchronous; a zero or missing diagonal entry is `who`'s error).  SPMV_PRECOND_NONE: nothing.
+int setup_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, double* dinv, const char* who);
+// z = M^-1 r for the preconditioners that are launch sequences of their own: the two triangular solves of ILU(0) (ilu0.hip), or one
+// symmetric Gauss-Seidel sweep from z = 0 (symgs.hip)
+int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const double* r, double* z);
+
+// ---- width and grids -----------------------------------------------------------------------------------------------------------
+inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// n doubles at p may go in 16-byte accesses, two elements per lane (an odd last element by one extra lane)
+inline bool wide_ok(const double* p, int64_t n) { return aligned16(p) && n >= 2; }
+// workgroups of a grid-stride kernel over n elements, two per lane
+inline int pair_grid(int64_t n) { return stream_grid(std::max<int64_t>(1, n / 2)); }
+}  // namespace spmv

@@ -36,6 +36,7 @@
 
 #include "common.hpp"
 #include "solver_common.hpp"
+#include "solver_host.hpp"
 #include "wave.hpp"
 
 namespace spmv
@@ -364,7 +365,8 @@ int log2_pow2_at_least(int v)
 int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B, double* X, int max_iter, double rel_tol,
                    int check_every, int precond, int32_t* iters, double* rel_resid)
 {
-    const int64_t n = A->nrow;
+    const char* const who = "spmv_cg_multi";
+    const int64_t     n   = A->nrow;
     for (int c = 0; c < k; ++c)
     {
         iters[c]     = 0;
@@ -375,55 +377,28 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
     const size_t nk = (size_t)n * (size_t)k;
     const bool   pre = precond == SPMV_PRECOND_JACOBI;
     // wide: 16-byte accesses, two columns per lane - every row then starts on a 16-byte boundary (k even) of 16-byte aligned arrays
-    const bool wide    = (k % 2) == 0 && ((((uintptr_t)X) | ((uintptr_t)B)) & 15) == 0;
+    const bool wide    = (k % 2) == 0 && aligned16(X) && aligned16(B);
     const int  kp_log2 = log2_pow2_at_least(wide ? k / 2 : k);
     const int  kc_log2 = log2_pow2_at_least(k);
     const int  rpb     = kBlock >> kp_log2;
     const int  grid    = (int)std::max<int64_t>(1, std::min<int64_t>(kCgmMaxGrid, ceil_div(n, rpb)));
-    double *   work = nullptr, *dinv = nullptr, *part = nullptr;
-    CgmScalars* s = nullptr;
-    auto        release = [&]() {
-        if (work) (void)hipFree(work);
-        if (dinv) (void)hipFree(dinv);
-        if (part) (void)hipFree(part);
-        if (s) (void)hipFree(s);
-    };
-    if (pre)
-    {
-        if (hipMalloc(&dinv, sizeof(double) * (size_t)n) != hipSuccess)
-            SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg_multi: out of device memory for the diagonal (%lld entries)", (long long)n);
-        const int rc_d = jacobi_inverse_diagonal(ctx, A, dinv, "spmv_cg_multi");
-        if (rc_d != SPMV_OK)
-        {
-            release();
-            return rc_d;
-        }
-    }
-    // R, P, S, W and (Jacobi) U: one allocation, every vector on a 256-byte boundary
-    const size_t vec_stride = (nk + 31) & ~(size_t)31;
-    const int    nvec       = pre ? 5 : 4;
-    if (hipMalloc(&work, sizeof(double) * vec_stride * nvec) != hipSuccess || hipMalloc(&s, sizeof(CgmScalars)) != hipSuccess ||
-        hipMalloc(&part, sizeof(double) * 3 * (size_t)grid * k) != hipSuccess)
-    {
-        release();
-        SPMV_FAIL(SPMV_ERR_ALLOC, "spmv_cg_multi: out of device memory for %d work vectors of %lld x %d entries", nvec, (long long)n, k);
-    }
-    double *R = work, *P = work + vec_stride, *S = work + 2 * vec_stride, *W = work + 3 * vec_stride;
-    double* U = pre ? work + 4 * vec_stride : R;
-    int     rc = SPMV_OK;
+    // R, P, S, W, (Jacobi) U and dinv, and the partial sums of three quantities per column
+    double *       R, *P, *S, *W, *U = nullptr, *dinv = nullptr, *part;
+    CgmScalars*    s = nullptr;
+    SolveWorkspace ws(ctx, who);
+    for (double** piece : {&R, &P, &S, &W}) ws.piece(*piece, nk);
+    if (pre) ws.piece(U, nk);
+    if (pre) ws.piece(dinv, n);
+    ws.piece(part, 3 * (size_t)grid * k);
+    SPMV_TRY(ws.allocate((void**)&s, sizeof(CgmScalars)));
+    SPMV_TRY(setup_preconditioner(ctx, A, precond, dinv, who));
+    if (!U) U = R;  // M = I: the preconditioned residual is the residual itself
     CgmScalars           h;
     std::vector<int32_t> frozen(kCgmMaxK, 0);
     std::vector<double>  limit(k), rr(k);
-    auto fetch = [&]() { return read_scalars(ctx, &h, s, sizeof(CgmScalars), "spmv_cg_multi"); };
-    auto freeze = [&]() -> int {  // the host's flags to the device, before the next iteration is queued
-        if (hipMemcpyAsync(s->frozen, frozen.data(), sizeof(int32_t) * kCgmMaxK, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-        {
-            set_error("spmv_cg_multi: writing the column flags failed: %s", hipGetErrorString(hipGetLastError()));
-            return SPMV_ERR_HIP;
-        }
-        return SPMV_OK;
-    };
+    auto fetch = [&]() { return read_scalars(ctx, &h, s, sizeof(CgmScalars), who); };
+    // the host's flags to the device, before the next iteration is queued
+    auto freeze = [&]() { return write_scalars(ctx, s->frozen, frozen.data(), sizeof(int32_t) * kCgmMaxK, who, "writing the column flags"); };
 #define SPMV_CGM_LAUNCH(KERNEL, ...)                                                                                      \
     do                                                                                                                    \
     {                                                                                                                     \
@@ -444,91 +419,78 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
         else                                                                                                                  \
             hipLaunchKernelGGL((KERNEL<false, 1>), dim3(grid), dim3(kBlock), 0, st, n, (int)k, kp_log2, kc_log2, __VA_ARGS__); \
     } while (0)
-    do
+    SPMV_TRY(spmm_apply(ctx, A, k, X, W, true));  // W = A X0
+    SPMV_CGM_LAUNCH_PRE(cgm_init_kernel, B, (const double*)W, R, U, P, S, (const double*)dinv, part, s);
+    SPMV_TRY(fetch());
+    int live = 0;
+    for (int c = 0; c < k; ++c)
     {
-        if (hipMemsetAsync(s, 0, sizeof(CgmScalars), st) != hipSuccess)
+        const double bb = h.bb[c];
+        rr[c]           = h.rr[c];
+        limit[c]        = rel_tol * rel_tol * bb;  // squared norms are compared
+        if (!std::isfinite(bb) || !std::isfinite(rr[c]))
+            SPMV_FAIL(SPMV_ERR_INVALID, "spmv_cg_multi: column %d: b.b = %g, r0.r0 = %g: b, x0 or the matrix hold non-finite numbers", c, bb, rr[c]);
+        if (!(bb > 0.0) || rr[c] <= limit[c])
         {
-            rc = SPMV_ERR_HIP;
-            break;
+            // b_c = 0: x0 stays (spmv_cg's rule); else x0 already solves the system to rel_tol
+            frozen[c]    = 1;
+            rel_resid[c] = bb > 0.0 ? sqrt(rr[c] / bb) : 0.0;
         }
-        if ((rc = spmm_apply(ctx, A, k, X, W, true)) != SPMV_OK) break;  // W = A X0
-        SPMV_CGM_LAUNCH_PRE(cgm_init_kernel, B, (const double*)W, R, U, P, S, (const double*)dinv, part, s);
+        else
+            ++live;
+    }
+    if (live == 0) return SPMV_OK;
+    if (live < k) SPMV_TRY(freeze());
+    const int     every = std::max(1, check_every);
+    const double* in    = U;  // the product runs on the (preconditioned) residual
+    int           j = 0, rc = SPMV_OK;
+    while (j < max_iter && live > 0)
+    {
+        if ((rc = spmm_apply(ctx, A, k, in, W, true)) != SPMV_OK) break;  // W = A U
+        SPMV_CGM_LAUNCH(cgm_dots_kernel, in, (const double*)W, part, s);
+        SPMV_CGM_LAUNCH_PRE(cgm_fused_kernel, (const double*)W, U, P, S, X, R, (const double*)dinv, part, s);
+        ++j;
+        if (j % every != 0 && j != max_iter) continue;
         if ((rc = fetch()) != SPMV_OK) break;
-        int live = 0;
-        for (int c = 0; c < k && rc == SPMV_OK; ++c)
-        {
-            const double bb = h.bb[c];
-            rr[c]           = h.rr[c];
-            limit[c]        = rel_tol * rel_tol * bb;  // squared norms are compared
-            if (!std::isfinite(bb) || !std::isfinite(rr[c]))
-            {
-                set_error("spmv_cg_multi: column %d: b.b = %g, r0.r0 = %g: b, x0 or the matrix hold non-finite numbers", c, bb, rr[c]);
-                rc = SPMV_ERR_INVALID;
-            }
-            else if (!(bb > 0.0) || rr[c] <= limit[c])
-            {
-                // b_c = 0: x0 stays (spmv_cg's rule); else x0 already solves the system to rel_tol
-                frozen[c]    = 1;
-                rel_resid[c] = bb > 0.0 ? sqrt(rr[c] / bb) : 0.0;
-            }
-            else
-                ++live;
-        }
-        if (rc != SPMV_OK || live == 0) break;
-        if (live < k && (rc = freeze()) != SPMV_OK) break;
-        const int     every = std::max(1, check_every);
-        const double* in    = U;  // the product runs on the (preconditioned) residual
-        int           j     = 0;
-        while (j < max_iter && live > 0)
-        {
-            if ((rc = spmm_apply(ctx, A, k, in, W, true)) != SPMV_OK) break;  // W = A U
-            SPMV_CGM_LAUNCH(cgm_dots_kernel, in, (const double*)W, part, s);
-            SPMV_CGM_LAUNCH_PRE(cgm_fused_kernel, (const double*)W, U, P, S, X, R, (const double*)dinv, part, s);
-            ++j;
-            if (j % every != 0 && j != max_iter) continue;
-            if ((rc = fetch()) != SPMV_OK) break;
-            bool changed = false;
-            for (int c = 0; c < k; ++c)
-            {
-                if (frozen[c]) continue;
-                rr[c] = h.rr[c];
-                // the status word is set only with a residual to speak of; it is looked at first
-                if (h.status[c] == 2 || !std::isfinite(rr[c]))
-                {
-                    set_error("spmv_cg_multi: column %d: the residual is not finite at or before iteration %d (non-finite numbers in b, x0 or the matrix, or overflow)", c, j);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
-                if (h.status[c] != 0)
-                {
-                    set_error("spmv_cg_multi: column %d: p.Ap <= 0 (or r.M^-1 r <= 0) at or before iteration %d: the matrix is not positive definite", c, j);
-                    rc = SPMV_ERR_INVALID;
-                    break;
-                }
-                if (rr[c] <= limit[c])
-                {
-                    frozen[c]    = 1;
-                    iters[c]     = j;
-                    rel_resid[c] = sqrt(rr[c] / h.bb[c]);
-                    changed      = true;
-                    --live;
-                }
-            }
-            if (rc != SPMV_OK) break;
-            if (changed && live > 0 && (rc = freeze()) != SPMV_OK) break;
-        }
-        if (rc == SPMV_OK && hipGetLastError() != hipSuccess) rc = SPMV_ERR_HIP;
+        bool changed = false;
         for (int c = 0; c < k; ++c)
-            if (!frozen[c])
+        {
+            if (frozen[c]) continue;
+            rr[c] = h.rr[c];
+            // the status word is set only with a residual to speak of; it is looked at first
+            if (h.status[c] == 2 || !std::isfinite(rr[c]))
             {
+                set_error("spmv_cg_multi: column %d: the residual is not finite at or before iteration %d (non-finite numbers in b, x0 or the matrix, or overflow)", c, j);
+                rc = SPMV_ERR_INVALID;
+                break;
+            }
+            if (h.status[c] != 0)
+            {
+                set_error("spmv_cg_multi: column %d: p.Ap <= 0 (or r.M^-1 r <= 0) at or before iteration %d: the matrix is not positive definite", c, j);
+                rc = SPMV_ERR_INVALID;
+                break;
+            }
+            if (rr[c] <= limit[c])
+            {
+                frozen[c]    = 1;
                 iters[c]     = j;
                 rel_resid[c] = sqrt(rr[c] / h.bb[c]);
+                changed      = true;
+                --live;
             }
-    } while (0);
+        }
+        if (rc != SPMV_OK) break;
+        if (changed && live > 0 && (rc = freeze()) != SPMV_OK) break;
+    }
+    if (rc == SPMV_OK) rc = hip_step(hipGetLastError(), who, "a launch of the iteration");
+    for (int c = 0; c < k; ++c)
+        if (!frozen[c])
+        {
+            iters[c]     = j;
+            rel_resid[c] = sqrt(rr[c] / h.bb[c]);
+        }
 #undef SPMV_CGM_LAUNCH
 #undef SPMV_CGM_LAUNCH_PRE
-    (void)hipStreamSynchronize(st);
-    release();
-    return rc;
+    return rc;  // (the workspace waits for the stream and frees)
 }
 }  // namespace spmv
