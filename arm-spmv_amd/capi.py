@@ -18,7 +18,7 @@ LIB_PATH = Path(os.environ.get("SPMV_HIP_SO") or _PKG / "lib" / "libspmv_hip.so"
 
 FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA = 0, 1, 2, 3, 4
 CSR_AUTO, CSR_VECTOR, CSR_LDSWIN, CSR_SCALAR, CSR_PANEL, CSR_TWOPHASE, CSR_SEGSCAN, CSR_SPLIT, CSR_ELL = 0, 1, 2, 3, 4, 5, 6, 7, 8
-PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0 = 0, 1, 2, 3
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0, PRECOND_CHEBYSHEV = 0, 1, 2, 3, 4
 FLAG_DPP_REDUCE, FLAG_XCD_REMAP = 1, 2
 
 _i32p = C.POINTER(C.c_int32)
@@ -112,6 +112,12 @@ SIGNATURES = {
     "spmv_ilu0_solve": (C.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_ilu0_factors": (C.c_int, [_vp, _vp, _f64p]),
     "spmv_ilu0_order": (C.c_int, [_vp, _vp, _i32p]),
+    "spmv_chebyshev_coefficients": (C.c_int, [C.c_int32, C.c_double, C.c_double, _f64p, _f64p, _f64p]),
+    "spmv_lanczos": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_uint64, _f64p, _f64p, _f64p, _f64p, _i32p]),
+    "spmv_chebyshev_setup": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_double]),
+    "spmv_chebyshev_info": (C.c_int, [_vp, _i32p, _i32p, _f64p, _f64p]),
+    "spmv_chebyshev_solve": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_chebyshev": (C.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_coo_to_csr": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_coo_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_csr_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -191,6 +197,14 @@ def plan_check(plan: bytes) -> tuple[int, int, int]:
     f, k, n = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     _check(load().spmv_plan_check(plan, len(plan), C.byref(f), C.byref(k), C.byref(n)))
     return f.value, k.value, n.value
+
+
+def chebyshev_coefficients(degree: int, lmin: float, lmax: float) -> tuple[float, np.ndarray, np.ndarray]:
+    """(c0, c1[degree], c2[degree]) of the Chebyshev polynomial on [lmin, lmax] as the engine computes them on the host
+    (spmv_chebyshev_coefficients); needs no device"""
+    c0, c1, c2 = C.c_double(0.0), np.zeros(max(int(degree), 1)), np.zeros(max(int(degree), 1))
+    _check(load().spmv_chebyshev_coefficients(degree, lmin, lmax, C.byref(c0), c1.ctypes.data_as(_f64p), c2.ctypes.data_as(_f64p)))
+    return c0.value, c1[:degree], c2[:degree]
 
 
 def partition_rows(nrow: int, nparts: int, part: int) -> tuple[int, int]:
@@ -464,11 +478,43 @@ class Context:
         _check(self._lib.spmv_ilu0_order(self.h, A.h, out.ctypes.data_as(_i32p)))
         return out
 
+    def lanczos(self, A: "Matrix", steps: int, scaled: bool = False, seed: int = 1):
+        """`steps` (1 .. 64) Lanczos steps without reorthogonalisation on a symmetric handle (scaled: on diag(sqrt s) A diag(sqrt s),
+        s_i = 1 / a_ii of a CSR handle) from gen_vector(seed) normalised, synchronous.  Returns (ritz_min, ritz_max, alpha, beta,
+        steps_done): the extreme eigenvalues of the tridiagonal matrix and its coefficients alpha_j, beta_{j+1}, j < steps_done
+        (fewer than `steps` where an invariant subspace ended the run)"""
+        lo, hi, done = C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+        alpha, beta = np.zeros(max(int(steps), 1)), np.zeros(max(int(steps), 1))
+        _check(self._lib.spmv_lanczos(self.h, A.h, 1 if scaled else 0, steps, seed, C.byref(lo), C.byref(hi), alpha.ctypes.data_as(_f64p),
+                                      beta.ctypes.data_as(_f64p), C.byref(done)))
+        return lo.value, hi.value, alpha[: done.value], beta[: done.value], done.value
+
+    def chebyshev_setup(self, A: "Matrix", degree: int = 4, scaled: bool = True, lmin: float = 0.0, lmax: float = 0.0) -> None:
+        """the Chebyshev polynomial preconditioner of degree `degree` (products per application) on [lmin, lmax] for diag(s) A, s_i =
+        1 / a_ii where scaled (a CSR handle), synchronous; replaces earlier state.  lmax = 0: the row bound of a CSR handle (and 1.05
+        times Lanczos' largest Ritz value where A.set_param("cheby_lanczos_steps", m > 0)); lmin = 0: lmax / "cheby_ratio" (30)"""
+        _check(self._lib.spmv_chebyshev_setup(self.h, A.h, degree, 1 if scaled else 0, lmin, lmax))
+
+    def chebyshev_info(self, A: "Matrix") -> tuple[int, bool, float, float]:
+        """(degree, scaled, lmin, lmax) of the handle's Chebyshev state; degree 0: not set up"""
+        d, s, lo, hi = C.c_int32(0), C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
+        _check(self._lib.spmv_chebyshev_info(A.h, C.byref(d), C.byref(s), C.byref(lo), C.byref(hi)))
+        return d.value, bool(s.value), lo.value, hi.value
+
+    def chebyshev_solve(self, A: "Matrix", r: "Vector", z: "Vector") -> None:
+        """z = M^-1 r with the handle's Chebyshev polynomial (chebyshev_setup first), asynchronous; r and z must not overlap"""
+        _check(self._lib.spmv_chebyshev_solve(self.h, A.h, r.h, z.h))
+
+    def chebyshev(self, A: "Matrix", b: "Vector", x: "Vector") -> None:
+        """one smoothing step x += M^-1 (b - A x) with the handle's Chebyshev polynomial (chebyshev_setup first), asynchronous"""
+        _check(self._lib.spmv_chebyshev(self.h, A.h, b.h, x.h))
+
     def cg(self, A: "Matrix", b: "Vector", x: "Vector", max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
            jacobi: bool = False, symgs: bool = False, precond: int | None = None):
         """conjugate gradients on the device from the x passed in (jacobi: diagonal preconditioner, symgs: one symmetric
         Gauss-Seidel sweep per iteration; CSR handles); returns (iterations, ||r|| / ||b||).  precond, if given, is passed as it
-        is (PRECOND_*; PRECOND_ILU0: the ILU(0) factors of a CSR handle, set up on first use)"""
+        is (PRECOND_*; PRECOND_ILU0: the ILU(0) factors of a CSR handle, set up on first use; PRECOND_CHEBYSHEV: the handle's Chebyshev
+        polynomial, set up on first use with the defaults unless chebyshev_setup was called)"""
         it, res = C.c_int32(0), C.c_double(0.0)
         pc = precond if precond is not None else (PRECOND_SYMGS if symgs else (PRECOND_JACOBI if jacobi else PRECOND_NONE))
         _check(self._lib.spmv_cg(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, pc, C.byref(it), C.byref(res)))

@@ -104,6 +104,7 @@ void mat_free(spmv_mat* m)
     csr_layouts_free(m, kCsrAllLayouts);
     symgs_free(m);
     ilu0_free(m);
+    cheby_free(m);
     if (m->rowgrouped) mat_free(m->rowgrouped);
     coo_free_bins(m);
     delete m;
@@ -814,6 +815,8 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
         SPMV_REQUIRE(value == 0 || value == 1, "ilu0_order: 0 (row order) or 1 (multicolour), got %lld", (long long)value);
         m->ilu_order = (int32_t)value;
     }
+    else if (int crc = SPMV_OK; cheby_set_param(m, name, value, &crc))  // "cheby_degree", "cheby_ratio", "cheby_lanczos_steps": at the next set-up
+        return crc;
     else if (!strcmp(name, "twophase_panel_cols"))  // takes effect at the next spmv_mat_set_kernel(TWOPHASE)
         m->tp_pcols_req = (int32_t)value;
     else if (!strcmp(name, "twophase_placement_budget_mb"))
@@ -908,6 +911,7 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         SPMV_REQUIRE(ilu0_info(m, name, value) == SPMV_OK, "unknown parameter '%s'", name);
         return SPMV_OK;
     }
+    if (cheby_get_param(m, name, value)) return SPMV_OK;  // "cheby_ready", "cheby_degree", "cheby_bytes", "cheby_launches", ...
     if (transpose_get_param(m, name, value)) return SPMV_OK;  // "transpose_ready", "transpose_bytes", "transpose_kernel", ...
     if (!strcmp(name, "panel_keep_csr"))
         *value = (m->b && m->v) || m->nnz == 0 ? 1 : 0;
@@ -1295,10 +1299,10 @@ int spmv_apply_dot(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec
 
 // The five solves.  Every check is made before the device is touched, so that they hold (and are tested) on a machine without one;
 // the checks they share and what each solver's refusals depend on (solver_rules) are solver_host.hpp's.
-static const solver_rules kCgRules       = {"spmv_cg", "the matrix", true, nullptr, nullptr, solver_rules::jacobi_arrays_unsupported};
-static const solver_rules kCgMultiRules  = {"spmv_cg_multi", "the matrix", false, "k columns", "k columns", solver_rules::jacobi_arrays_elsewhere};
-static const solver_rules kBicgstabRules = {"spmv_bicgstab", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid};
-static const solver_rules kGmresRules    = {"spmv_gmres", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid};
+static const solver_rules kCgRules       = {"spmv_cg", "the matrix", true, nullptr, nullptr, solver_rules::jacobi_arrays_unsupported, nullptr};
+static const solver_rules kCgMultiRules  = {"spmv_cg_multi", "the matrix", false, "k columns", "k columns", solver_rules::jacobi_arrays_elsewhere, "k columns"};
+static const solver_rules kBicgstabRules = {"spmv_bicgstab", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr};
+static const solver_rules kGmresRules    = {"spmv_gmres", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr};
 
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
             int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
@@ -1449,6 +1453,67 @@ int spmv_ilu0_order(spmv_ctx* ctx, const spmv_mat* A, int32_t* order_host)
     SPMV_TRY(use_device(ctx));
     SPMV_TRY(ilu0_setup(const_cast<spmv_mat*>(A)));
     return ilu0_sequence(A, order_host);
+}
+
+// The Chebyshev polynomial preconditioner and the Lanczos spectrum estimate (chebyshev.hip).  Every check is made before the device is
+// touched and reads the leading fields of the handle alone, so that they hold (and are tested) on a machine without one.
+int spmv_chebyshev_coefficients(int32_t degree, double lmin, double lmax, double* c0, double* c1, double* c2)
+{
+    return cheby_coefficients(degree, lmin, lmax, c0, c1, c2);
+}
+
+int spmv_lanczos(spmv_ctx* ctx, const spmv_mat* A, int32_t scaled, int32_t steps, uint64_t seed, double* ritz_min, double* ritz_max,
+                 double* alpha, double* beta, int32_t* steps_done)
+{
+    SPMV_REQUIRE(ctx && A && ritz_min && ritz_max && steps_done, "spmv_lanczos: null argument");
+    SPMV_REQUIRE(steps >= 1 && steps <= 64, "spmv_lanczos: steps=%d, must be 1 .. 64", steps);
+    SPMV_REQUIRE(A->nrow == A->ncol && A->row_begin == 0, "spmv_lanczos: needs the whole square matrix (%d x %d, first row %lld)", A->nrow, A->ncol,
+                 (long long)A->row_begin);
+    if (scaled) SPMV_TRY(cheby_check_scaled(A, "spmv_lanczos"));
+    *ritz_min = *ritz_max = 0.0;
+    *steps_done           = 0;
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return cheby_lanczos(ctx, A, scaled, steps, seed, ritz_min, ritz_max, alpha, beta, steps_done);
+}
+
+int spmv_chebyshev_setup(spmv_ctx* ctx, spmv_mat* A, int32_t degree, int32_t scaled, double lmin, double lmax)
+{
+    SPMV_REQUIRE(ctx && A, "spmv_chebyshev_setup: null argument");
+    SPMV_TRY(cheby_check_setup(A, degree, scaled, lmin, lmax, "spmv_chebyshev_setup"));
+    SPMV_REQUIRE(A->ctx == ctx, "spmv_chebyshev_setup: the matrix belongs to another context");
+    SPMV_TRY(use_device(ctx));
+    return cheby_setup(ctx, A, degree, scaled, lmin, lmax);
+}
+
+int spmv_chebyshev_info(const spmv_mat* A, int32_t* degree, int32_t* scaled, double* lmin, double* lmax)
+{
+    SPMV_REQUIRE(A && degree && scaled && lmin && lmax, "spmv_chebyshev_info: null argument");
+    return cheby_info(A, degree, scaled, lmin, lmax);
+}
+
+int spmv_chebyshev_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z)
+{
+    SPMV_REQUIRE(ctx && A && r && z, "spmv_chebyshev_solve: null argument");
+    SPMV_TRY(cheby_check_handle(A, "spmv_chebyshev_solve"));
+    SPMV_REQUIRE(r->n == A->nrow && z->n == A->nrow, "spmv_chebyshev_solve: r has %lld and z %lld entries, the matrix %d rows", (long long)r->n,
+                 (long long)z->n, A->nrow);
+    SPMV_REQUIRE(vectors_disjoint(r, z), "spmv_chebyshev_solve: r and z must not overlap");
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return cheby_apply(ctx, A, r->d, z->d);
+}
+
+int spmv_chebyshev(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x)
+{
+    SPMV_REQUIRE(ctx && A && b && x, "spmv_chebyshev: null argument");
+    SPMV_TRY(cheby_check_handle(A, "spmv_chebyshev"));
+    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "spmv_chebyshev: b has %lld and x %lld entries, the matrix %d rows", (long long)b->n,
+                 (long long)x->n, A->nrow);
+    SPMV_REQUIRE(vectors_disjoint(b, x), "spmv_chebyshev: b and x must not overlap");
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return cheby_smooth(ctx, A, b->d, x->d);
 }
 
 // ---- conversions ------------------------------------------------------------------------------------------

@@ -142,6 +142,7 @@ namespace spmv
 {
 struct symgs_plan;
 struct ilu0_plan;
+struct cheby_state;
 struct transpose_state;
 // ---- plans (plan.hip): the decisions a handle's set-up made - by model or by timing - as plain data ------------------------------
 // One node per handle, children by index (the row-grouped copy of a COO / CSC / ELL handle or the short-row copy of a split,
@@ -362,6 +363,13 @@ struct spmv_mat
     // built by spmv_mat_transpose_setup, no part of the forward state (kernel, copies, device_bytes, plan)
     struct spmv::transpose_state* tr            = nullptr;
     int32_t                       tr_kernel_req = SPMV_CSR_AUTO;  // "transpose_kernel": handed to spmv_mat_set_kernel on the companion
+
+    // the Chebyshev polynomial preconditioner (chebyshev.hip): degree, bounds, coefficient table, 1 / a_ii and three work vectors; built
+    // by spmv_chebyshev_setup (or by the first solve with SPMV_PRECOND_CHEBYSHEV), no part of the forward state, of plans or of trials
+    struct spmv::cheby_state* cheby = nullptr;
+    int32_t                   cheby_degree        = 4;   // "cheby_degree": what a solver's own set-up takes
+    int32_t                   cheby_ratio         = 30;  // "cheby_ratio": lmin = lmax / ratio where lmin is estimated
+    int32_t                   cheby_lanczos_steps = 0;   // "cheby_lanczos_steps": > 0: 1.05 ritz_max of that many steps competes with the row bound
 };
 
 namespace spmv
@@ -458,7 +466,7 @@ bool adds_into_y_with_atomics(const spmv_mat* A);       // global_atomic_add_f64
 // The five solves' drivers.  Each is entered from its ABI entry (abi.hip) behind the argument checks and use_device, zeroes its
 // outputs, returns at an empty system, and shares its host side - the workspace that owns its device memory, the preconditioner's
 // set-up and application, the looks at its scalars - with the others through solver_host.hpp.
-// solver.hip: conjugate gradients for a symmetric positive definite A (precond: NONE, JACOBI, SYMGS, ILU0)
+// solver.hip: conjugate gradients for a symmetric positive definite A (precond: NONE, JACOBI, SYMGS, ILU0, CHEBYSHEV)
 int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
              int precond, int* iters, double* rel_resid);
 int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t n, double* device_out);
@@ -468,11 +476,11 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
 // solver_cgls.hip: CGLS for min ||b - A x||^2 + damp^2 ||x||^2 over the forward and the transposed product of any handle
 int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                double damp, int* iters, double* rel_normal_resid, double* rel_resid);
-// solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle (precond: NONE, JACOBI, ILU0)
+// solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle (precond: NONE, JACOBI, ILU0, CHEBYSHEV)
 int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                    int precond, int* iters, double* rel_resid);
 // solver_gmres.hip: right-preconditioned restarted GMRES(restart) for square A over one forward product of any handle per iteration
-// (restart: 1 .. 64; precond: NONE, JACOBI, ILU0)
+// (restart: 1 .. 64; precond: NONE, JACOBI, ILU0, CHEBYSHEV)
 int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int restart, int max_iter, double rel_tol, int check_every,
                 int precond, int* iters, double* rel_resid);
 // kernels_ell.hip (what a product launches: ell_settings.hpp)
@@ -539,6 +547,20 @@ int  ilu0_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z);  
 int  ilu0_factor_values(const spmv_mat* m, double* out);      // aligned to the handle's own entries, to the host
 int  ilu0_sequence(const spmv_mat* m, int32_t* out);
 int  ilu0_info(const spmv_mat* m, const char* what, int64_t* value);
+// chebyshev.hip: the Chebyshev polynomial preconditioner z = p_d(diag(s) A) diag(s) r (SPMV_PRECOND_CHEBYSHEV), and the Lanczos estimate
+int  cheby_coefficients(int degree, double lmin, double lmax, double* c0, double* c1, double* c2);  // host only; c1, c2: degree entries
+int  cheby_check_handle(const spmv_mat* m, const char* who);  // on the host: INVALID (not square, a shard that starts behind row 0)
+int  cheby_check_scaled(const spmv_mat* m, const char* who);  // on the host: INVALID (the Jacobi scaling: not CSR, arrays released)
+int  cheby_check_setup(const spmv_mat* m, int degree, int scaled, double lmin, double lmax, const char* who);  // on the host
+int  cheby_setup(spmv_ctx* ctx, spmv_mat* m, int degree, int scaled, double lmin, double lmax);  // synchronous; replaces earlier state
+void cheby_free(spmv_mat* m);
+int  cheby_info(const spmv_mat* m, int32_t* degree, int32_t* scaled, double* lmin, double* lmax);
+int  cheby_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z);   // z = M^-1 r, asynchronous; r and z must not overlap
+int  cheby_smooth(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x);  // x += M^-1 (b - A x), asynchronous
+int  cheby_lanczos(spmv_ctx* ctx, const spmv_mat* A, int scaled, int steps, uint64_t seed, double* ritz_min, double* ritz_max, double* alpha,
+                   double* beta, int32_t* steps_done);  // synchronous; alpha, beta: host arrays of `steps` entries or null
+bool cheby_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "cheby_*"; false: not one of them
+bool cheby_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "cheby_*"; false: not one of them
 // convert_sort.hip
 int sort_ids_by_key(spmv_ctx* ctx, const int32_t* keys, int64_t n, int bits, int32_t* out_ids);
 int coo_place_by_stable_sort(spmv_ctx* ctx, int64_t nnz, int32_t nrow, const int32_t* row, const int32_t* col, const double* val,

@@ -356,9 +356,10 @@ int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int m
     hipStream_t st = ctx->stream;
     // z = M^-1 r is a vector of its own where an application stands between the product and the updates: one symmetric Gauss-Seidel
     // sweep from z = 0 per iteration (symgs.hip), or z = U^-1 L^-1 r with the ILU(0) factors (ilu0.hip: L U = L D L^T for a
-    // symmetric A).  Two launches per iteration (cg_fused_kernel) unless there is one, or SPMV_CG_THREE_LAUNCHES=1 asks for the
-    // textbook arrangement (A/B; read once per solve).
-    const bool  given   = precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0, jacobi = precond == SPMV_PRECOND_JACOBI;
+    // symmetric A), or the Chebyshev polynomial z = p_d(diag(s) A) diag(s) r of the handle (chebyshev.hip).  Two launches per
+    // iteration (cg_fused_kernel) unless there is one, or SPMV_CG_THREE_LAUNCHES=1 asks for the textbook arrangement (A/B; read
+    // once per solve).
+    const bool  given   = precond == SPMV_PRECOND_SYMGS || applied_by_launches(precond), jacobi = precond == SPMV_PRECOND_JACOBI;
     const char* e_three = getenv("SPMV_CG_THREE_LAUNCHES");
     const bool  fused   = !given && !(e_three && e_three[0] == '1');
     // the pieces a run does not need stay null, which is how the kernels and the launches below tell the arrangements apart

@@ -335,7 +335,7 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
     *rel_resid            = 0.0;
     if (n == 0) return SPMV_OK;
     hipStream_t st  = ctx->stream;
-    const bool  pre = precond == SPMV_PRECOND_JACOBI, ilu = precond == SPMV_PRECOND_ILU0;
+    const bool  pre = precond == SPMV_PRECOND_JACOBI, ilu = applied_by_launches(precond);  // ilu: ILU(0) or the Chebyshev polynomial
     // r, rhat, p, v, s, t (Jacobi: dinv, phat, shat; ILU(0): phat, shat) and the partial sums of two quantities
     double *r, *rhat, *p, *v, *sv, *t, *dinv = nullptr, *phat = nullptr, *shat = nullptr, *part;
     BicgScalars*   s = nullptr;

@@ -438,7 +438,7 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
     if (n == 0) return SPMV_OK;
     const int   m  = restart;
     hipStream_t st = ctx->stream;
-    const bool  pre = precond == SPMV_PRECOND_JACOBI, ilu = precond == SPMV_PRECOND_ILU0;
+    const bool  pre = precond == SPMV_PRECOND_JACOBI, ilu = applied_by_launches(precond);  // ilu: ILU(0) or the Chebyshev polynomial
     // the basis (m + 1 vectors, a padded vector apart), w, z (Jacobi, ILU(0)), dinv (Jacobi) and the partial sums of m + 2 quantities
     const size_t   sn = SolveWorkspace::padded((size_t)n);
     double *       V, *w, *z = nullptr, *dinv = nullptr, *part;

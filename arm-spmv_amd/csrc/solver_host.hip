@@ -1,5 +1,5 @@
 // solver_host.hip — the host side that the five solves share (solver_host.hpp): argument checks, the workspace, the preconditioner's
-// set-up and application.  One kernel: the inverse diagonal of a CSR handle, for Jacobi.
+// set-up and application.  One kernel: the inverse diagonal of a CSR handle, for Jacobi and for Chebyshev's scaling.
 #include "solver_host.hpp"
 
 namespace spmv
@@ -26,8 +26,10 @@ __global__ __launch_bounds__(kBlock) void csr_inv_diag_kernel(int nrow, int64_t 
     dinv[i] = 1.0 / d;
 }
 
+}  // namespace
+
 // dinv[i] = 1 / a_ii; the flag is the first word of the context's scratch
-int jacobi_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, const char* who)
+int jacobi_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, const char* who, const char* what)
 {
     SPMV_TRY(ensure_scratch(ctx, 64));
     int* flag   = (int*)ctx->scratch;
@@ -38,10 +40,9 @@ int jacobi_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, cons
     SPMV_HIP(hipGetLastError());
     if (hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess || h_flag != 0)
-        SPMV_FAIL(SPMV_ERR_INVALID, "%s: the matrix has a zero or missing diagonal entry (Jacobi preconditioner)", who);
+        SPMV_FAIL(SPMV_ERR_INVALID, "%s: the matrix has a zero or missing diagonal entry (%s)", who, what);
     return SPMV_OK;
 }
-}  // namespace
 
 // ---- argument checks -----------------------------------------------------------------------------------------------------------
 bool vectors_disjoint(const spmv_vec* b, const spmv_vec* x)
@@ -57,7 +58,8 @@ int check_limits(const char* who, int max_iter, double rel_tol)
 
 int check_known_preconditioner(const char* who, int precond)
 {
-    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0,
+    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0 ||
+                     precond == SPMV_PRECOND_CHEBYSHEV,
                  "%s: unknown preconditioner %d", who, precond);
     return SPMV_OK;
 }
@@ -85,6 +87,11 @@ int check_preconditioner(const solver_rules& S, const spmv_mat* A, int precond)
     {
         if (S.ilu0_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the ILU(0) preconditioner is not built for %s", S.who, S.ilu0_not_built_for);
         return ilu0_check_handle(A, S.who);
+    }
+    if (precond == SPMV_PRECOND_CHEBYSHEV)
+    {
+        if (S.cheby_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the Chebyshev preconditioner is not built for %s", S.who, S.cheby_not_built_for);
+        return cheby_check_handle(A, S.who);  // (whether the handle is set up, and what its own set-up needs, is looked at on the device's side)
     }
     if (precond != SPMV_PRECOND_JACOBI) return SPMV_OK;
     // Jacobi reads the diagonal from the handle's own CSR arrays (the plain solve needs the product alone and takes a handle that
@@ -159,12 +166,19 @@ int setup_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, double* 
         case SPMV_PRECOND_JACOBI: return jacobi_inverse_diagonal(ctx, A, dinv, who);
         case SPMV_PRECOND_SYMGS: return symgs_setup(const_cast<spmv_mat*>(A));
         case SPMV_PRECOND_ILU0: return ilu0_setup(const_cast<spmv_mat*>(A));
+        case SPMV_PRECOND_CHEBYSHEV:  // a handle that was set up explicitly is used as it stands
+            return A->cheby ? SPMV_OK : cheby_setup(ctx, const_cast<spmv_mat*>(A), A->cheby_degree, /*scaled=*/1, 0.0, 0.0);
         default: return SPMV_OK;
     }
 }
 
 int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const double* r, double* z)
 {
-    return precond == SPMV_PRECOND_ILU0 ? ilu0_apply(ctx, A, r, z) : symgs_sweep(ctx, A, r, z, true);
+    switch (precond)
+    {
+        case SPMV_PRECOND_ILU0: return ilu0_apply(ctx, A, r, z);
+        case SPMV_PRECOND_CHEBYSHEV: return cheby_apply(ctx, A, r, z);
+        default: return symgs_sweep(ctx, A, r, z, true);
+    }
 }
 }  // namespace spmv

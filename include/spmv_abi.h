@@ -343,6 +343,8 @@ int spmv_mat_set_flags(spmv_mat* m, uint32_t flags);
  *                    many runs, each ending in an atomic on y: results differ from the scan in place by rounding only.
  *   "symgs_order"    sweep order of spmv_symgs / SPMV_PRECOND_SYMGS: 1 multicolour (default), 0 the matrix's own row order
  *   "ilu0_order"     sweep order of the ILU(0) factorisation (spmv_ilu0_setup / SPMV_PRECOND_ILU0), with the same meaning and default
+ *   "cheby_degree"   degree a solver's own set-up of SPMV_PRECOND_CHEBYSHEV takes (1 .. 64, default 4); "cheby_ratio": lmax / lmin where
+ *                    lmin is estimated (2 .. 10^6, default 30); "cheby_lanczos_steps": 0 (default) .. 64, see spmv_chebyshev_setup
  *   "panel_two_per_cu"   0 = never two workgroups per CU (default 1: two when their accumulators fit the LDS twice) */
 int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
 /* What is in effect: "panel_rows", "panel_width", "panel_sort", "panel_groups", "panel_layout", "panel_unroll",
@@ -361,7 +363,7 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
  * handle were found to be diagonals and conforming rows read no column index), "symgs_order", "symgs_colours",
  * "symgs_levels_forward", "symgs_levels_backward", "symgs_launches", "symgs_bytes", "symgs_fused" (1: the colouring is proper and
  * the sweep takes one launch per colour), "ilu0_order", "ilu0_ready", "ilu0_colours", "ilu0_levels_forward", "ilu0_levels_backward",
- * "ilu0_launches" (per application), "ilu0_bytes". */
+ * "ilu0_launches" (per application), "ilu0_bytes", and the "cheby_*" names listed at spmv_chebyshev_setup. */
 int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value);
 /* ---- plans: a handle's set-up decisions as plain data (plan.hip) ------------------------------------------------------------
  * AUTO is a measurement (spmv_mat_set_kernel above): which kernel a handle runs, in which layout, with which chunk size,
@@ -496,8 +498,13 @@ enum spmv_precond
     SPMV_PRECOND_JACOBI = 1, /* z = D^-1 r, D = diag(A) read from a CSR handle (zero diagonal: SPMV_ERR_INVALID) */
     SPMV_PRECOND_SYMGS  = 2, /* z = one symmetric Gauss-Seidel sweep on A z = r from z = 0 (spmv_symgs below; the handle is
                                 set up on first use although it is passed as const) */
-    SPMV_PRECOND_ILU0   = 3  /* z = U^-1 L^-1 r with the ILU(0) factors of a CSR handle (spmv_ilu0_setup below; set up on first use
+    SPMV_PRECOND_ILU0   = 3, /* z = U^-1 L^-1 r with the ILU(0) factors of a CSR handle (spmv_ilu0_setup below; set up on first use
                                 in the same way).  spmv_cg, spmv_bicgstab and spmv_gmres; spmv_cg_multi: SPMV_ERR_UNSUPPORTED */
+    SPMV_PRECOND_CHEBYSHEV = 4 /* z = p_d(diag(s) A) diag(s) r, a fixed Chebyshev polynomial applied through the handle's own forward
+                                product (spmv_chebyshev_setup below).  A handle that was set up is used as it stands, any format; one
+                                that was not is set up on first use with degree "cheby_degree" (4), Jacobi scaling and estimated
+                                bounds, which needs a CSR handle with its arrays.  spmv_cg, spmv_bicgstab and spmv_gmres, with the
+                                work vectors and arrangement of SPMV_PRECOND_ILU0; spmv_cg_multi: SPMV_ERR_UNSUPPORTED */
 };
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter,
             double rel_tol, int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
@@ -677,6 +684,58 @@ int spmv_ilu0_setup(spmv_ctx* ctx, spmv_mat* A);
 int spmv_ilu0_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z);
 int spmv_ilu0_factors(spmv_ctx* ctx, const spmv_mat* A, double* values_host /* nnz entries */);
 int spmv_ilu0_order(spmv_ctx* ctx, const spmv_mat* A, int32_t* order_host /* nrow entries */);
+
+/* The Chebyshev polynomial preconditioner / smoother, and the Lanczos estimate of a symmetric handle's extreme eigenvalues
+ * (chebyshev.hip).  A: a handle of any format that holds the whole square matrix (a shard that starts behind row 0:
+ * SPMV_ERR_INVALID).
+ *
+ *   Definition.  degree d in 1 .. 64 (the products per application); s_i = 1 / a_ii where `scaled` (the diagonal as
+ *   SPMV_PRECOND_JACOBI reads it from a CSR handle that still has its arrays, duplicates summed; a zero or missing entry:
+ *   SPMV_ERR_INVALID), s_i = 1 otherwise; B = diag(s) A; 0 < lmin < lmax.  On the host, in double, every line one rounded operation:
+ *       theta = (lmax + lmin) / 2;  delta = (lmax - lmin) / 2;  sigma = theta / delta;  rho_0 = 1 / sigma;  c0 = 1 / theta
+ *       for k = 1..d:  rho_k = 1 / (2 sigma - rho_{k-1});  c1_k = rho_k rho_{k-1};  c2_k = 2 rho_k / delta
+ *   (spmv_chebyshev_coefficients returns this table; it touches no device).  The application z = M^-1 r leaves r as it is:
+ *       d = c0 (s .* r);  z = d;  t = r;      for k = 1..d:  w = A d;  t = t - w;  d = c1_k d + c2_k (s .* t);  z = z + d
+ *   that is z = p_d(B) diag(s) r; the start and the d terms are d + 1 corrections of the Chebyshev iteration, so p_d has degree d
+ *   and 1 - lambda p_d(lambda) = T_{d+1}((theta - lambda) / delta) / T_{d+1}(sigma): one application contracts the error of a
+ *   symmetric system by at most 1 / T_{d+1}(sigma) where the bounds hold.  M^-1 is symmetric
+ *   positive definite whenever A is and lmax is at or above B's largest eigenvalue: a legitimate preconditioner of spmv_cg.  An lmax
+ *   that is too small shows as r.M^-1 r <= 0, which spmv_cg reports.  2 d + 1 launches per application ("cheby_launches"): one
+ *   start, and per term the handle's forward product and ONE pass over the vectors; no dot product, no look by the host.
+ *
+ *   spmv_chebyshev_setup (synchronous; replaces earlier state).  lmax = 0: estimated.  A CSR handle that still has its arrays takes
+ *   the row bound max_i |s_i| sum_j |a_ij| over every stored entry - the infinity norm of B, a RIGOROUS upper bound of every
+ *   |lambda|.  Where spmv_mat_set_param "cheby_lanczos_steps" is above 0 (default 0) it also takes 1.05 times the largest Ritz value
+ *   of that many steps of spmv_lanczos (seed 1) and keeps the smaller of the two, or the Lanczos value alone on a handle without CSR
+ *   arrays.  A Ritz value is a LOWER estimate of the largest eigenvalue; the factor 1.05 (what Ifpack2 and hypre put on their
+ *   power-method estimates) usually covers the difference and guarantees nothing.  Neither source: SPMV_ERR_UNSUPPORTED.
+ *   lmin = 0: lmax / "cheby_ratio" (default 30, the smoother default of the same libraries; 2 .. 10^6).  SPMV_ERR_INVALID: a
+ *   negative or non-finite bound, lmin >= lmax, degree outside 1 .. 64, a matrix that is not square or a shard that starts behind
+ *   row 0, `scaled` on a handle that is not CSR with its arrays.  Explicit bounds with scaled = 0: any format.  nrow = 0: SPMV_OK.
+ *   spmv_chebyshev_info: what the state holds; not set up: degree 0.
+ *
+ *   spmv_chebyshev_solve: z = M^-1 r, asynchronous; r and z must not overlap; the handle must be set up.
+ *   spmv_chebyshev: x += M^-1 (b - A x), one smoothing step (one product more), asynchronous; b and x must not overlap.
+ *
+ *   spmv_lanczos (synchronous): `steps` (1 .. 64) steps of the Lanczos recurrence without reorthogonalisation on
+ *   C = diag(sqrt s) A diag(sqrt s), which has B's spectrum (scaled: every a_ii > 0, else SPMV_ERR_INVALID; unscaled: A itself),
+ *   from v_0 = spmv_gen_vec_uniform(seed) normalised.  One product and two launches per step, every sum deterministic, alpha and
+ *   beta on the device until the end.  beta_{j+1} at or below 2^-44 max(|alpha|, beta) seen so far is an invariant subspace and
+ *   ends the run quietly (steps_done < steps).  Returns the smallest and the largest eigenvalue of the steps_done x steps_done
+ *   tridiagonal matrix (bisection on the Sturm count, to 2 ulp of the largest |value|) and, where asked for, alpha_j and
+ *   beta_{j+1}, j = 0 .. steps_done - 1.  A is meant to be symmetric; nothing checks it.
+ *
+ *   The state lives in the handle (spmv_mat_get_param "cheby_ready", "cheby_degree", "cheby_bytes", "cheby_launches",
+ *   "cheby_lanczos_steps", "cheby_ratio", "cheby_lmax_source": 0 the caller's, 1 the row bound, 2 Lanczos): degree, bounds, the
+ *   table, s where scaled and three work vectors; it is counted in device_bytes and freed with the handle, and is no part of the
+ *   forward state, of plans or of trials. */
+int spmv_chebyshev_coefficients(int32_t degree, double lmin, double lmax, double* c0, double* c1 /* degree */, double* c2 /* degree */);
+int spmv_lanczos(spmv_ctx* ctx, const spmv_mat* A, int32_t scaled, int32_t steps, uint64_t seed, double* ritz_min, double* ritz_max,
+                 double* alpha /* steps entries or NULL */, double* beta /* steps entries or NULL */, int32_t* steps_done);
+int spmv_chebyshev_setup(spmv_ctx* ctx, spmv_mat* A, int32_t degree, int32_t scaled, double lmin, double lmax);
+int spmv_chebyshev_info(const spmv_mat* A, int32_t* degree, int32_t* scaled, double* lmin, double* lmax);
+int spmv_chebyshev_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z);
+int spmv_chebyshev(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x);
 
 /* ---- format conversion on the device (src/matrix.cpp:115-154, :450-500) -------------------------- */
 /* Both keep the COO order of the entries inside each row (stable), like the reference's backward
