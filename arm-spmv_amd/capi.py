@@ -18,7 +18,7 @@ LIB_PATH = Path(os.environ.get("SPMV_HIP_SO") or _PKG / "lib" / "libspmv_hip.so"
 
 FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA = 0, 1, 2, 3, 4
 CSR_AUTO, CSR_VECTOR, CSR_LDSWIN, CSR_SCALAR, CSR_PANEL, CSR_TWOPHASE, CSR_SEGSCAN, CSR_SPLIT, CSR_ELL = 0, 1, 2, 3, 4, 5, 6, 7, 8
-PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0, PRECOND_CHEBYSHEV = 0, 1, 2, 3, 4
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0, PRECOND_CHEBYSHEV, PRECOND_AMG = 0, 1, 2, 3, 4, 5
 FLAG_DPP_REDUCE, FLAG_XCD_REMAP = 1, 2
 
 _i32p = C.POINTER(C.c_int32)
@@ -118,6 +118,10 @@ SIGNATURES = {
     "spmv_chebyshev_info": (C.c_int, [_vp, _i32p, _i32p, _f64p, _f64p]),
     "spmv_chebyshev_solve": (C.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_chebyshev": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_amg_setup": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double]),
+    "spmv_amg_info": (C.c_int, [_vp, _i32p, _i64p, _i64p]),
+    "spmv_amg_level": (C.c_int, [_vp, _vp, C.c_int32, _i32p, _i32p, _i32p, _f64p]),
+    "spmv_amg_solve": (C.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_coo_to_csr": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_coo_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_csr_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -509,12 +513,43 @@ class Context:
         """one smoothing step x += M^-1 (b - A x) with the handle's Chebyshev polynomial (chebyshev_setup first), asynchronous"""
         _check(self._lib.spmv_chebyshev(self.h, A.h, b.h, x.h))
 
+    def amg_setup(self, A: "Matrix", max_levels: int = 0, coarse_max: int = 0, smooth_degree: int = 0, strength: float = 0.0,
+                  overcorrection: float = 0.0) -> None:
+        """aggregation AMG on a CSR handle (spmv_amg_setup), synchronous; replaces earlier state and the handle's Chebyshev state (the
+        smoother of level 0).  0 takes the default: 16 levels, a dense coarsest solve from 256 rows down, smoothing degree 2, every
+        stored entry a neighbour, overcorrection 1.5"""
+        _check(self._lib.spmv_amg_setup(self.h, A.h, max_levels, coarse_max, smooth_degree, strength, overcorrection))
+
+    def amg_info(self, A: "Matrix") -> tuple[int, np.ndarray, np.ndarray]:
+        """(levels, rows per level, entries per level) of the handle's hierarchy"""
+        levels, rows, nnz = C.c_int32(0), np.zeros(32, dtype=np.int64), np.zeros(32, dtype=np.int64)
+        _check(self._lib.spmv_amg_info(A.h, C.byref(levels), rows.ctypes.data_as(_i64p), nnz.ctypes.data_as(_i64p)))
+        return levels.value, rows[: levels.value], nnz[: levels.value]
+
+    def amg_level(self, A: "Matrix", level: int):
+        """(agg, row_ptr, col, val) of one level on the host: the aggregate of every row (None on the coarsest level) and the level's
+        operator as CSR"""
+        levels, rows, nnz = self.amg_info(A)
+        if not 0 <= level < levels:
+            raise SpmvError(-1, f"amg_level: level={level}, the hierarchy has {levels}")
+        n, e = int(rows[level]), int(nnz[level])
+        agg = np.zeros(n, dtype=np.int32) if level + 1 < levels else None
+        rp, cc, cv = np.zeros(n + 1, dtype=np.int32), np.zeros(e, dtype=np.int32), np.zeros(e, dtype=np.float64)
+        _check(self._lib.spmv_amg_level(self.h, A.h, level, agg.ctypes.data_as(_i32p) if agg is not None else None, rp.ctypes.data_as(_i32p),
+                                        cc.ctypes.data_as(_i32p), cv.ctypes.data_as(_f64p)))
+        return agg, rp, cc, cv
+
+    def amg_solve(self, A: "Matrix", r: "Vector", z: "Vector") -> None:
+        """z = B r, one V(1,1) cycle of the handle's hierarchy (amg_setup first), asynchronous; r and z must not overlap"""
+        _check(self._lib.spmv_amg_solve(self.h, A.h, r.h, z.h))
+
     def cg(self, A: "Matrix", b: "Vector", x: "Vector", max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
            jacobi: bool = False, symgs: bool = False, precond: int | None = None):
         """conjugate gradients on the device from the x passed in (jacobi: diagonal preconditioner, symgs: one symmetric
         Gauss-Seidel sweep per iteration; CSR handles); returns (iterations, ||r|| / ||b||).  precond, if given, is passed as it
         is (PRECOND_*; PRECOND_ILU0: the ILU(0) factors of a CSR handle, set up on first use; PRECOND_CHEBYSHEV: the handle's Chebyshev
-        polynomial, set up on first use with the defaults unless chebyshev_setup was called)"""
+        polynomial, set up on first use with the defaults unless chebyshev_setup was called; PRECOND_AMG: one cycle of the handle's
+        aggregation AMG hierarchy, likewise unless amg_setup was called)"""
         it, res = C.c_int32(0), C.c_double(0.0)
         pc = precond if precond is not None else (PRECOND_SYMGS if symgs else (PRECOND_JACOBI if jacobi else PRECOND_NONE))
         _check(self._lib.spmv_cg(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, pc, C.byref(it), C.byref(res)))

@@ -105,6 +105,7 @@ void mat_free(spmv_mat* m)
     symgs_free(m);
     ilu0_free(m);
     cheby_free(m);
+    amg_free(m);
     if (m->rowgrouped) mat_free(m->rowgrouped);
     coo_free_bins(m);
     delete m;
@@ -815,6 +816,10 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
         SPMV_REQUIRE(value == 0 || value == 1, "ilu0_order: 0 (row order) or 1 (multicolour), got %lld", (long long)value);
         m->ilu_order = (int32_t)value;
     }
+    else if (int arc = SPMV_OK; amg_set_param(m, name, value, &arc))  // "amg_level_kernel": at the next set-up
+    {
+        if (arc != SPMV_OK) return arc;
+    }
     else if (int crc = SPMV_OK; cheby_set_param(m, name, value, &crc))  // "cheby_degree", "cheby_ratio", "cheby_lanczos_steps": at the next set-up
         return crc;
     else if (!strcmp(name, "twophase_panel_cols"))  // takes effect at the next spmv_mat_set_kernel(TWOPHASE)
@@ -911,6 +916,7 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         SPMV_REQUIRE(ilu0_info(m, name, value) == SPMV_OK, "unknown parameter '%s'", name);
         return SPMV_OK;
     }
+    if (amg_get_param(m, name, value)) return SPMV_OK;  // "amg_ready", "amg_levels", "amg_bytes", "amg_launches", "amg_mis_rounds", "amg_level_kernel"
     if (cheby_get_param(m, name, value)) return SPMV_OK;  // "cheby_ready", "cheby_degree", "cheby_bytes", "cheby_launches", ...
     if (transpose_get_param(m, name, value)) return SPMV_OK;  // "transpose_ready", "transpose_bytes", "transpose_kernel", ...
     if (!strcmp(name, "panel_keep_csr"))
@@ -1299,10 +1305,10 @@ int spmv_apply_dot(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec
 
 // The five solves.  Every check is made before the device is touched, so that they hold (and are tested) on a machine without one;
 // the checks they share and what each solver's refusals depend on (solver_rules) are solver_host.hpp's.
-static const solver_rules kCgRules       = {"spmv_cg", "the matrix", true, nullptr, nullptr, solver_rules::jacobi_arrays_unsupported, nullptr};
-static const solver_rules kCgMultiRules  = {"spmv_cg_multi", "the matrix", false, "k columns", "k columns", solver_rules::jacobi_arrays_elsewhere, "k columns"};
-static const solver_rules kBicgstabRules = {"spmv_bicgstab", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr};
-static const solver_rules kGmresRules    = {"spmv_gmres", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr};
+static const solver_rules kCgRules       = {"spmv_cg", "the matrix", true, nullptr, nullptr, solver_rules::jacobi_arrays_unsupported, nullptr, nullptr};
+static const solver_rules kCgMultiRules  = {"spmv_cg_multi", "the matrix", false, "k columns", "k columns", solver_rules::jacobi_arrays_elsewhere, "k columns", "k columns"};
+static const solver_rules kBicgstabRules = {"spmv_bicgstab", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr};
+static const solver_rules kGmresRules    = {"spmv_gmres", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr};
 
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
             int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
@@ -1502,6 +1508,44 @@ int spmv_chebyshev_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, sp
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
     return cheby_apply(ctx, A, r->d, z->d);
+}
+
+// Aggregation AMG (amg.hip).  Every check is made before the device is touched.
+int spmv_amg_setup(spmv_ctx* ctx, spmv_mat* A, int32_t max_levels, int32_t coarse_max, int32_t smooth_degree, double strength, double overcorrection)
+{
+    SPMV_REQUIRE(ctx && A, "spmv_amg_setup: null argument");
+    SPMV_TRY(amg_check_setup(A, max_levels, coarse_max, smooth_degree, strength, overcorrection, "spmv_amg_setup"));
+    SPMV_REQUIRE(A->ctx == ctx, "spmv_amg_setup: the matrix belongs to another context");
+    SPMV_TRY(use_device(ctx));
+    return amg_setup(ctx, A, max_levels, coarse_max, smooth_degree, strength, overcorrection);
+}
+
+int spmv_amg_info(const spmv_mat* A, int32_t* levels, int64_t* rows, int64_t* nnz)
+{
+    SPMV_REQUIRE(A && levels, "spmv_amg_info: null argument");
+    return amg_info(A, levels, rows, nnz);
+}
+
+int spmv_amg_level(spmv_ctx* ctx, const spmv_mat* A, int32_t level, int32_t* agg_host, int32_t* row_ptr, int32_t* col, double* val)
+{
+    SPMV_REQUIRE(ctx && A, "spmv_amg_level: null argument");
+    SPMV_TRY(amg_check_handle(A, "spmv_amg_level"));
+    if (!A->amg) SPMV_FAIL(SPMV_ERR_INVALID, "spmv_amg_level: the handle was not set up (spmv_amg_setup)");
+    SPMV_TRY(use_device(ctx));
+    return amg_level_download(ctx, A, level, agg_host, row_ptr, col, val);
+}
+
+int spmv_amg_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z)
+{
+    SPMV_REQUIRE(ctx && A && r && z, "spmv_amg_solve: null argument");
+    SPMV_TRY(amg_check_handle(A, "spmv_amg_solve"));
+    SPMV_REQUIRE(r->n == A->nrow && z->n == A->nrow, "spmv_amg_solve: r has %lld and z %lld entries, the matrix %d rows", (long long)r->n,
+                 (long long)z->n, A->nrow);
+    SPMV_REQUIRE(vectors_disjoint(r, z), "spmv_amg_solve: r and z must not overlap");
+    if (!A->amg) SPMV_FAIL(SPMV_ERR_INVALID, "spmv_amg_solve: the handle was not set up (spmv_amg_setup)");
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return amg_apply(ctx, A, r->d, z->d);
 }
 
 int spmv_chebyshev(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x)

@@ -1,0 +1,912 @@
+// amg.hip — aggregation algebraic multigrid (SPMV_PRECOND_AMG, spmv_amg_*): a deterministic device set-up and one V(1,1) cycle
+// z = B r, device-resident, on CDNA4 (gfx950).  tests/amg_ref.py is the NumPy twin of every line below.
+//
+// The method.  Level 0 is the handle's own CSR arrays; level l + 1 is built from level l until level l is the coarsest:
+// n_l <= coarse_max, or l + 1 == max_levels, or the next level would hold more than 0.8 n_l rows (5 n_c > 4 n_l: stalled).
+//
+// Strength.  Every row needs a stored non-zero diagonal entry (duplicates summed, as Jacobi reads it).  theta <= 0: every stored
+// entry a_ij with j != i makes j a neighbour of i.  theta > 0: j != i is a neighbour iff a_ij^2 >= theta^2 |a_ii a_jj|, per
+// stored entry.  The graph is what the row lists give: nothing is symmetrised.
+//
+// Aggregation by MIS(2).  The priority of row i is the pair (h(i), i), compared as unsigned numbers, the hash first; h is the
+// 32-bit finaliser h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16 of i.  It travels as the 64-bit key
+// (h << 32 | i) + 1, so that 0 is below every priority.  All rows start undecided.  One round: t_i = the priority of an
+// undecided row, 0 otherwise; twice t_i <- max(t_i, max over the neighbours j of t_j), from one buffer into another; an
+// undecided row whose t is its own priority becomes a root; the flag "is a root" is spread twice the same way; an undecided
+// row that the flag reaches is removed.  Rounds run until no row is undecided (the host reads one counter per round; the
+// largest undecided priority always becomes a root, so the loop ends).  Roots take the aggregate ids 0, 1, .. in ascending row
+// order (an exclusive scan).  Pass 1: a row that is no root and has roots among its neighbours joins the one of smallest id.
+// Pass 2: every row still free joins the smallest aggregate id among its neighbours as pass 1 left them.  A removed row has a
+// root within two steps of its own row lists, so pass 2 leaves no row free.  Nothing depends on the order of the launches.
+//
+// Coarse operator.  A_c[I, J] = sum of a_ij over ALL stored entries with agg(i) = I and agg(j) = J.  Entry ids are ordered
+// stably by (I, J) (two passes of sort_ids_by_key, J first), runs of equal keys are marked and counted by a scan, and one lane
+// per coarse entry adds its run from 0.0 left to right in that order - plain additions, so the sum is defined.  The result is
+// CSR with ascending columns, in a handle of its own that goes through the engine's kernel selection ("amg_level_kernel" != 0
+// forces that kernel id on every coarse handle).  Beside agg every level keeps the member lists agg_ptr / agg_rows (rows
+// ascending within an aggregate: one more stable sort).
+//
+// Smoother.  Every level holds the Chebyshev state of chebyshev.hip with degree smooth_degree, Jacobi scaling, lmax the row
+// bound and lmin = lmax / 30; level 0's is the handle's own (spmv_amg_setup replaces it, as spmv_chebyshev_setup would).
+//
+// Coarsest solve.  n_L <= 1024: the host downloads the operator and inverts it densely by LU with partial pivoting, in double
+// (a pivot below 2^-44 of the largest entry: SPMV_ERR_INVALID, "singular coarsest operator"); the inverse goes to the device
+// row-major and x_L = inverse b_L is one launch, a wavefront per row.  n_L > 1024: one Chebyshev application of that level.
+//
+// Cycle.  On level l with right-hand side b_l (b_0 = r, x_0 = z; r is never written):
+//   x_l = M_l^-1 b_l                              cheby_apply
+//   w = A_l x_l;  b_{l+1}[I] = sum over the members i of I, ascending, of (b_l[i] - w[i]), from 0.0      amg_restrict_kernel
+//   x_{l+1} = cycle(l + 1)
+//   x_l[i] += omega x_{l+1}[agg(i)]               amg_prolong_add_kernel
+//   x_l += M_l^-1 (b_l - A_l x_l)                 cheby_smooth
+// 4 d + 7 launches a level (d = smooth_degree) and 1 (dense) or 2 d + 1 (Chebyshev) at the coarsest: "amg_launches".  The state
+// owns b_l, x_l (l >= 1) and w_l; an application allocates nothing and reads nothing back.  Every sum has a fixed order.
+#include <cmath>
+#include <memory>
+
+#include "common.hpp"
+#include "solver_host.hpp"
+#include "wave.hpp"
+
+namespace spmv
+{
+struct amg_level
+{
+    int64_t   n = 0, nnz = 0;
+    spmv_mat* A = nullptr;  // level 0: the handle itself (borrowed); else an internal CSR handle, owned
+    int64_t   nc = 0;       // aggregates (0 on the coarsest level)
+    int32_t * agg = nullptr, *agg_ptr = nullptr, *agg_rows = nullptr;  // [n], [nc + 1], [n]; null on the coarsest level
+    double *  b = nullptr, *x = nullptr, *w = nullptr;                 // into the slab; b and x null on level 0
+};
+
+struct amg_state
+{
+    std::vector<amg_level> lv;
+    int32_t max_levels = 0, coarse_max = 0, degree = 0;
+    double  strength = 0.0, omega = 0.0;
+    double* inv  = nullptr;  // the coarsest operator's inverse, row-major (null: Chebyshev serves the coarsest level)
+    double* slab = nullptr;  // the levels' vectors
+    int64_t bytes = 0;
+    int32_t mis_rounds = 0;
+};
+
+namespace
+{
+constexpr int     kAmgMaxLevels = 32, kAmgDenseMax = 1024, kAmgMaxDegree = 64, kAmgMaxRounds = 4096;
+constexpr int32_t kUndecided = 0, kRoot = 1, kRemoved = 2;
+
+// ---- set-up kernels --------------------------------------------------------------------------------------------------------------
+static __host__ __device__ __forceinline__ uint32_t amg_hash(uint32_t h)
+{
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    h ^= h >> 16;
+    return h;
+}
+static __device__ __forceinline__ uint64_t amg_priority(int64_t i) { return (((uint64_t)amg_hash((uint32_t)i) << 32) | (uint32_t)i) + 1; }
+
+template <bool STRONG>
+static __device__ __forceinline__ bool amg_neighbour(int64_t i, int j, double a, const double* __restrict__ diag, double theta2)
+{
+    if (j == i) return false;
+    if constexpr (STRONG)
+        return a * a >= theta2 * fabs(diag[i] * diag[j]);
+    else
+        return true;
+}
+
+// diag[i] = a_ii, duplicates summed; a zero or missing entry is counted
+__global__ __launch_bounds__(kBlock) void amg_diag_kernel(int64_t n, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                          const double* __restrict__ val, double* __restrict__ diag, int32_t* __restrict__ zeros)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    {
+        double    d   = 0.0;
+        const int end = row_ptr[i + 1];
+        for (int e = row_ptr[i]; e < end; ++e)
+            if (col[e] == i) d += val[e];
+        diag[i] = d;
+        if (d == 0.0) atomicAdd(zeros, 1);
+    }
+}
+
+// out_i = max(v_i, max over the neighbours j of v_j), one lane per row.  What v is:
+enum : int
+{
+    kSrcPriority = 0,  // the priority of an undecided row, 0 otherwise (from state)
+    kSrcBuffer   = 1,  // in[]
+    kSrcRoot     = 2   // 1 for a root - of an earlier round (state) or of this one (undecided, in[] is its own priority) - 0 otherwise
+};
+template <int SRC>
+static __device__ __forceinline__ uint64_t amg_source(int64_t j, const int32_t* __restrict__ state, const uint64_t* __restrict__ in)
+{
+    if constexpr (SRC == kSrcPriority)
+        return state[j] == kUndecided ? amg_priority(j) : 0;
+    else if constexpr (SRC == kSrcBuffer)
+        return in[j];
+    else
+    {
+        const int32_t s = state[j];
+        return (s == kRoot || (s == kUndecided && in[j] == amg_priority(j))) ? 1 : 0;
+    }
+}
+template <int SRC, bool STRONG>
+__global__ __launch_bounds__(kBlock) void amg_propagate_kernel(int64_t n, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                               const double* __restrict__ val, const double* __restrict__ diag, double theta2,
+                                                               const int32_t* __restrict__ state, const uint64_t* __restrict__ in,
+                                                               uint64_t* __restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    {
+        uint64_t  t   = amg_source<SRC>(i, state, in);
+        const int end = row_ptr[i + 1];
+        for (int e = row_ptr[i]; e < end; ++e)
+        {
+            const int j = col[e];
+            if (amg_neighbour<STRONG>(i, j, STRONG ? val[e] : 0.0, diag, theta2)) t = max(t, amg_source<SRC>(j, state, in));
+        }
+        out[i] = t;
+    }
+}
+
+// the end of a round: an undecided row whose t is its own priority becomes a root, one that the root flag reached is removed,
+// the others are counted
+__global__ __launch_bounds__(kBlock) void amg_update_kernel(int64_t n, const uint64_t* __restrict__ t, const uint64_t* __restrict__ reached,
+                                                            int32_t* __restrict__ state, int32_t* __restrict__ undecided)
+{
+    int left = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    {
+        if (state[i] != kUndecided) continue;
+        if (t[i] == amg_priority(i))
+            state[i] = kRoot;
+        else if (reached[i])
+            state[i] = kRemoved;
+        else
+            ++left;
+    }
+    if (left) atomicAdd(undecided, left);  // (an integer sum: the order does not matter)
+}
+
+// flag[i] = 1 for a root, i < n;  flag[n] = 0: the scan of n + 1 entries ends on the number of roots
+__global__ __launch_bounds__(kBlock) void amg_root_flag_kernel(int64_t n, const int32_t* __restrict__ state, int32_t* __restrict__ flag)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= n; i += (int64_t)gridDim.x * kBlock)
+        flag[i] = (i < n && state[i] == kRoot) ? 1 : 0;
+}
+
+// pass 1: a root takes its id; another row the smallest id among the roots of its neighbours, or -1
+template <bool STRONG>
+__global__ __launch_bounds__(kBlock) void amg_pass1_kernel(int64_t n, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                           const double* __restrict__ val, const double* __restrict__ diag, double theta2,
+                                                           const int32_t* __restrict__ state, const int32_t* __restrict__ root_id,
+                                                           int32_t* __restrict__ agg)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    {
+        int32_t best = INT32_MAX;
+        if (state[i] == kRoot)
+            best = root_id[i];
+        else
+        {
+            const int end = row_ptr[i + 1];
+            for (int e = row_ptr[i]; e < end; ++e)
+            {
+                const int j = col[e];
+                if (amg_neighbour<STRONG>(i, j, STRONG ? val[e] : 0.0, diag, theta2) && state[j] == kRoot) best = min(best, root_id[j]);
+            }
+        }
+        agg[i] = best == INT32_MAX ? -1 : best;
+    }
+}
+
+// pass 2: a row still free takes the smallest aggregate id among its neighbours as pass 1 left them; a row that stays free
+// (there is none: see the header) is counted
+template <bool STRONG>
+__global__ __launch_bounds__(kBlock) void amg_pass2_kernel(int64_t n, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                           const double* __restrict__ val, const double* __restrict__ diag, double theta2,
+                                                           const int32_t* __restrict__ agg1, int32_t* __restrict__ agg, int32_t* __restrict__ count,
+                                                           int32_t* __restrict__ free_rows)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    {
+        int32_t mine = agg1[i];
+        if (mine < 0)
+        {
+            int32_t   best = INT32_MAX;
+            const int end  = row_ptr[i + 1];
+            for (int e = row_ptr[i]; e < end; ++e)
+            {
+                const int j = col[e];
+                if (!amg_neighbour<STRONG>(i, j, STRONG ? val[e] : 0.0, diag, theta2)) continue;
+                const int32_t a = agg1[j];
+                if (a >= 0) best = min(best, a);
+            }
+            mine = best == INT32_MAX ? -1 : best;
+        }
+        agg[i] = mine;
+        if (mine < 0)
+            atomicAdd(free_rows, 1);
+        else
+            atomicAdd(count + mine, 1);  // members per aggregate (an integer sum)
+    }
+}
+
+// the key (I, J) of every stored entry
+__global__ __launch_bounds__(kBlock) void amg_key_kernel(int64_t n, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                         const int32_t* __restrict__ agg, int32_t* __restrict__ key_i, int32_t* __restrict__ key_j)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    {
+        const int32_t I   = agg[i];
+        const int     end = row_ptr[i + 1];
+        for (int e = row_ptr[i]; e < end; ++e)
+        {
+            key_i[e] = I;
+            key_j[e] = agg[col[e]];
+        }
+    }
+}
+
+// out[k] = src[idx[k]]
+__global__ __launch_bounds__(kBlock) void amg_gather_kernel(int64_t n, const int32_t* __restrict__ src, const int32_t* __restrict__ idx,
+                                                            int32_t* __restrict__ out)
+{
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock) out[k] = src[idx[k]];
+}
+
+// head[k] = 1 where the k-th entry in (I, J) order starts a run, k < nnz;  head[nnz] = 0
+__global__ __launch_bounds__(kBlock) void amg_head_kernel(int64_t nnz, const int32_t* __restrict__ order, const int32_t* __restrict__ key_i,
+                                                          const int32_t* __restrict__ key_j, int32_t* __restrict__ head)
+{
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k <= nnz; k += (int64_t)gridDim.x * kBlock)
+    {
+        int32_t h = 0;
+        if (k < nnz)
+        {
+            const int32_t e = order[k];
+            h               = 1;
+            if (k > 0)
+            {
+                const int32_t p = order[k - 1];
+                h               = (key_i[e] != key_i[p] || key_j[e] != key_j[p]) ? 1 : 0;
+            }
+        }
+        head[k] = h;
+    }
+}
+
+// every run's start, column and row: seg_start[s] (and seg_start[runs] = nnz), col_c[s] = J, and the entries per coarse row
+__global__ __launch_bounds__(kBlock) void amg_segment_kernel(int64_t nnz, const int32_t* __restrict__ order, const int32_t* __restrict__ key_i,
+                                                             const int32_t* __restrict__ key_j, const int32_t* __restrict__ head,
+                                                             const int32_t* __restrict__ run_of, int32_t* __restrict__ seg_start,
+                                                             int32_t* __restrict__ col_c, int32_t* __restrict__ row_count)
+{
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k <= nnz; k += (int64_t)gridDim.x * kBlock)
+    {
+        if (k == nnz)
+            seg_start[run_of[k]] = (int32_t)nnz;
+        else if (head[k])
+        {
+            const int32_t s = run_of[k], e = order[k];
+            seg_start[s]    = (int32_t)k;
+            col_c[s]        = key_j[e];
+            atomicAdd(row_count + key_i[e], 1);
+        }
+    }
+}
+
+// one lane per coarse entry: its run from 0.0, left to right, plain additions
+__global__ __launch_bounds__(kBlock) void amg_run_sum_kernel(int64_t runs, const int32_t* __restrict__ seg_start, const int32_t* __restrict__ order,
+                                                             const double* __restrict__ val, double* __restrict__ val_c)
+{
+    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < runs; s += (int64_t)gridDim.x * kBlock)
+    {
+        double    acc = 0.0;
+        const int end = seg_start[s + 1];
+        for (int k = seg_start[s]; k < end; ++k) acc += val[order[k]];
+        val_c[s] = acc;
+    }
+}
+
+// ---- cycle kernels ---------------------------------------------------------------------------------------------------------------
+// b_c[I] = sum over the members i of I, ascending, of (b[i] - w[i]), from 0.0: one lane per aggregate, no atomics
+__global__ __launch_bounds__(kBlock) void amg_restrict_kernel(int64_t nc, const int32_t* __restrict__ agg_ptr, const int32_t* __restrict__ agg_rows,
+                                                              const double* __restrict__ b, const double* __restrict__ w, double* __restrict__ b_c)
+{
+    for (int64_t I = (int64_t)blockIdx.x * kBlock + threadIdx.x; I < nc; I += (int64_t)gridDim.x * kBlock)
+    {
+        double    acc = 0.0;
+        const int end = agg_ptr[I + 1];
+        for (int k = agg_ptr[I]; k < end; ++k)
+        {
+            const int i = agg_rows[k];
+            acc += b[i] - w[i];
+        }
+        b_c[I] = acc;
+    }
+}
+
+// x[i] += omega x_c[agg[i]].  WIDE: x is 16-byte aligned (agg always is): two elements per lane, an odd last one by one lane
+template <bool WIDE>
+__global__ __launch_bounds__(kBlock) void amg_prolong_add_kernel(int64_t n, double omega, const int32_t* __restrict__ agg,
+                                                                 const double* __restrict__ x_c, double* __restrict__ x)
+{
+    const int64_t stride = (int64_t)gridDim.x * kBlock, first = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if constexpr (WIDE)
+    {
+        const int64_t npairs = n / 2;
+        for (int64_t i = first; i < npairs; i += stride)
+        {
+            const i32x2 a  = ((const i32x2*)agg)[i];
+            const f64x2 xv = ((const f64x2*)x)[i];
+            ((f64x2*)x)[i] = f64x2{fma(omega, x_c[a[0]], xv[0]), fma(omega, x_c[a[1]], xv[1])};
+        }
+    }
+    const bool    lead = blockIdx.x == 0 && threadIdx.x == 0;
+    const int64_t from = WIDE ? (((n & 1) && lead) ? n - 1 : n) : first;
+    for (int64_t i = from; i < n; i += stride) x[i] = fma(omega, x_c[agg[i]], x[i]);
+}
+
+// x = inverse b: one wavefront per row of the row-major inverse, lanes stride the columns, the fixed butterfly of wave.hpp
+__global__ __launch_bounds__(kBlock) void amg_dense_apply_kernel(int n, const double* __restrict__ inv, const double* __restrict__ b,
+                                                                 double* __restrict__ x)
+{
+    const int row = blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    if (row >= n) return;  // (a whole wavefront: no lane of it takes part in the butterfly)
+    const double* r   = inv + (size_t)row * n;
+    double        acc = 0.0;
+    for (int c = threadIdx.x & 63; c < n; c += kWave) acc = fma(r[c], b[c], acc);
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) x[row] = acc;
+}
+
+// ---- host helpers ----------------------------------------------------------------------------------------------------------------
+// device memory of a set-up step: freed, behind the stream, when the step returns however it returns
+struct device_pool
+{
+    spmv_ctx*          ctx;
+    const char*        who;
+    std::vector<void*> held;
+    device_pool(spmv_ctx* c, const char* w) : ctx(c), who(w) {}
+    device_pool(const device_pool&)            = delete;
+    device_pool& operator=(const device_pool&) = delete;
+    ~device_pool()
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void* p : held) (void)hipFree(p);
+    }
+    template <typename T>
+    int get(T*& out, size_t count)
+    {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            SPMV_FAIL(SPMV_ERR_ALLOC, "%s: out of device memory for %zu bytes of set-up memory", who, count * sizeof(T));
+        }
+        held.push_back(p);
+        out = (T*)p;
+        return SPMV_OK;
+    }
+    void keep(void* p) { held.erase(std::remove(held.begin(), held.end(), p), held.end()); }  // the caller owns p from here on
+};
+
+int key_bits(int64_t values)
+{
+    int bits = 1;
+    while (bits < 31 && ((int64_t)1 << bits) < values) ++bits;
+    return bits;
+}
+
+void free_state(amg_state* st)
+{
+    if (!st) return;
+    for (size_t l = 0; l < st->lv.size(); ++l)
+    {
+        amg_level& L = st->lv[l];
+        for (void* p : {(void*)L.agg, (void*)L.agg_ptr, (void*)L.agg_rows})
+            if (p) (void)hipFree(p);
+        if (l > 0 && L.A) mat_free(L.A);
+    }
+    if (st->inv) (void)hipFree(st->inv);
+    if (st->slab) (void)hipFree(st->slab);
+    delete st;
+}
+
+#define SPMV_AMG_BY_STRENGTH(strong, launch_true, launch_false) \
+    do                                                          \
+    {                                                           \
+        if (strong) launch_true; else launch_false;             \
+    } while (0)
+
+// the aggregates of one level: agg[n] (the caller's from here on), their number, the members per aggregate, the rounds
+int aggregate(spmv_ctx* ctx, const spmv_mat* A, int level, double theta, int32_t** agg_out, int32_t** count_out, int64_t* nc_out, int32_t* rounds_out)
+{
+    const char* const who = "spmv_amg_setup";
+    const int64_t     n   = A->nrow;
+    hipStream_t       s   = ctx->stream;
+    const int         grid = stream_grid(n);
+    const bool        strong = theta > 0.0;
+    const double      theta2 = theta * theta;
+    device_pool       pool(ctx, who);
+    double*           diag;
+    int32_t *         state, *counters, *flag, *root_id, *agg1, *agg, *count;
+    uint64_t *        ta, *tb, *tc;
+    SPMV_TRY(pool.get(diag, (size_t)n));
+    SPMV_TRY(pool.get(state, (size_t)n));
+    SPMV_TRY(pool.get(counters, 4));
+    SPMV_TRY(pool.get(ta, (size_t)n));
+    SPMV_TRY(pool.get(tb, (size_t)n));
+    SPMV_TRY(pool.get(tc, (size_t)n));
+    SPMV_TRY(hip_step(hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), s), who, "clearing the counters"));
+    SPMV_TRY(hip_step(hipMemsetAsync(state, 0, sizeof(int32_t) * (size_t)n, s), who, "clearing the states"));
+    hipLaunchKernelGGL(amg_diag_kernel, dim3(grid), dim3(kBlock), 0, s, n, A->a, A->b, A->v, diag, counters);
+    int32_t h[4] = {0, 0, 0, 0};
+    SPMV_TRY(read_scalars(ctx, h, counters, sizeof(h), who));
+    SPMV_REQUIRE(h[0] == 0, "%s: the operator of level %d has %d rows with a zero or missing diagonal entry", who, level, h[0]);
+#define SPMV_AMG_PROPAGATE(SRC, in, out)                                                                                                         \
+    SPMV_AMG_BY_STRENGTH(strong,                                                                                                                  \
+                         hipLaunchKernelGGL((amg_propagate_kernel<SRC, true>), dim3(grid), dim3(kBlock), 0, s, n, A->a, A->b, A->v,              \
+                                            (const double*)diag, theta2, (const int32_t*)state, (const uint64_t*)in, out),                        \
+                         hipLaunchKernelGGL((amg_propagate_kernel<SRC, false>), dim3(grid), dim3(kBlock), 0, s, n, A->a, A->b, A->v,             \
+                                            (const double*)diag, theta2, (const int32_t*)state, (const uint64_t*)in, out))
+    int rounds = 0;
+    for (;;)
+    {
+        SPMV_REQUIRE(rounds < kAmgMaxRounds, "%s: the aggregation of level %d did not end within %d rounds", who, level, kAmgMaxRounds);
+        SPMV_TRY(hip_step(hipMemsetAsync(counters + 1, 0, sizeof(int32_t), s), who, "clearing the counter of undecided rows"));
+        SPMV_AMG_PROPAGATE(kSrcPriority, tc, ta);  // (reads the states alone)
+        SPMV_AMG_PROPAGATE(kSrcBuffer, ta, tb);
+        SPMV_AMG_PROPAGATE(kSrcRoot, tb, ta);
+        SPMV_AMG_PROPAGATE(kSrcBuffer, ta, tc);
+        hipLaunchKernelGGL(amg_update_kernel, dim3(grid), dim3(kBlock), 0, s, n, (const uint64_t*)tb, (const uint64_t*)tc, state, counters + 1);
+        SPMV_TRY(hip_step(hipGetLastError(), who, "a launch of an aggregation round"));
+        ++rounds;
+        SPMV_TRY(read_scalars(ctx, h, counters, sizeof(h), who));
+        if (h[1] == 0) break;
+    }
+#undef SPMV_AMG_PROPAGATE
+    SPMV_TRY(pool.get(flag, (size_t)n + 1));
+    SPMV_TRY(pool.get(root_id, (size_t)n + 1));
+    hipLaunchKernelGGL(amg_root_flag_kernel, dim3(stream_grid(n + 1)), dim3(kBlock), 0, s, n, (const int32_t*)state, flag);
+    SPMV_TRY(exclusive_scan_i32(ctx, flag, root_id, n + 1));
+    int32_t nc = 0;
+    SPMV_TRY(read_scalars(ctx, &nc, root_id + n, sizeof(nc), who));
+    SPMV_REQUIRE(nc >= 1 && nc <= n, "%s: level %d counts %d roots among %lld rows", who, level, nc, (long long)n);
+    SPMV_TRY(pool.get(agg1, (size_t)n));
+    SPMV_TRY(pool.get(agg, (size_t)n));
+    SPMV_TRY(pool.get(count, (size_t)nc + 1));
+    SPMV_TRY(hip_step(hipMemsetAsync(count, 0, sizeof(int32_t) * ((size_t)nc + 1), s), who, "clearing the member counts"));
+    SPMV_AMG_BY_STRENGTH(strong,
+                         hipLaunchKernelGGL(amg_pass1_kernel<true>, dim3(grid), dim3(kBlock), 0, s, n, A->a, A->b, A->v, (const double*)diag, theta2,
+                                            (const int32_t*)state, (const int32_t*)root_id, agg1),
+                         hipLaunchKernelGGL(amg_pass1_kernel<false>, dim3(grid), dim3(kBlock), 0, s, n, A->a, A->b, A->v, (const double*)diag, theta2,
+                                            (const int32_t*)state, (const int32_t*)root_id, agg1));
+    SPMV_AMG_BY_STRENGTH(strong,
+                         hipLaunchKernelGGL(amg_pass2_kernel<true>, dim3(grid), dim3(kBlock), 0, s, n, A->a, A->b, A->v, (const double*)diag, theta2,
+                                            (const int32_t*)agg1, agg, count, counters + 2),
+                         hipLaunchKernelGGL(amg_pass2_kernel<false>, dim3(grid), dim3(kBlock), 0, s, n, A->a, A->b, A->v, (const double*)diag, theta2,
+                                            (const int32_t*)agg1, agg, count, counters + 2));
+    SPMV_TRY(hip_step(hipGetLastError(), who, "a launch of the aggregation passes"));
+    SPMV_TRY(read_scalars(ctx, h, counters, sizeof(h), who));
+    SPMV_REQUIRE(h[2] == 0, "%s: %d rows of level %d were left without an aggregate", who, h[2], level);
+    pool.keep(agg);
+    pool.keep(count);
+    *agg_out    = agg;
+    *count_out  = count;
+    *nc_out     = nc;
+    *rounds_out = rounds;
+    return SPMV_OK;
+}
+#undef SPMV_AMG_BY_STRENGTH
+
+// the member lists of a level: agg_ptr (the scan of the member counts) and agg_rows (rows by aggregate, ascending within one)
+int member_lists(spmv_ctx* ctx, amg_level& L, const int32_t* count)
+{
+    const char* const who = "spmv_amg_setup";
+    void *            p = nullptr, *q = nullptr;
+    if (hipMalloc(&p, sizeof(int32_t) * ((size_t)L.nc + 1)) != hipSuccess || hipMalloc(&q, sizeof(int32_t) * (size_t)L.n) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        SPMV_FAIL(SPMV_ERR_ALLOC, "%s: out of device memory for the member lists of %lld rows", who, (long long)L.n);
+    }
+    L.agg_ptr  = (int32_t*)p;
+    L.agg_rows = (int32_t*)q;
+    SPMV_TRY(exclusive_scan_i32(ctx, count, L.agg_ptr, L.nc + 1));
+    return sort_ids_by_key(ctx, L.agg, L.n, key_bits(L.nc), L.agg_rows);
+}
+
+// A_c = P^T A P over every stored entry, as a CSR handle of its own
+int coarse_operator(spmv_ctx* ctx, const spmv_mat* A, const int32_t* agg, int64_t nc, int32_t level_kernel, spmv_mat** out)
+{
+    const char* const who = "spmv_amg_setup";
+    const int64_t     n = A->nrow, nnz = A->nnz;
+    hipStream_t       s    = ctx->stream;
+    const int         bits = key_bits(nc), grid_e = stream_grid(nnz + 1);
+    device_pool       pool(ctx, who);
+    int32_t *         key_i, *key_j, *ids1, *key_i1, *ids2, *order, *head, *run_of, *seg_start, *row_count;
+    SPMV_TRY(pool.get(key_i, (size_t)nnz));
+    SPMV_TRY(pool.get(key_j, (size_t)nnz));
+    SPMV_TRY(pool.get(ids1, (size_t)nnz));
+    SPMV_TRY(pool.get(key_i1, (size_t)nnz));
+    SPMV_TRY(pool.get(ids2, (size_t)nnz));
+    SPMV_TRY(pool.get(order, (size_t)nnz));
+    hipLaunchKernelGGL(amg_key_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, A->a, A->b, agg, key_i, key_j);
+    SPMV_TRY(hip_step(hipGetLastError(), who, "the key map's launch"));
+    SPMV_TRY(sort_ids_by_key(ctx, key_j, nnz, bits, ids1));
+    hipLaunchKernelGGL(amg_gather_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)key_i, (const int32_t*)ids1, key_i1);
+    SPMV_TRY(sort_ids_by_key(ctx, key_i1, nnz, bits, ids2));
+    hipLaunchKernelGGL(amg_gather_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)ids1, (const int32_t*)ids2, order);
+    SPMV_TRY(pool.get(head, (size_t)nnz + 1));
+    SPMV_TRY(pool.get(run_of, (size_t)nnz + 1));
+    hipLaunchKernelGGL(amg_head_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)order, (const int32_t*)key_i, (const int32_t*)key_j, head);
+    SPMV_TRY(hip_step(hipGetLastError(), who, "the head marking's launch"));
+    SPMV_TRY(exclusive_scan_i32(ctx, head, run_of, nnz + 1));
+    int32_t runs = 0;
+    SPMV_TRY(read_scalars(ctx, &runs, run_of + nnz, sizeof(runs), who));
+    SPMV_REQUIRE(runs >= 1 && runs <= nnz, "%s: %d coarse entries from %lld entries", who, runs, (long long)nnz);
+    SPMV_TRY(pool.get(seg_start, (size_t)runs + 1));
+    SPMV_TRY(pool.get(row_count, (size_t)nc + 1));
+    SPMV_TRY(hip_step(hipMemsetAsync(row_count, 0, sizeof(int32_t) * ((size_t)nc + 1), s), who, "clearing the coarse row counts"));
+    spmv_mat* C = nullptr;
+    SPMV_TRY(mat_alloc(ctx, SPMV_FMT_CSR, (int32_t)nc, (int32_t)nc, runs, 0, (size_t)nc + 1, (size_t)runs, (size_t)runs, &C));
+    hipLaunchKernelGGL(amg_segment_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)order, (const int32_t*)key_i, (const int32_t*)key_j,
+                       (const int32_t*)head, (const int32_t*)run_of, seg_start, const_cast<int32_t*>(C->b), row_count);
+    int rc = hip_step(hipGetLastError(), who, "the segment kernel's launch");
+    if (rc == SPMV_OK) rc = exclusive_scan_i32(ctx, row_count, const_cast<int32_t*>(C->a), nc + 1);
+    if (rc == SPMV_OK)
+    {
+        hipLaunchKernelGGL(amg_run_sum_kernel, dim3(stream_grid(runs)), dim3(kBlock), 0, s, (int64_t)runs, (const int32_t*)seg_start,
+                           (const int32_t*)order, A->v, const_cast<double*>(C->v));
+        rc = hip_step(hipGetLastError(), who, "the run sum's launch");
+    }
+    if (rc == SPMV_OK) rc = hip_step(hipStreamSynchronize(s), who, "waiting for the coarse operator");
+    if (rc == SPMV_OK)
+    {
+        if (level_kernel != SPMV_CSR_AUTO)
+        {
+            C->kernel_forced = true;
+            C->kernel        = level_kernel;
+        }
+        rc = csr_analyse(C);  // the engine's usual selection: the model and, where it pays, a trial
+    }
+    if (rc != SPMV_OK)
+    {
+        mat_free(C);
+        return rc;
+    }
+    *out = C;
+    return SPMV_OK;
+}
+
+// the inverse of the coarsest operator (n <= 1024): LU with partial pivoting on the host, in double
+int dense_inverse(spmv_ctx* ctx, const spmv_mat* A, double** inv_out)
+{
+#pragma clang fp contract(off)
+    const char* const who = "spmv_amg_setup";
+    const int         n   = A->nrow;
+    const size_t      nnz = (size_t)A->nnz;
+    std::vector<int32_t> rp((size_t)n + 1), cc(nnz);
+    std::vector<double>  cv(nnz), lu((size_t)n * n, 0.0), inv((size_t)n * n, 0.0);
+    hipError_t e = hipMemcpyAsync(rp.data(), A->a, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(cc.data(), A->b, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(cv.data(), A->v, sizeof(double) * nnz, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    SPMV_TRY(hip_step(e, who, "downloading the coarsest operator"));
+    double largest = 0.0;
+    for (int i = 0; i < n; ++i)
+        for (int k = rp[(size_t)i]; k < rp[(size_t)i + 1]; ++k) lu[(size_t)i * n + cc[(size_t)k]] += cv[(size_t)k];
+    for (double v : lu) largest = std::max(largest, std::fabs(v));
+    std::vector<int> perm((size_t)n);
+    for (int i = 0; i < n; ++i) perm[(size_t)i] = i;
+    for (int k = 0; k < n; ++k)
+    {
+        int p = k;
+        for (int i = k + 1; i < n; ++i)
+            if (std::fabs(lu[(size_t)i * n + k]) > std::fabs(lu[(size_t)p * n + k])) p = i;  // the first of the largest
+        const double pivot = lu[(size_t)p * n + k];
+        if (!(std::fabs(pivot) >= 0x1p-44 * largest) || pivot == 0.0)
+            SPMV_FAIL(SPMV_ERR_INVALID, "%s: singular coarsest operator (%d rows: pivot %g at step %d, largest entry %g)", who, n, pivot, k, largest);
+        if (p != k)
+        {
+            std::swap(perm[(size_t)p], perm[(size_t)k]);
+            for (int j = 0; j < n; ++j) std::swap(lu[(size_t)p * n + j], lu[(size_t)k * n + j]);
+        }
+        for (int i = k + 1; i < n; ++i)
+        {
+            const double m = lu[(size_t)i * n + k] / pivot;
+            lu[(size_t)i * n + k] = m;
+            if (m != 0.0)
+                for (int j = k + 1; j < n; ++j) lu[(size_t)i * n + j] -= m * lu[(size_t)k * n + j];
+        }
+    }
+    // inverse = U^-1 L^-1 P, every column of P at once: rows of `inv` are the right-hand sides' rows
+    for (int i = 0; i < n; ++i) inv[(size_t)i * n + perm[(size_t)i]] = 1.0;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < i; ++k)
+        {
+            const double m = lu[(size_t)i * n + k];
+            if (m != 0.0)
+                for (int j = 0; j < n; ++j) inv[(size_t)i * n + j] -= m * inv[(size_t)k * n + j];
+        }
+    for (int i = n - 1; i >= 0; --i)
+    {
+        for (int k = i + 1; k < n; ++k)
+        {
+            const double u = lu[(size_t)i * n + k];
+            if (u != 0.0)
+                for (int j = 0; j < n; ++j) inv[(size_t)i * n + j] -= u * inv[(size_t)k * n + j];
+        }
+        const double d = lu[(size_t)i * n + i];
+        for (int j = 0; j < n; ++j) inv[(size_t)i * n + j] /= d;
+    }
+    void* dev = nullptr;
+    if (hipMalloc(&dev, sizeof(double) * (size_t)n * n) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        SPMV_FAIL(SPMV_ERR_ALLOC, "%s: out of device memory for the inverse of %d rows", who, n);
+    }
+    e = hipMemcpyAsync(dev, inv.data(), sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess)
+    {
+        (void)hipFree(dev);
+        return hip_step(e, who, "uploading the inverse");
+    }
+    *inv_out = (double*)dev;
+    return SPMV_OK;
+}
+}  // namespace
+
+// ---- checks on the host: the leading fields of the handle alone ------------------------------------------------------------------
+int amg_check_handle(const spmv_mat* m, const char* who)
+{
+    if (m->format != SPMV_FMT_CSR) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: AMG needs a CSR handle (format %d)", who, m->format);
+    SPMV_REQUIRE(m->nrow == m->ncol && m->row_begin == 0, "%s: AMG needs the whole square matrix (%d x %d, first row %lld)", who, m->nrow, m->ncol,
+                 (long long)m->row_begin);
+    SPMV_REQUIRE(m->nnz == 0 || (m->b && m->v), "%s: the CSR arrays are gone (panel_keep_csr = 0 released them)", who);
+    return SPMV_OK;
+}
+
+int amg_check_setup(const spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection, const char* who)
+{
+    SPMV_REQUIRE(max_levels >= 0 && max_levels <= kAmgMaxLevels, "%s: max_levels=%d, must be 1 .. 32 (0: 16)", who, max_levels);
+    SPMV_REQUIRE(coarse_max >= 0 && coarse_max <= kAmgDenseMax, "%s: coarse_max=%d, must be 1 .. 1024 (0: 256)", who, coarse_max);
+    SPMV_REQUIRE(smooth_degree >= 0 && smooth_degree <= kAmgMaxDegree, "%s: smooth_degree=%d, must be 1 .. 64 (0: 2)", who, smooth_degree);
+    SPMV_REQUIRE(std::isfinite(strength), "%s: strength=%g, must be finite (<= 0: every stored entry)", who, strength);
+    SPMV_REQUIRE(overcorrection == 0.0 || (overcorrection > 0.0 && overcorrection < 2.0), "%s: overcorrection=%g, must be inside (0, 2) (0: 1.5)", who,
+                 overcorrection);
+    return amg_check_handle(m, who);
+}
+
+// ---- the state in the handle -----------------------------------------------------------------------------------------------------
+void amg_free(spmv_mat* m)
+{
+    if (!m->amg) return;
+    m->device_bytes -= m->amg->bytes;
+    free_state(m->amg);
+    m->amg = nullptr;
+}
+
+int amg_setup(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection)
+{
+    const char* const who = "spmv_amg_setup";
+    SPMV_TRY(amg_check_setup(m, max_levels, coarse_max, smooth_degree, strength, overcorrection, who));
+    auto deleter = [](amg_state* p) { free_state(p); };
+    std::unique_ptr<amg_state, decltype(deleter)> st(new amg_state(), deleter);
+    st->max_levels = max_levels ? max_levels : 16;
+    st->coarse_max = coarse_max ? coarse_max : 256;
+    st->degree     = smooth_degree ? smooth_degree : 2;
+    st->strength   = strength > 0.0 ? strength : 0.0;
+    st->omega      = overcorrection != 0.0 ? overcorrection : 1.5;
+    st->lv.emplace_back();
+    st->lv[0].A   = m;
+    st->lv[0].n   = m->nrow;
+    st->lv[0].nnz = m->nnz;
+    if (m->nrow > 0)
+    {
+        // the hierarchy
+        for (int l = 0;; ++l)
+        {
+            const int64_t n = st->lv[(size_t)l].n;
+            if (n <= st->coarse_max || l + 1 == st->max_levels) break;
+            int32_t *agg = nullptr, *count = nullptr;
+            int64_t  nc = 0;
+            int32_t  rounds = 0;
+            SPMV_TRY(aggregate(ctx, st->lv[(size_t)l].A, l, st->strength, &agg, &count, &nc, &rounds));
+            st->mis_rounds += rounds;
+            if (5 * nc > 4 * n)  // stalled: this level is the coarsest
+            {
+                (void)hipFree(agg);
+                (void)hipFree(count);
+                break;
+            }
+            {
+                amg_level& L = st->lv[(size_t)l];
+                L.agg        = agg;
+                L.nc         = nc;
+                const int rc = member_lists(ctx, L, count);
+                (void)hipStreamSynchronize(ctx->stream);
+                (void)hipFree(count);
+                SPMV_TRY(rc);
+                st->bytes += (int64_t)sizeof(int32_t) * (2 * n + nc + 1);
+            }
+            spmv_mat* C = nullptr;
+            SPMV_TRY(coarse_operator(ctx, st->lv[(size_t)l].A, agg, nc, m->amg_level_kernel, &C));
+            st->lv.emplace_back();
+            amg_level& N = st->lv.back();
+            N.A          = C;
+            N.n          = nc;
+            N.nnz        = C->nnz;
+            SPMV_TRY(cheby_setup(ctx, C, st->degree, /*scaled=*/1, 0.0, 0.0));
+        }
+        // the vectors: w on every level, b and x below level 0
+        const size_t nlev = st->lv.size();
+        size_t       doubles = 0;
+        for (size_t l = 0; l < nlev; ++l) doubles += SolveWorkspace::padded((size_t)st->lv[l].n) * (l == 0 ? 1 : 3);
+        if (hipMalloc(&st->slab, sizeof(double) * doubles) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            SPMV_FAIL(SPMV_ERR_ALLOC, "%s: out of device memory for the levels' vectors (%zu bytes)", who, sizeof(double) * doubles);
+        }
+        st->bytes += (int64_t)(sizeof(double) * doubles);
+        double* at = st->slab;
+        for (size_t l = 0; l < nlev; ++l)
+        {
+            const size_t sn = SolveWorkspace::padded((size_t)st->lv[l].n);
+            st->lv[l].w     = at;
+            at += sn;
+            if (l > 0)
+            {
+                st->lv[l].b = at;
+                st->lv[l].x = at + sn;
+                at += 2 * sn;
+            }
+        }
+        // the coarsest solve
+        const amg_level& last = st->lv.back();
+        if (last.n <= kAmgDenseMax)
+        {
+            SPMV_TRY(dense_inverse(ctx, last.A, &st->inv));
+            st->bytes += (int64_t)sizeof(double) * last.n * last.n;
+        }
+        for (size_t l = 1; l < nlev; ++l) st->bytes += st->lv[l].A->device_bytes;
+        // level 0's smoother is the handle's own Chebyshev state; it is replaced last, behind everything that can fail above
+        if (nlev > 1 || !st->inv) SPMV_TRY(cheby_setup(ctx, m, st->degree, /*scaled=*/1, 0.0, 0.0));
+    }
+    SPMV_TRY(hip_step(hipStreamSynchronize(ctx->stream), who, "waiting for the stream"));  // (an application of the earlier state may be in flight)
+    amg_free(m);
+    m->amg = st.release();
+    m->device_bytes += m->amg->bytes;
+    return SPMV_OK;
+}
+
+int amg_info(const spmv_mat* m, int32_t* levels, int64_t* rows, int64_t* nnz)
+{
+    const amg_state* st = m->amg;
+    if (!st) SPMV_FAIL(SPMV_ERR_INVALID, "spmv_amg_info: the handle was not set up (spmv_amg_setup)");
+    *levels = (int32_t)st->lv.size();
+    for (size_t l = 0; l < st->lv.size(); ++l)
+    {
+        if (rows) rows[l] = st->lv[l].n;
+        if (nnz) nnz[l] = st->lv[l].nnz;
+    }
+    return SPMV_OK;
+}
+
+int amg_level_download(spmv_ctx* ctx, const spmv_mat* m, int level, int32_t* agg_host, int32_t* row_ptr, int32_t* col, double* val)
+{
+    const char* const who = "spmv_amg_level";
+    const amg_state*  st  = m->amg;
+    if (!st) SPMV_FAIL(SPMV_ERR_INVALID, "%s: the handle was not set up (spmv_amg_setup)", who);
+    SPMV_REQUIRE(level >= 0 && level < (int)st->lv.size(), "%s: level=%d, the hierarchy has %d", who, level, (int)st->lv.size());
+    const amg_level& L = st->lv[(size_t)level];
+    SPMV_REQUIRE(!agg_host || L.agg, "%s: level %d is the coarsest: it has no aggregates", who, level);
+    hipStream_t s = ctx->stream;
+    hipError_t  e = hipSuccess;
+    if (agg_host && L.n) e = hipMemcpyAsync(agg_host, L.agg, sizeof(int32_t) * (size_t)L.n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && row_ptr) e = hipMemcpyAsync(row_ptr, L.A->a, sizeof(int32_t) * ((size_t)L.n + 1), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && col && L.nnz) e = hipMemcpyAsync(col, L.A->b, sizeof(int32_t) * (size_t)L.nnz, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && val && L.nnz) e = hipMemcpyAsync(val, L.A->v, sizeof(double) * (size_t)L.nnz, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return hip_step(e, who, "downloading the level");
+}
+
+static int64_t amg_launches(const amg_state* st, const spmv_mat* m)
+{
+    if (!st || m->nrow == 0) return 0;
+    int64_t total = 0;
+    const size_t nlev = st->lv.size();
+    for (size_t l = 0; l < nlev; ++l)
+    {
+        int64_t d = 0;
+        (void)cheby_get_param(st->lv[l].A, "cheby_degree", &d);  // (of the level's state as it stands)
+        total += l + 1 < nlev ? 4 * d + 7 : (st->inv ? 1 : 2 * d + 1);
+    }
+    return total;
+}
+
+bool amg_get_param(const spmv_mat* m, const char* name, int64_t* value)
+{
+    const amg_state* st = m->amg;
+    if (!strcmp(name, "amg_ready"))
+        *value = st ? 1 : 0;
+    else if (!strcmp(name, "amg_levels"))
+        *value = st ? (int64_t)st->lv.size() : 0;
+    else if (!strcmp(name, "amg_bytes"))
+        *value = st ? st->bytes : 0;
+    else if (!strcmp(name, "amg_launches"))  // per application
+        *value = amg_launches(st, m);
+    else if (!strcmp(name, "amg_mis_rounds"))  // the sum over the levels
+        *value = st ? st->mis_rounds : 0;
+    else if (!strcmp(name, "amg_level_kernel"))
+        *value = m->amg_level_kernel;
+    else
+        return false;
+    return true;
+}
+
+bool amg_set_param(spmv_mat* m, const char* name, int64_t value, int* rc)
+{
+    *rc = SPMV_OK;
+    if (strcmp(name, "amg_level_kernel")) return false;
+    if (value < SPMV_CSR_AUTO || value > SPMV_CSR_ELL)
+    {
+        set_error("%s: a CSR kernel id 1 .. 8 for every coarse handle of the next set-up, or 0 (AUTO), got %lld", name, (long long)value);
+        *rc = SPMV_ERR_INVALID;
+    }
+    else
+        m->amg_level_kernel = (int32_t)value;
+    return true;
+}
+
+// ---- the application: z = B r, one V(1,1) cycle; asynchronous ---------------------------------------------------------------------
+int amg_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z)
+{
+    const char* const who = "spmv_amg_solve";
+    const amg_state*  st  = A->amg;
+    if (!st) SPMV_FAIL(SPMV_ERR_INVALID, "%s: the handle was not set up (spmv_amg_setup)", who);
+    if (A->nrow == 0) return SPMV_OK;
+    hipStream_t  s    = ctx->stream;
+    const size_t nlev = st->lv.size();
+    apply_extra  over;
+    over.overwrite = true;
+    for (size_t l = 0; l < nlev; ++l)
+    {
+        const amg_level& L = st->lv[l];
+        const double*    b = l == 0 ? r : L.b;
+        double*          x = l == 0 ? z : L.x;
+        if (l + 1 == nlev)
+        {
+            if (st->inv)
+                hipLaunchKernelGGL(amg_dense_apply_kernel, dim3((unsigned)ceil_div(L.n, kBlock / kWave)), dim3(kBlock), 0, s, (int)L.n,
+                                   (const double*)st->inv, b, x);
+            else
+                SPMV_TRY(cheby_apply(ctx, L.A, b, x));
+            break;
+        }
+        SPMV_TRY(cheby_apply(ctx, L.A, b, x));
+        SPMV_TRY(mat_apply_ex(ctx, L.A, x, L.w, over));
+        hipLaunchKernelGGL(amg_restrict_kernel, dim3(stream_grid(L.nc)), dim3(kBlock), 0, s, L.nc, (const int32_t*)L.agg_ptr, (const int32_t*)L.agg_rows,
+                           b, (const double*)L.w, st->lv[l + 1].b);
+    }
+    for (size_t l = nlev - 1; l-- > 0;)
+    {
+        const amg_level& L = st->lv[l];
+        const double*    b = l == 0 ? r : L.b;
+        double*          x = l == 0 ? z : L.x;
+        if (wide_ok(x, L.n))
+            hipLaunchKernelGGL(amg_prolong_add_kernel<true>, dim3(pair_grid(L.n)), dim3(kBlock), 0, s, L.n, st->omega, (const int32_t*)L.agg,
+                               (const double*)st->lv[l + 1].x, x);
+        else
+            hipLaunchKernelGGL(amg_prolong_add_kernel<false>, dim3(stream_grid(L.n)), dim3(kBlock), 0, s, L.n, st->omega, (const int32_t*)L.agg,
+                               (const double*)st->lv[l + 1].x, x);
+        SPMV_TRY(cheby_smooth(ctx, L.A, b, x));
+    }
+    return hip_step(hipGetLastError(), who, "a launch of the cycle");
+}
+}  // namespace spmv

@@ -143,6 +143,7 @@ namespace spmv
 struct symgs_plan;
 struct ilu0_plan;
 struct cheby_state;
+struct amg_state;
 struct transpose_state;
 // ---- plans (plan.hip): the decisions a handle's set-up made - by model or by timing - as plain data ------------------------------
 // One node per handle, children by index (the row-grouped copy of a COO / CSC / ELL handle or the short-row copy of a split,
@@ -370,6 +371,12 @@ struct spmv_mat
     int32_t                   cheby_degree        = 4;   // "cheby_degree": what a solver's own set-up takes
     int32_t                   cheby_ratio         = 30;  // "cheby_ratio": lmin = lmax / ratio where lmin is estimated
     int32_t                   cheby_lanczos_steps = 0;   // "cheby_lanczos_steps": > 0: 1.05 ritz_max of that many steps competes with the row bound
+
+    // aggregation AMG (amg.hip): aggregates, member lists, the coarse handles with their smoothers, the coarsest inverse and the levels'
+    // vectors; built by spmv_amg_setup (or by the first solve with SPMV_PRECOND_AMG), no part of the forward state, of plans, of trials,
+    // of copies or of the transposed state
+    struct spmv::amg_state* amg              = nullptr;
+    int32_t                 amg_level_kernel = 0;  // "amg_level_kernel": != 0 forces that CSR kernel id on every coarse handle of the next set-up
 };
 
 namespace spmv
@@ -466,7 +473,7 @@ bool adds_into_y_with_atomics(const spmv_mat* A);       // global_atomic_add_f64
 // The five solves' drivers.  Each is entered from its ABI entry (abi.hip) behind the argument checks and use_device, zeroes its
 // outputs, returns at an empty system, and shares its host side - the workspace that owns its device memory, the preconditioner's
 // set-up and application, the looks at its scalars - with the others through solver_host.hpp.
-// solver.hip: conjugate gradients for a symmetric positive definite A (precond: NONE, JACOBI, SYMGS, ILU0, CHEBYSHEV)
+// solver.hip: conjugate gradients for a symmetric positive definite A (precond: NONE, JACOBI, SYMGS, ILU0, CHEBYSHEV, AMG)
 int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
              int precond, int* iters, double* rel_resid);
 int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t n, double* device_out);
@@ -476,11 +483,11 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
 // solver_cgls.hip: CGLS for min ||b - A x||^2 + damp^2 ||x||^2 over the forward and the transposed product of any handle
 int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                double damp, int* iters, double* rel_normal_resid, double* rel_resid);
-// solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle (precond: NONE, JACOBI, ILU0, CHEBYSHEV)
+// solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle (precond: NONE, JACOBI, ILU0, CHEBYSHEV, AMG)
 int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                    int precond, int* iters, double* rel_resid);
 // solver_gmres.hip: right-preconditioned restarted GMRES(restart) for square A over one forward product of any handle per iteration
-// (restart: 1 .. 64; precond: NONE, JACOBI, ILU0, CHEBYSHEV)
+// (restart: 1 .. 64; precond: NONE, JACOBI, ILU0, CHEBYSHEV, AMG)
 int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int restart, int max_iter, double rel_tol, int check_every,
                 int precond, int* iters, double* rel_resid);
 // kernels_ell.hip (what a product launches: ell_settings.hpp)
@@ -561,6 +568,16 @@ int  cheby_lanczos(spmv_ctx* ctx, const spmv_mat* A, int scaled, int steps, uint
                    double* beta, int32_t* steps_done);  // synchronous; alpha, beta: host arrays of `steps` entries or null
 bool cheby_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "cheby_*"; false: not one of them
 bool cheby_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "cheby_*"; false: not one of them
+// amg.hip: aggregation AMG, one V(1,1) cycle z = B r (SPMV_PRECOND_AMG)
+int  amg_check_handle(const spmv_mat* m, const char* who);  // on the host: UNSUPPORTED (not CSR) / INVALID (a shard, not square, arrays released)
+int  amg_check_setup(const spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection, const char* who);
+int  amg_setup(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection);  // synchronous; 0: the default
+void amg_free(spmv_mat* m);
+int  amg_info(const spmv_mat* m, int32_t* levels, int64_t* rows, int64_t* nnz);
+int  amg_level_download(spmv_ctx* ctx, const spmv_mat* m, int level, int32_t* agg_host, int32_t* row_ptr, int32_t* col, double* val);
+int  amg_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z);  // z = B r, asynchronous; r and z must not overlap
+bool amg_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "amg_*"; false: not one of them
+bool amg_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "amg_level_kernel"; false: not that
 // convert_sort.hip
 int sort_ids_by_key(spmv_ctx* ctx, const int32_t* keys, int64_t n, int bits, int32_t* out_ids);
 int coo_place_by_stable_sort(spmv_ctx* ctx, int64_t nnz, int32_t nrow, const int32_t* row, const int32_t* col, const double* val,

@@ -59,7 +59,7 @@ int check_limits(const char* who, int max_iter, double rel_tol)
 int check_known_preconditioner(const char* who, int precond)
 {
     SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0 ||
-                     precond == SPMV_PRECOND_CHEBYSHEV,
+                     precond == SPMV_PRECOND_CHEBYSHEV || precond == SPMV_PRECOND_AMG,
                  "%s: unknown preconditioner %d", who, precond);
     return SPMV_OK;
 }
@@ -92,6 +92,11 @@ int check_preconditioner(const solver_rules& S, const spmv_mat* A, int precond)
     {
         if (S.cheby_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the Chebyshev preconditioner is not built for %s", S.who, S.cheby_not_built_for);
         return cheby_check_handle(A, S.who);  // (whether the handle is set up, and what its own set-up needs, is looked at on the device's side)
+    }
+    if (precond == SPMV_PRECOND_AMG)
+    {
+        if (S.amg_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the AMG preconditioner is not built for %s", S.who, S.amg_not_built_for);
+        return amg_check_handle(A, S.who);
     }
     if (precond != SPMV_PRECOND_JACOBI) return SPMV_OK;
     // Jacobi reads the diagonal from the handle's own CSR arrays (the plain solve needs the product alone and takes a handle that
@@ -168,6 +173,8 @@ int setup_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, double* 
         case SPMV_PRECOND_ILU0: return ilu0_setup(const_cast<spmv_mat*>(A));
         case SPMV_PRECOND_CHEBYSHEV:  // a handle that was set up explicitly is used as it stands
             return A->cheby ? SPMV_OK : cheby_setup(ctx, const_cast<spmv_mat*>(A), A->cheby_degree, /*scaled=*/1, 0.0, 0.0);
+        case SPMV_PRECOND_AMG:  // likewise; 0: every default
+            return A->amg ? SPMV_OK : amg_setup(ctx, const_cast<spmv_mat*>(A), 0, 0, 0, 0.0, 0.0);
         default: return SPMV_OK;
     }
 }
@@ -178,6 +185,7 @@ int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const do
     {
         case SPMV_PRECOND_ILU0: return ilu0_apply(ctx, A, r, z);
         case SPMV_PRECOND_CHEBYSHEV: return cheby_apply(ctx, A, r, z);
+        case SPMV_PRECOND_AMG: return amg_apply(ctx, A, r, z);
         default: return symgs_sweep(ctx, A, r, z, true);
     }
 }

@@ -345,6 +345,7 @@ int spmv_mat_set_flags(spmv_mat* m, uint32_t flags);
  *   "ilu0_order"     sweep order of the ILU(0) factorisation (spmv_ilu0_setup / SPMV_PRECOND_ILU0), with the same meaning and default
  *   "cheby_degree"   degree a solver's own set-up of SPMV_PRECOND_CHEBYSHEV takes (1 .. 64, default 4); "cheby_ratio": lmax / lmin where
  *                    lmin is estimated (2 .. 10^6, default 30); "cheby_lanczos_steps": 0 (default) .. 64, see spmv_chebyshev_setup
+ *   "amg_level_kernel"   a CSR kernel id (1 .. 8) that the next spmv_amg_setup forces on every coarse handle; 0 (default): each selects
  *   "panel_two_per_cu"   0 = never two workgroups per CU (default 1: two when their accumulators fit the LDS twice) */
 int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
 /* What is in effect: "panel_rows", "panel_width", "panel_sort", "panel_groups", "panel_layout", "panel_unroll",
@@ -363,7 +364,8 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
  * handle were found to be diagonals and conforming rows read no column index), "symgs_order", "symgs_colours",
  * "symgs_levels_forward", "symgs_levels_backward", "symgs_launches", "symgs_bytes", "symgs_fused" (1: the colouring is proper and
  * the sweep takes one launch per colour), "ilu0_order", "ilu0_ready", "ilu0_colours", "ilu0_levels_forward", "ilu0_levels_backward",
- * "ilu0_launches" (per application), "ilu0_bytes", and the "cheby_*" names listed at spmv_chebyshev_setup. */
+ * "ilu0_launches" (per application), "ilu0_bytes", the "cheby_*" names listed at spmv_chebyshev_setup and the "amg_*" names listed
+ * at spmv_amg_setup. */
 int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value);
 /* ---- plans: a handle's set-up decisions as plain data (plan.hip) ------------------------------------------------------------
  * AUTO is a measurement (spmv_mat_set_kernel above): which kernel a handle runs, in which layout, with which chunk size,
@@ -500,11 +502,15 @@ enum spmv_precond
                                 set up on first use although it is passed as const) */
     SPMV_PRECOND_ILU0   = 3, /* z = U^-1 L^-1 r with the ILU(0) factors of a CSR handle (spmv_ilu0_setup below; set up on first use
                                 in the same way).  spmv_cg, spmv_bicgstab and spmv_gmres; spmv_cg_multi: SPMV_ERR_UNSUPPORTED */
-    SPMV_PRECOND_CHEBYSHEV = 4 /* z = p_d(diag(s) A) diag(s) r, a fixed Chebyshev polynomial applied through the handle's own forward
+    SPMV_PRECOND_CHEBYSHEV = 4, /* z = p_d(diag(s) A) diag(s) r, a fixed Chebyshev polynomial applied through the handle's own forward
                                 product (spmv_chebyshev_setup below).  A handle that was set up is used as it stands, any format; one
                                 that was not is set up on first use with degree "cheby_degree" (4), Jacobi scaling and estimated
                                 bounds, which needs a CSR handle with its arrays.  spmv_cg, spmv_bicgstab and spmv_gmres, with the
                                 work vectors and arrangement of SPMV_PRECOND_ILU0; spmv_cg_multi: SPMV_ERR_UNSUPPORTED */
+    SPMV_PRECOND_AMG = 5 /* z = B r, one V(1,1) cycle of aggregation AMG on a CSR handle (spmv_amg_setup below).  A handle that was set up
+                            is used as it stands; one that was not is set up on first use with every default.  spmv_cg, spmv_bicgstab
+                            and spmv_gmres, with the work vectors and arrangement of SPMV_PRECOND_ILU0; spmv_cg_multi:
+                            SPMV_ERR_UNSUPPORTED */
 };
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter,
             double rel_tol, int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
@@ -736,6 +742,46 @@ int spmv_chebyshev_setup(spmv_ctx* ctx, spmv_mat* A, int32_t degree, int32_t sca
 int spmv_chebyshev_info(const spmv_mat* A, int32_t* degree, int32_t* scaled, double* lmin, double* lmax);
 int spmv_chebyshev_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z);
 int spmv_chebyshev(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x);
+
+/* ---- aggregation algebraic multigrid (amg.hip) -----------------------------------------------------------------------
+ * spmv_amg_setup builds a hierarchy on the device from a CSR handle (square, the whole matrix, arrays kept: the rules of
+ *   spmv_ilu0_setup, checked on the host before any device use) and spmv_amg_solve applies one V(1,1) cycle z = B r.  Synchronous;
+ *   replaces earlier state; a failed set-up leaves the earlier state.  An argument of 0 takes its default:
+ *     max_levels 1 .. 32 (16);  coarse_max 1 .. 1024 (256);  smooth_degree 1 .. 64 (2);  strength theta, <= 0 (default): every stored
+ *     off-diagonal entry is a neighbour, > 0: j is a neighbour of i iff a_ij^2 >= theta^2 |a_ii a_jj|;  overcorrection omega inside
+ *     (0, 2) (1.5).  Anything else: SPMV_ERR_INVALID.
+ *   The method.  Level 0 is the handle's arrays.  Every row needs a stored non-zero diagonal entry (duplicates summed), else
+ *   SPMV_ERR_INVALID.  Rows are aggregated by a maximal independent set of distance 2 over the rows' own neighbour lists (nothing is
+ *   symmetrised): the priority of row i is the pair (h(i), i) compared as unsigned numbers, h the 32-bit finaliser h ^= h >> 16;
+ *   h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16 of i; in a round every undecided row whose priority is the largest
+ *   among the undecided rows within two steps becomes a root and the undecided rows within two steps of a root are removed, until no
+ *   row is undecided.  Roots take ids in ascending row order; a row with roots among its neighbours joins the one of smallest id;
+ *   every other row joins the smallest id among its neighbours as that pass left them.  The coarse operator is
+ *   A_c[I, J] = sum of a_ij over all stored entries with agg(i) = I, agg(j) = J, added from 0.0 in ascending (I, J, entry) order: the
+ *   result does not depend on the order of the launches.  Level l is the coarsest when n_l <= coarse_max, l + 1 == max_levels, or the
+ *   next level would hold more than 0.8 n_l rows.  Every level is smoothed by the Chebyshev polynomial of spmv_chebyshev_setup(degree =
+ *   smooth_degree, scaled, estimated bounds: the row bound, ratio 30); level 0's is the HANDLE'S OWN Chebyshev state, which
+ *   spmv_amg_setup replaces as spmv_chebyshev_setup would.  A coarsest level of at most 1024 rows is inverted densely on the host (LU
+ *   with partial pivoting in double; a pivot below 2^-44 of the largest entry: SPMV_ERR_INVALID, "singular coarsest operator") and
+ *   applied by one launch; a larger one takes one Chebyshev application.  The cycle on level l with right-hand side b_l:
+ *     x_l = M_l^-1 b_l;  b_{l+1}[I] = sum over i in I, ascending, of (b_l - A_l x_l)[i];  x_{l+1} = cycle(l + 1);
+ *     x_l[i] += omega x_{l+1}[agg(i)];  x_l += M_l^-1 (b_l - A_l x_l)
+ *   B is symmetric positive definite for a symmetric positive definite A and 0 < omega < 2, so spmv_cg may use it.  r is never
+ *   written; r and z must not overlap; asynchronous, nothing is allocated or read back; results are deterministic.
+ * spmv_amg_info: the number of levels and, where the pointers are not NULL, rows and entries per level (arrays of at least 32).
+ * spmv_amg_level: to the host, the aggregate of every row of `level` (NULL, or an array of rows[level]; the coarsest level has none:
+ *   SPMV_ERR_INVALID) and the operator of `level` as CSR (NULLs, or arrays of rows + 1, entries, entries).
+ * spmv_amg_solve, spmv_amg_level and spmv_amg_info on a handle that was not set up: SPMV_ERR_INVALID.
+ * spmv_mat_get_param: "amg_ready", "amg_levels", "amg_bytes" (counted in device_bytes), "amg_launches" (per application: 4 d + 7 a
+ *   level and 1 or 2 d + 1 at the coarsest), "amg_mis_rounds" (summed over the levels).  spmv_mat_set_param "amg_level_kernel": a CSR
+ *   kernel id forced on every coarse handle of the next set-up (0, the default: each selects its own).  The state is freed with the
+ *   handle and is no part of plans, trials, copies or the transposed state. */
+int spmv_amg_setup(spmv_ctx* ctx, spmv_mat* A, int32_t max_levels, int32_t coarse_max, int32_t smooth_degree, double strength,
+                   double overcorrection);
+int spmv_amg_info(const spmv_mat* A, int32_t* levels, int64_t* rows /* levels, or NULL */, int64_t* nnz /* levels, or NULL */);
+int spmv_amg_level(spmv_ctx* ctx, const spmv_mat* A, int32_t level, int32_t* agg_host /* rows[level], or NULL */, int32_t* row_ptr,
+                   int32_t* col, double* val /* the operator of `level`, or NULLs */);
+int spmv_amg_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z);
 
 /* ---- format conversion on the device (src/matrix.cpp:115-154, :450-500) -------------------------- */
 /* Both keep the COO order of the entries inside each row (stable), like the reference's backward
