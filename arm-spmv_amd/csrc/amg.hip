@@ -23,7 +23,8 @@
 // stably by (I, J) (two passes of sort_ids_by_key, J first), runs of equal keys are marked and counted by a scan, and one lane
 // per coarse entry adds its run from 0.0 left to right in that order - plain additions, so the sum is defined.  The result is
 // CSR with ascending columns, in a handle of its own that goes through the engine's kernel selection ("amg_level_kernel" != 0
-// forces that kernel id on every coarse handle).  Beside agg every level keeps the member lists agg_ptr / agg_rows (rows
+// forces that kernel id on every coarse handle; an id that a coarse operator cannot run - the LDS-window kernel where a block's
+// window is wider than its tile - fails the set-up with SPMV_ERR_UNSUPPORTED, naming the level).  Beside agg every level keeps the member lists agg_ptr / agg_rows (rows
 // ascending within an aggregate: one more stable sort).
 //
 // Smoother.  Every level holds the Chebyshev state of chebyshev.hip with degree smooth_degree, Jacobi scaling, lmax the row
@@ -40,7 +41,12 @@
 //   x_l[i] += omega x_{l+1}[agg(i)]               amg_prolong_add_kernel
 //   x_l += M_l^-1 (b_l - A_l x_l)                 cheby_smooth
 // 4 d + 7 launches a level (d = smooth_degree) and 1 (dense) or 2 d + 1 (Chebyshev) at the coarsest: "amg_launches".  The state
-// owns b_l, x_l (l >= 1) and w_l; an application allocates nothing and reads nothing back.  Every sum has a fixed order.
+// owns b_l, x_l (l >= 1) and w_l; an application allocates nothing and reads nothing back.  Every sum of this
+// file has a fixed order; the products A_l x are as reproducible as the kernel each level runs (include/spmv_abi.h, "Order of the
+// additions"): the six ids that store every y_i once - VECTOR, LDSWIN, SCALAR, ELL (a fixed order per row), PANEL and TWOPHASE (row
+// sums in LDS, which the tests see return equal bits on their small hierarchies) - give equal bits from call to call on a level 0
+// that runs one of them; no such promise under SEGSCAN and SPLIT (atomic adds on y in arrival order) nor under AUTO, where every
+// coarse handle selects for itself - from 64K entries on by a timed trial that may choose any of the eight.
 #include <cmath>
 #include <memory>
 
@@ -521,7 +527,9 @@ int member_lists(spmv_ctx* ctx, amg_level& L, const int32_t* count)
 }
 
 // A_c = P^T A P over every stored entry, as a CSR handle of its own
-int coarse_operator(spmv_ctx* ctx, const spmv_mat* A, const int32_t* agg, int64_t nc, int32_t level_kernel, spmv_mat** out)
+// (`level`: the level the operator becomes, for messages).  A forced kernel id whose product cannot launch on this operator is
+// refused here, once, and not by every product of every cycle; no other kernel takes its place.
+int coarse_operator(spmv_ctx* ctx, const spmv_mat* A, const int32_t* agg, int64_t nc, int32_t level_kernel, int level, spmv_mat** out)
 {
     const char* const who = "spmv_amg_setup";
     const int64_t     n = A->nrow, nnz = A->nnz;
@@ -573,6 +581,13 @@ int coarse_operator(spmv_ctx* ctx, const spmv_mat* A, const int32_t* agg, int64_
             C->kernel        = level_kernel;
         }
         rc = csr_analyse(C);  // the engine's usual selection: the model and, where it pays, a trial
+        if (rc == SPMV_OK && C->kernel_forced && C->kernel == SPMV_CSR_LDSWIN && !csr_ldswin_fits(C))
+        {
+            set_error("%s: amg_level_kernel=%d (the LDS-window kernel) cannot run the operator of level %d (%lld rows): its widest block window "
+                      "is %d columns, the tile holds %d",
+                      who, level_kernel, level, (long long)nc, C->win_max_span, csr_ldswin_capacity());
+            rc = SPMV_ERR_UNSUPPORTED;
+        }
     }
     if (rc != SPMV_OK)
     {
@@ -736,7 +751,7 @@ int amg_setup(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int sm
                 st->bytes += (int64_t)sizeof(int32_t) * (2 * n + nc + 1);
             }
             spmv_mat* C = nullptr;
-            SPMV_TRY(coarse_operator(ctx, st->lv[(size_t)l].A, agg, nc, m->amg_level_kernel, &C));
+            SPMV_TRY(coarse_operator(ctx, st->lv[(size_t)l].A, agg, nc, m->amg_level_kernel, l + 1, &C));
             st->lv.emplace_back();
             amg_level& N = st->lv.back();
             N.A          = C;

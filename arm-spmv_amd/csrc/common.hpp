@@ -398,6 +398,7 @@ bool csr_layout_built(const spmv_mat* m, int32_t kernel);  // kernel_reads_own_l
 constexpr uint32_t kCsrAllLayouts = ~0u;
 void csr_choose_kernel(spmv_mat* m);  // the model's pick (no launches)
 int  csr_ldswin_capacity();           // columns of x the LDS-window kernel's tile holds
+bool csr_ldswin_fits(const spmv_mat* m);  // the widest block window of an analysed handle is known and the tile holds it: LDSWIN can launch
 // select.hip: AUTO by measurement
 bool select_trials_enabled(const spmv_mat* m);
 // ms per launch of n launches between the context's two events (ev_begin / ev_end); a launch that fails ends it with that code

@@ -365,7 +365,7 @@ void csr_choose_kernel(spmv_mat* m)
 {
     const double mean       = m->nrow > 0 ? (double)m->nnz / (double)m->nrow : 0.0;
     const bool   big_enough = m->nnz >= (int64_t)3 << 19 && mean >= 0.5;
-    const bool   fits       = m->win_max_span > 0 && m->win_max_span <= kWinDoubles;
+    const bool   fits       = csr_ldswin_fits(m);
     const double reuse      = m->win_max_span > 0 ? mean * kWinRows / (double)m->win_max_span : 0.0;
     const bool   dense_runs = m->contig_frac >= 0.8 && mean >= 24.0;
     const bool   hub_rows   = m->nnz >= (int64_t)64 << 10 && m->max_row_nnz >= 1024 && (double)m->max_row_nnz >= 32.0 * std::max(mean, 1.0);
@@ -385,6 +385,10 @@ void csr_choose_kernel(spmv_mat* m)
 }
 
 int csr_ldswin_capacity() { return kWinDoubles; }
+
+// Can the LDS-window kernel launch on this handle?  What csr_apply refuses at every product, and what a caller that forces the
+// kernel on a handle of its own (amg.hip: "amg_level_kernel") asks once, at its set-up.
+bool csr_ldswin_fits(const spmv_mat* m) { return m->win_max_span > 0 && m->win_max_span <= kWinDoubles; }
 
 // Row statistics + kernel choice.  Runs once when a CSR handle is created.
 int csr_analyse(spmv_mat* m)
@@ -545,7 +549,7 @@ int csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, cons
             SPMV_HIP(hipGetLastError());
             return SPMV_OK;
         case SPMV_CSR_LDSWIN:
-            if (A->win_max_span <= 0 || A->win_max_span > kWinDoubles)
+            if (!csr_ldswin_fits(A))
                 SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "LDS-window kernel: widest block window is %d columns, tile holds %d",
                           A->win_max_span, kWinDoubles);
             return launch_ldswin(ctx, A, x, y, lanes);

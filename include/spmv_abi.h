@@ -345,7 +345,9 @@ int spmv_mat_set_flags(spmv_mat* m, uint32_t flags);
  *   "ilu0_order"     sweep order of the ILU(0) factorisation (spmv_ilu0_setup / SPMV_PRECOND_ILU0), with the same meaning and default
  *   "cheby_degree"   degree a solver's own set-up of SPMV_PRECOND_CHEBYSHEV takes (1 .. 64, default 4); "cheby_ratio": lmax / lmin where
  *                    lmin is estimated (2 .. 10^6, default 30); "cheby_lanczos_steps": 0 (default) .. 64, see spmv_chebyshev_setup
- *   "amg_level_kernel"   a CSR kernel id (1 .. 8) that the next spmv_amg_setup forces on every coarse handle; 0 (default): each selects
+ *   "amg_level_kernel"   a CSR kernel id (1 .. 8) that the next spmv_amg_setup forces on every coarse handle; 0 (default): each selects.
+ *                    An id that a coarse operator cannot run (LDSWIN: a block window wider than the tile) fails that set-up
+ *                    (SPMV_ERR_UNSUPPORTED); no other kernel takes its place
  *   "panel_two_per_cu"   0 = never two workgroups per CU (default 1: two when their accumulators fit the LDS twice) */
 int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
 /* What is in effect: "panel_rows", "panel_width", "panel_sort", "panel_groups", "panel_layout", "panel_unroll",
@@ -774,8 +776,15 @@ int spmv_chebyshev(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x);
  * spmv_amg_solve, spmv_amg_level and spmv_amg_info on a handle that was not set up: SPMV_ERR_INVALID.
  * spmv_mat_get_param: "amg_ready", "amg_levels", "amg_bytes" (counted in device_bytes), "amg_launches" (per application: 4 d + 7 a
  *   level and 1 or 2 d + 1 at the coarsest), "amg_mis_rounds" (summed over the levels).  spmv_mat_set_param "amg_level_kernel": a CSR
- *   kernel id forced on every coarse handle of the next set-up (0, the default: each selects its own).  The state is freed with the
- *   handle and is no part of plans, trials, copies or the transposed state. */
+ *   kernel id forced on every coarse handle of the next set-up (0, the default: each selects its own).  A forced id that a coarse
+ *   operator cannot run - the LDS-window kernel where a block of 256 rows spans more columns than its tile holds - fails the set-up
+ *   with SPMV_ERR_UNSUPPORTED (the message names the level, the id, the window and the capacity), leaving the earlier state.  The
+ *   hierarchy's bits do not depend on the id.  The application is bit-reproducible from call to call and from set-up to set-up under
+ *   the six ids whose kernels store every y_i once (VECTOR, LDSWIN, SCALAR, PANEL, TWOPHASE, ELL; PANEL and TWOPHASE within what "Order
+ *   of the additions" above says of their LDS sums) where level 0 runs one of them too; it is not promised to be under SEGSCAN and
+ *   SPLIT (atomic adds on y in arrival order), nor under 0: every coarse handle then selects as any handle does, from 64K entries on
+ *   by a timed trial that may pick any of the eight.  The state is freed with the handle and is no part of plans, trials, copies or
+ *   the transposed state. */
 int spmv_amg_setup(spmv_ctx* ctx, spmv_mat* A, int32_t max_levels, int32_t coarse_max, int32_t smooth_degree, double strength,
                    double overcorrection);
 int spmv_amg_info(const spmv_mat* A, int32_t* levels, int64_t* rows /* levels, or NULL */, int64_t* nnz /* levels, or NULL */);

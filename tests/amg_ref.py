@@ -1,5 +1,6 @@
 """NumPy twin of aggregation AMG (csrc/amg.hip; SPMV_PRECOND_AMG): the definition that include/spmv_abi.h states, restated number
-for number.  tests/test_amg_ref.py holds it to facts of its own on the CPU; tests/test_gpu_amg.py holds the engine to it.
+for number.  tests/test_amg_ref.py holds it to facts of its own on the CPU; tests/test_gpu_amg.py and
+tests/test_gpu_amg_edges.py hold the engine to it.
 
 Level 0 is the matrix; level l + 1 is built from level l until level l is the coarsest: n_l <= coarse_max, l + 1 == max_levels, or
 5 n_c > 4 n_l (stalled).
@@ -29,7 +30,7 @@ import solver_ref as sr
 DEFAULTS = dict(max_levels=16, coarse_max=256, smooth_degree=2, strength=0.0, overcorrection=1.5)
 DENSE_MAX = 1024
 SINGULAR = 2.0**-44
-MUTATIONS = ("tie", "strong_sum", "post_degree")
+MUTATIONS = ("tie", "strong_sum", "post_degree", "restrict_drop", "prolong_tail")
 _U32 = np.uint32
 _U64 = np.uint64
 
@@ -178,24 +179,33 @@ class Level:
         self.degree = degree
         self._rows = np.repeat(np.arange(n), np.diff(self.rp))
         self._cheby = None
+        self.smoother = None  # (scaled, lmin, lmax) in place of the default set-up: what a later spmv_chebyshev_setup left on the handle
 
     def mv(self, x):
         return np.bincount(self._rows, weights=self.cv * x[self.cc], minlength=self.n)
 
     def cheby(self, degree=None):
-        """(s, c0, c1, c2) of the default set-up"""
+        """(s, c0, c1, c2) of the default set-up, or of `smoother` (s None: unscaled)"""
         degree = degree or self.degree
         if self._cheby is None or self._cheby[0] != degree:
-            s = cr.inverse_diagonal(self.n, self.rp, self.cc, self.cv)
-            lmax = cr.row_bound(self.n, self.rp, self.cc, self.cv, s)
-            self._cheby = (degree, s) + cr.coefficients(degree, lmax / 30.0, lmax)
+            if self.smoother is None:
+                s = cr.inverse_diagonal(self.n, self.rp, self.cc, self.cv)
+                lmax = cr.row_bound(self.n, self.rp, self.cc, self.cv, s)
+                lmin = lmax / 30.0
+            else:
+                scaled, lmin, lmax = self.smoother
+                s = cr.inverse_diagonal(self.n, self.rp, self.cc, self.cv) if scaled else None
+            self._cheby = (degree, s) + cr.coefficients(degree, lmin, lmax)
         return self._cheby[1:]
 
 
 class Hierarchy:
-    """the twin of spmv_amg_setup; 0 or None for an argument: its default"""
+    """the twin of spmv_amg_setup; 0 or None for an argument: its default.  level0_smoother = (degree, scaled, lmin, lmax): level 0
+    smooths with that polynomial instead (the handle's own Chebyshev state after a later spmv_chebyshev_setup: the cycle reads it
+    as it stands; the hierarchy and the coarse levels' smoothers are what the set-up built)"""
 
-    def __init__(self, n, rp, cc, cv, max_levels=0, coarse_max=0, smooth_degree=0, strength=0.0, overcorrection=0.0, mutate=None):
+    def __init__(self, n, rp, cc, cv, max_levels=0, coarse_max=0, smooth_degree=0, strength=0.0, overcorrection=0.0, mutate=None,
+                 level0_smoother=None):
         self.max_levels = max_levels or DEFAULTS["max_levels"]
         self.coarse_max = coarse_max or DEFAULTS["coarse_max"]
         self.degree = smooth_degree or DEFAULTS["smooth_degree"]
@@ -223,6 +233,9 @@ class Hierarchy:
         last = self.levels[-1]
         if last.n <= DENSE_MAX:
             self.inv = dense_inverse(last.n, last.rp, last.cc, last.cv)
+        if level0_smoother is not None:
+            self.levels[0].degree = int(level0_smoother[0])
+            self.levels[0].smoother = (bool(level0_smoother[1]), float(level0_smoother[2]), float(level0_smoother[3]))
 
     @property
     def rows(self):
@@ -235,8 +248,8 @@ class Hierarchy:
     def launches(self):
         if self.levels[0].n == 0:
             return 0
-        d = self.degree
-        return (len(self.levels) - 1) * (4 * d + 7) + (1 if self.inv is not None else 2 * d + 1)
+        degrees = [L.degree for L in self.levels]  # (level 0's may have been replaced: level0_smoother)
+        return sum(4 * d + 7 for d in degrees[:-1]) + (1 if self.inv is not None else 2 * degrees[-1] + 1)
 
     def apply(self, r, level=0):
         """z = B r"""
@@ -251,11 +264,18 @@ class Hierarchy:
         s, c0, c1, c2 = L.cheby()
         x = cr.apply(L.mv, s, r, c0, c1, c2)
         bc = np.zeros(L.nc)
-        np.add.at(bc, L.agg, r - L.mv(x))  # in ascending row order from 0.0
+        residual = r - L.mv(x)
+        if self.mutate == "restrict_drop":  # the mutation: the last member of every aggregate of two and more is left out
+            last = np.zeros(L.nc, dtype=np.int64)
+            np.maximum.at(last, L.agg, np.arange(L.n))
+            residual[last[np.bincount(L.agg, minlength=L.nc) > 1]] = 0.0
+        np.add.at(bc, L.agg, residual)  # in ascending row order from 0.0
         xc = self.apply(bc, level + 1)
         x = x + self.omega * xc[L.agg]
+        if self.mutate == "prolong_tail":  # the mutation: the last row's correction is added twice
+            x[-1] += self.omega * xc[L.agg[-1]]
         if self.mutate == "post_degree":  # the mutation: another polynomial behind the correction
-            s, c0, c1, c2 = L.cheby(self.degree + 1)
+            s, c0, c1, c2 = L.cheby(L.degree + 1)
         return cr.smooth(L.mv, s, r, x, c0, c1, c2)
 
     def dense_operator(self):
@@ -313,6 +333,114 @@ def random_nonsymmetric(n, k=4, seed=11):
         col.append(cols)
         val.append(vals)
     return (n,) + sr.csr_arrays(n, np.concatenate(row), np.concatenate(col), np.concatenate(val))
+
+
+def periodic_tridiagonal(n):
+    """2.5 on the diagonal, -1 at (i, i +- 1 mod n), columns ascending: rows 0 and n - 1 reach across the whole matrix, and so does
+    the first or last row of some block of rows on every coarse level"""
+    i = np.arange(n)
+    row = np.concatenate([i, i, i])
+    col = np.concatenate([(i - 1) % n, i, (i + 1) % n])
+    val = np.concatenate([np.full(n, -1.0), np.full(n, 2.5), np.full(n, -1.0)])
+    o = np.lexsort((col, row))
+    return (n,) + sr.csr_arrays(n, row[o], col[o], val[o])
+
+
+FUZZ_SIZES = (1, 2, 3, 5, 17, 64, 65, 130, 300, 700)
+FUZZ_BASE = 7031  # (of the bases 7000 .. 7059 the one whose seeds 0 .. 23 draw all ten sizes and most often n > coarse_max)
+FUZZ_E = 10  # every stored value of fuzz_system is an integer multiple of 2^-FUZZ_E (exact.scaled(cv, FUZZ_E))
+
+
+def fuzz_system(seed):
+    """(n, rp, cc, cv): a strictly row-dominant matrix with a positive diagonal on a structurally nonsymmetric pattern, as untidy as
+    CSR allows.  0 .. 6 random off-diagonal columns a row, values exact.dyadic (at most 10 bits, exponents -10 .. 0); about 15 % of
+    those entries stored twice, as two dyadic parts, about 10 % stored as 0.0; the diagonal = the row's sum of stored |off-diagonal
+    values| + 1 + one more |dyadic| (all on the grid 2^-10), in half the rows split into two stored parts; the entries of a row in
+    random order.  Row dominance with a positive diagonal survives the coarse operator's sums: no coarse diagonal is zero, no
+    coarsest operator singular."""
+    import exact
+
+    rng = np.random.default_rng(FUZZ_BASE + seed)
+    n = int(FUZZ_SIZES[rng.integers(len(FUZZ_SIZES))])
+    grid = 2**FUZZ_E
+    row, col, val = [], [], []
+    for i in range(n):
+        k = int(min(rng.integers(0, 7), n - 1))
+        others = rng.choice(n - 1, size=k, replace=False) if k else np.zeros(0, dtype=np.int64)
+        others = others + (others >= i)  # (skips i)
+        cols, vals = [], []
+        for j in others:
+            kind = rng.random()
+            if kind < 0.10:
+                parts = [0.0]
+            else:
+                parts = list(exact.dyadic(rng, 2 if kind < 0.25 else 1, 10, 0, -FUZZ_E))
+            cols += [int(j)] * len(parts)
+            vals += parts
+        weight = int(sum(abs(v) for v in vals) * grid) + grid + int(abs(exact.dyadic(rng, 1, 10, 0, -FUZZ_E)[0]) * grid)
+        if rng.random() < 0.5:
+            first = int(rng.integers(1, weight))  # (weight >= 2^10 + 1)
+            parts = [first / grid, (weight - first) / grid]
+        else:
+            parts = [weight / grid]
+        cols += [i] * len(parts)
+        vals += parts
+        o = rng.permutation(len(cols))
+        row.append(np.full(len(cols), i))
+        col.append(np.asarray(cols, dtype=np.int64)[o])
+        val.append(np.asarray(vals, dtype=np.float64)[o])
+    return (n,) + sr.csr_arrays(n, np.concatenate(row), np.concatenate(col), np.concatenate(val))
+
+
+FUZZ_SEEDS = tuple(range(24))
+
+
+def fuzz_setup(seed):
+    """the set-up arguments that go with fuzz_system(seed): theta cycles through 0, 0.1, 0.5; coarse_max is drawn from 1, 8, 256"""
+    return dict(strength=(0.0, 0.1, 0.5)[seed % 3], coarse_max=int(np.random.default_rng(FUZZ_BASE + 100 + seed).choice((1, 8, 256))))
+
+
+def galerkin_int64(n, rp, cc, cv, agg, nc, e=FUZZ_E):
+    """P^T A P in int64 on the grid 2^-e, dense (nc x nc), and the pattern (which (I, J) hold a stored entry): arithmetic that
+    shares no ordering code with coarse_operator"""
+    import exact
+
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    dense = np.zeros((nc, nc), dtype=np.int64)
+    stored = np.zeros((nc, nc), dtype=bool)
+    I, J = np.asarray(agg)[rows], np.asarray(agg)[np.asarray(cc)]
+    np.add.at(dense, (I, J), exact.scaled(cv, e))
+    stored[I, J] = True
+    return dense, stored
+
+
+PERIODIC = 100000
+_DEGREE1 = dict(smooth_degree=1, overcorrection=1.0)
+# The applications tests/test_gpu_amg_edges.py compares with the twin, name: (builder, arguments of Hierarchy).
+# tests/test_amg_ref.py::test_every_mutation_moves_every_application holds each to the five mutations.
+EDGE_CASES = {
+    "arrow300": (lambda: arrow(300), dict(coarse_max=8)),
+    "nonsymmetric500": (lambda: random_nonsymmetric(500), dict(coarse_max=8)),
+    "anisotropic16x16": (lambda: anisotropic_2d(16), dict(coarse_max=8, strength=0.5)),
+    "anisotropic16x16_quarter": (lambda: anisotropic_2d(16), dict(coarse_max=8, strength=0.25)),
+    "tridiagonal257": (lambda: cr.tridiagonal(257), dict(coarse_max=1)),
+    "diagonal257": (lambda: cr.diagonal(np.linspace(1.0, 2.0, 257)), dict(coarse_max=1)),
+}
+IRREGULAR = tuple(EDGE_CASES)
+EDGE_CASES.update({name + "_degree1": (EDGE_CASES[name][0], dict(EDGE_CASES[name][1], **_DEGREE1)) for name in IRREGULAR})
+EDGE_CASES.update({f"fuzz{seed:02d}": ((lambda seed=seed: fuzz_system(seed)), fuzz_setup(seed)) for seed in FUZZ_SEEDS})
+EDGE_CASES.update({
+    "laplacian32x32": (lambda: cr.laplacian_2d_csr(32), dict(coarse_max=8)),
+    "laplacian32x32_unscaled3": (lambda: cr.laplacian_2d_csr(32), dict(coarse_max=8, level0_smoother=(3, False) + cr.laplacian_2d_bounds(32))),
+    "periodic100000": (lambda: periodic_tridiagonal(PERIODIC), dict()),
+    "tridiagonal1024": (lambda: cr.tridiagonal(1024), dict(max_levels=1)),
+    "tridiagonal1025": (lambda: cr.tridiagonal(1025), dict(max_levels=1)),
+})
+
+
+def edge_rhs(name, n):
+    """the right-hand side the case is applied to"""
+    return np.random.default_rng(9000 + list(EDGE_CASES).index(name)).uniform(-1, 1, n)
 
 
 SYSTEMS = {  # name: (solver, builder)

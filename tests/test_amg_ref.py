@@ -1,7 +1,9 @@
 """The NumPy twin of aggregation AMG (tests/amg_ref.py) held to facts of its own, on the CPU: the aggregates partition the rows and
 their roots keep their distance, the coarse operator is the Galerkin product, the cycle is a symmetric positive definite operator
 that contracts the error in the energy norm, strength keeps aggregates inside the strong direction, the preconditioned counts fall
-as the prototype's did, and three mutations of the method are each noticed."""
+as the prototype's did, and three mutations of the method are each noticed.  Further down: the generators of
+tests/test_gpu_amg_edges.py (the periodic tridiagonal matrix whose level 1 no LDS window holds, the fuzz systems), their coarse
+operators against P^T A P in int64, and five mutations against the gate of that GPU test on every case it applies."""
 import numpy as np
 import pytest
 
@@ -188,3 +190,174 @@ def test_mutation_of_the_post_smoother_breaks_symmetry():
     n, rp, cc, cv = cr.laplacian_2d_csr(12)
     B = ar.Hierarchy(n, rp, cc, cv, coarse_max=8, mutate="post_degree").dense_operator()
     assert np.max(np.abs(B - B.T)) / np.max(np.abs(B)) >= 1e-4
+
+
+# ---- the generators of tests/test_gpu_amg_edges.py ------------------------------------------------------------------------------------
+WINDOW_ROWS, WINDOW_CAPACITY = 256, 16384  # kWinRows and kWinDoubles of csrc/kernels_csr.hip: the LDS-window kernel's block and tile
+
+
+def _widest_window(n, rp, cc):
+    """the widest span of columns, last - first + 1, over the blocks of 256 rows"""
+    spans = [int(cc[rp[i]:rp[min(i + WINDOW_ROWS, n)]].max()) - int(cc[rp[i]:rp[min(i + WINDOW_ROWS, n)]].min()) + 1
+             for i in range(0, n, WINDOW_ROWS) if rp[min(i + WINDOW_ROWS, n)] > rp[i]]
+    return max(spans)
+
+
+def test_the_periodic_tridiagonal_matrix():
+    n, rp, cc, cv = ar.periodic_tridiagonal(7)
+    want = 2.5 * np.eye(7) - np.roll(np.eye(7), 1, axis=1) - np.roll(np.eye(7), -1, axis=1)
+    assert np.array_equal(ar.dense_of(n, rp, cc, cv), want) and list(cc[:6]) == [0, 1, 6, 0, 1, 2] and len(cc) == 21
+    n, rp, cc, cv = ar.periodic_tridiagonal(ar.PERIODIC)
+    assert np.array_equal(np.diff(rp), np.full(n, 3)) and np.all(np.diff(cc.reshape(n, 3), axis=1) > 0), "columns ascend"
+
+
+def test_the_reproducers_level_1_is_wider_than_the_lds_window_and_level_2_is_not():
+    """what makes a forced LDS-window kernel fail on level 1 alone: a block of 256 rows there spans every column"""
+    H = ar.Hierarchy(*ar.periodic_tridiagonal(ar.PERIODIC))
+    assert H.rows == [100000, 27529, 7601, 2091, 574, 154]
+    spans = [_widest_window(L.n, L.rp, L.cc) for L in H.levels]
+    print("widest windows:", spans)
+    assert spans[1] == 27529 > WINDOW_CAPACITY and all(s <= WINDOW_CAPACITY for s in spans[2:])
+
+
+@pytest.mark.parametrize("seed", ar.FUZZ_SEEDS)
+def test_the_fuzz_systems_are_what_they_say(seed):
+    n, rp, cc, cv = ar.fuzz_system(seed)
+    assert n in ar.FUZZ_SIZES and len(rp) == n + 1 and rp[0] == 0 and rp[-1] == len(cc) == len(cv) and cc.dtype == np.int32
+    assert np.array_equal(ar.fuzz_system(seed)[3], cv), "the same system on every call"
+    iv = exact.scaled(cv, ar.FUZZ_E)
+    for i in range(n):
+        c, v, f = cc[rp[i]:rp[i + 1]], iv[rp[i]:rp[i + 1]], cv[rp[i]:rp[i + 1]]
+        off = c != i
+        assert len(set(c[off].tolist())) <= min(6, n - 1) and c.min() >= 0 and c.max() < n
+        assert all(count <= 2 for count in np.bincount(c[off], minlength=1)), "an off-diagonal entry is stored twice at most"
+        odd = np.abs(v[off & (v != 0)])
+        odd = odd // (odd & -odd)  # the mantissa: at most 10 bits, and the exponent within -10 .. 0
+        assert np.all(odd < 2**10) and np.all(np.abs(f[off]) < 2**10)
+        assert 1 <= int((~off).sum()) <= 2 and v[~off].sum() > np.abs(v[off]).sum(), "a positive, strictly dominant diagonal"
+    ar.Hierarchy(n, rp, cc, cv, **ar.fuzz_setup(seed))  # the twin raises on none of them: no zero diagonal, no singular operator
+
+
+def test_the_fuzz_systems_cover_what_csr_allows():
+    sizes, setups = set(), set()
+    entries = doubled = zeros = rows = split = unsorted = 0
+    for seed in ar.FUZZ_SEEDS:
+        n, rp, cc, cv = ar.fuzz_system(seed)
+        sizes.add(n)
+        setups.add(tuple(ar.fuzz_setup(seed).values()))
+        r = np.repeat(np.arange(n), np.diff(rp))
+        off = r != cc
+        pairs = r[off].astype(np.int64) * n + cc[off]
+        entries += len(set(pairs.tolist()))
+        doubled += len(pairs) - len(set(pairs.tolist()))
+        zeros += int((cv[off] == 0.0).sum())
+        rows += n
+        split += int((~off).sum()) - n
+        unsorted += sum(bool(np.any(np.diff(cc[rp[i]:rp[i + 1]]) < 0)) for i in range(n))
+        if n >= 17:
+            pattern = ar.dense_of(n, rp, cc, np.ones(len(cc))) != 0
+            assert not np.array_equal(pattern, pattern.T), "a structurally nonsymmetric pattern"
+    print(f"{entries} off-diagonal positions, {doubled} stored twice, {zeros} stored zeros; {rows} rows, {split} with a split diagonal, {unsorted} unsorted")
+    assert sizes == set(ar.FUZZ_SIZES) and {s[0] for s in setups} == {0.0, 0.1, 0.5} and {s[1] for s in setups} == {1, 8, 256}
+    assert 0.12 <= doubled / entries <= 0.18 and 0.07 <= zeros / entries <= 0.13 and 0.45 <= split / rows <= 0.55 and unsorted >= rows // 2
+
+
+# ---- the Galerkin product in integers --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", ar.FUZZ_SEEDS)
+def test_fuzz_coarse_operators_are_the_galerkin_products_in_integers(seed):
+    """every coarse value is P^T A P computed in int64 by a scatter that knows nothing of the twin's ordering, the stored pattern
+    is the pattern of the products, and the sum of all stored entries - 1^T A 1, which P^T . P keeps - is one integer on every
+    level"""
+    n, rp, cc, cv = ar.fuzz_system(seed)
+    H = ar.Hierarchy(n, rp, cc, cv, **ar.fuzz_setup(seed))
+    total = int(exact.scaled(cv, ar.FUZZ_E).sum())
+    for l in range(len(H.levels) - 1):
+        L, C = H.levels[l], H.levels[l + 1]
+        want, stored = ar.galerkin_int64(L.n, L.rp, L.cc, L.cv, L.agg, L.nc)
+        rows = np.repeat(np.arange(C.n), np.diff(C.rp))
+        got = np.zeros((C.n, C.n), dtype=np.int64)
+        got[rows, C.cc] = exact.scaled(C.cv, ar.FUZZ_E)
+        held = np.zeros((C.n, C.n), dtype=bool)
+        held[rows, C.cc] = True
+        assert len(set(zip(rows.tolist(), C.cc.tolist()))) == C.nnz, "a coarse entry is stored once"
+        assert np.array_equal(got, want) and np.array_equal(held, stored), (seed, l)
+        assert int(exact.scaled(C.cv, ar.FUZZ_E).sum()) == total, (seed, l)
+        d = ar.diagonal_of(C.n, C.rp, C.cc, C.cv)
+        assert np.all(d > 0) and np.all(2 * d > np.bincount(rows, weights=np.abs(C.cv), minlength=C.n)), "row dominance survives"
+
+
+def test_the_level_0_smoother_can_be_replaced():
+    n, rp, cc, cv = cr.laplacian_2d_csr(12)
+    H = ar.Hierarchy(n, rp, cc, cv, coarse_max=8)
+    lmin, lmax = cr.laplacian_2d_bounds(12)
+    G = ar.Hierarchy(n, rp, cc, cv, coarse_max=8, level0_smoother=(3, False, lmin, lmax))
+    assert G.rows == H.rows and G.launches() == H.launches() + 4
+    same = ar.Hierarchy(n, rp, cc, cv, coarse_max=8, level0_smoother=(2, True, 2.0 / 30.0, 2.0))  # (the default set-up, spelled out)
+    r = np.random.default_rng(3).uniform(-1, 1, n)
+    assert same.apply(r).tobytes() == H.apply(r).tobytes() and G.apply(r).tobytes() != H.apply(r).tobytes()
+    # levels 1 and below keep their smoothers: the two differ by level 0's polynomial alone
+    assert all(a.cheby()[1] == b.cheby()[1] for a, b in zip(G.levels[1:], H.levels[1:]))
+    B = G.dense_operator()
+    assert np.max(np.abs(B - B.T)) / np.max(np.abs(B)) <= 1e-13 and np.linalg.eigvalsh(0.5 * (B + B.T)).min() > 0.0
+
+
+# ---- sensitivity: what the gate of tests/test_gpu_amg_edges.py would notice ------------------------------------------------------------
+_ONE_LEVEL = "one level: nothing is aggregated, restricted or prolonged, and no smoother follows a correction"
+_SYMMETRIC = "a symmetric pattern: roots are more than two hops apart, no row sees two of them"
+_ONE_ROOT = "one aggregate: there is one root to join"
+_ALL_STRONG = "theta = 0: every stored off-diagonal entry is strong"
+# (mutation, case): why the mutation cannot change the case.  Held below: the mutated twin returns the unmutated twin's bytes.
+EXEMPT = {(m, case): _ONE_LEVEL for m in ar.MUTATIONS
+          for case in ("anisotropic16x16", "anisotropic16x16_degree1", "diagonal257", "diagonal257_degree1", "fuzz00", "fuzz05", "fuzz09",
+                       "fuzz10", "fuzz13", "fuzz21", "tridiagonal1024", "tridiagonal1025")}
+EXEMPT.update({("tie", case): _SYMMETRIC for case in ("arrow300", "arrow300_degree1", "anisotropic16x16_quarter", "anisotropic16x16_quarter_degree1",
+                                                      "tridiagonal257", "tridiagonal257_degree1", "laplacian32x32", "laplacian32x32_unscaled3",
+                                                      "periodic100000")})
+EXEMPT.update({("tie", case): _ONE_ROOT for case in ("fuzz03", "fuzz19")})
+EXEMPT.update({("strong_sum", case): _ALL_STRONG for case in ("arrow300", "arrow300_degree1", "nonsymmetric500", "nonsymmetric500_degree1",
+                                                              "tridiagonal257", "tridiagonal257_degree1", "laplacian32x32", "laplacian32x32_unscaled3",
+                                                              "periodic100000", "fuzz03", "fuzz06", "fuzz12", "fuzz15", "fuzz18")})
+EXEMPT[("strong_sum", "fuzz19")] = "two rows: the one weak entry is a stored zero"
+
+
+@pytest.mark.parametrize("name", list(ar.EDGE_CASES))
+def test_every_mutation_moves_every_application(name):
+    """each of the five mutations moves Hierarchy.apply away from the unmutated twin by more than the gate the GPU test holds the
+    engine to (oracle_lib.REL_TOL x max |want|), on every case that test applies - or is listed in EXEMPT with its reason"""
+    import copy
+
+    import oracle_lib as ol
+
+    build, kw = ar.EDGE_CASES[name]
+    if kw.get("max_levels") == 1:  # (one level by its arguments: the inverse of 1024 rows need not be built to know)
+        assert all(EXEMPT[m, name] == _ONE_LEVEL for m in ar.MUTATIONS)
+        return
+    n, rp, cc, cv = build()
+    H = ar.Hierarchy(n, rp, cc, cv, **kw)
+    r = ar.edge_rhs(name, n)
+    want = H.apply(r)
+    gate = ol.REL_TOL * np.max(np.abs(want))
+    for m in ar.MUTATIONS:
+        if m in ("tie", "strong_sum"):  # these change the hierarchy
+            M = ar.Hierarchy(n, rp, cc, cv, mutate=m, **kw)
+        else:  # these the cycle alone
+            M = copy.copy(H)
+            M.mutate = m
+        got = M.apply(r)
+        moved = float(np.max(np.abs(got - want)))
+        if (m, name) in EXEMPT:
+            assert got.tobytes() == want.tobytes(), (m, name, "is listed as exempt and moved", moved)
+            if EXEMPT[m, name] == _ONE_LEVEL:
+                assert len(H.levels) == 1
+            continue
+        print(f"{name}, {m}: moved by {moved / np.max(np.abs(want)):.3e} of max |want|")
+        assert moved > gate, (m, name, moved, gate)
+
+
+def test_every_mutation_is_caught_by_some_case():
+    """(the test above holds every pair that is not exempt to the gate)"""
+    assert set(case for _, case in EXEMPT) <= set(ar.EDGE_CASES) and set(m for m, _ in EXEMPT) <= set(ar.MUTATIONS)
+    for m in ar.MUTATIONS:
+        caught = [case for case in ar.EDGE_CASES if (m, case) not in EXEMPT]
+        print(f"{m}: caught by {len(caught)} of {len(ar.EDGE_CASES)} cases")
+        assert caught

@@ -3,7 +3,8 @@ SPMV_PRECOND_CHEBYSHEV in spmv_cg, spmv_bicgstab and spmv_gmres) against the Num
 tests/test_chebyshev_ref.py holds to facts of its own on the CPU.
 
 Shapes, for the paths of the kernels: n = 0, 1, 2, 3 and 257, diagonal and tridiagonal; n = 2 kMaxGrid kBlock + 3 = 1,048,579
-tridiagonal (the grid-stride loop's second trip and an odd tail); r and z 8 bytes past a 16-byte boundary (the narrow path), alone
+tridiagonal (the grid-stride loop's second trip and an odd tail); n = (8 << 20) + 3 = 8,388,611 tridiagonal (from 8 << 20 rows on the
+wide step reads and writes w and t nontemporally: all eight instantiations, scaled x first x last); r and z 8 bytes past a 16-byte boundary (the narrow path), alone
 and mixed with aligned vectors; degree 1 (the first and the last term in one launch), 2 and 9; scaled and unscaled; a CSR handle
 forced to the row-parallel kernel and one left to AUTO; an ELL and a COO handle with explicit bounds."""
 import numpy as np
@@ -128,6 +129,74 @@ def test_application_matches_the_twin_beyond_one_trip_of_the_grid(ctx, aligned):
     r_host = _once(("r", "big"), lambda: np.random.default_rng(7).uniform(-1, 1, n))
     want = _once(("want", "big"), lambda: _twin_apply(n, rp, cc, cv, (2, True, 2.0 / 30.0, 2.0), r_host))
     _close(_apply(ctx, A, r_host, aligned), want, f"n = {n}, aligned {aligned}")
+
+
+# From kChebyNtRows = 8 << 20 rows on the wide step kernel reads w and t and writes t with nontemporal accesses: eight instantiations
+# (scaled x first x last) that the sizes above never reach and the benchmarked sizes always do.  One matrix, one r, one handle.
+NT_ROWS = (8 << 20) + 3
+
+
+def _nt(ctx):
+    def make():
+        n, rp, cc, cv = _matrix("tridiagonal", NT_ROWS)
+        r_host = np.random.default_rng(11).uniform(-1, 1, n)
+        return n, rp, cc, cv, r_host, ctx.csr(n, n, rp, cc, cv), ctx.vector_from(r_host)
+
+    return _once(("nt", "system"), make)
+
+
+def _nt_setup(ctx, A, n, rp, cc, cv, degree, scaled):
+    """the default scaled set-up, or unscaled on [0.1, the row bound]; returns chebyshev_info"""
+    if scaled:
+        ctx.chebyshev_setup(A, degree)
+        assert ctx.chebyshev_info(A) == (degree, True, 2.0 / 30.0, 2.0)
+    else:
+        ctx.chebyshev_setup(A, degree, scaled=False, lmin=0.1, lmax=cr.row_bound(n, rp, cc, cv))
+        assert ctx.chebyshev_info(A) == (degree, False, 0.1, 4.0)
+    return ctx.chebyshev_info(A)
+
+
+@pytest.mark.parametrize("scaled", (True, False), ids=["scaled", "unscaled"])
+@pytest.mark.parametrize("degree", (1, 3))
+def test_application_matches_the_twin_on_the_nontemporal_path(ctx, degree, scaled):
+    """degree 1: the first and the last term in one launch; degree 3: a first, a middle and a last one"""
+    n, rp, cc, cv, r_host, A, r = _nt(ctx)
+    info = _nt_setup(ctx, A, n, rp, cc, cv, degree, scaled)
+    want = _once(("nt", "want", degree, scaled), lambda: _twin_apply(n, rp, cc, cv, info, r_host))
+    z = ctx.vector(n)
+    z.fill(7.0)  # (whatever z holds is ignored)
+    assert r.device_ptr % 16 == 0 and z.device_ptr % 16 == 0 and n >= 8 << 20
+    ctx.chebyshev_solve(A, r, z)
+    ctx.sync()
+    _close(z.download(), want, f"n = {n}, degree {degree}, scaled {scaled}, kernel {A.info.kernel}")
+
+
+def test_a_narrow_z_of_that_size_takes_the_plain_path(ctx):
+    """for contrast: 8 bytes past a 16-byte boundary there is no wide path, so no nontemporal one; the same numbers"""
+    n, rp, cc, cv, r_host, A, r = _nt(ctx)
+    info = _nt_setup(ctx, A, n, rp, cc, cv, 3, True)
+    want = _once(("nt", "want", 3, True), lambda: _twin_apply(n, rp, cc, cv, info, r_host))
+    z, keep = _device_vector(ctx, np.full(n, 7.0), False)
+    ctx.chebyshev_solve(A, r, z)
+    ctx.sync()
+    _close(z.download(), want, f"n = {n}, degree 3, scaled, z narrow")
+
+
+def test_the_smoother_follows_the_twin_on_the_nontemporal_path(ctx):
+    """x += M^-1 (b - A x): the residual is the state's own t, so no step is a FIRST one, and the start adds into x"""
+    n, rp, cc, cv, r_host, A, b = _nt(ctx)
+    info = _nt_setup(ctx, A, n, rp, cc, cv, 2, True)
+    c0, c1, c2 = cr.coefficients(2, info[2], info[3])
+    s, mv = cr.inverse_diagonal(n, rp, cc, cv), _mv(n, rp, cc, cv)
+    twin = np.random.default_rng(12).uniform(-1, 1, n)
+    x = ctx.vector_from(twin)
+    assert x.device_ptr % 16 == 0
+    for call in range(2):
+        ctx.chebyshev(A, b, x)
+        ctx.sync()
+        twin = cr.smooth(mv, s, r_host, twin, c0, c1, c2)
+        _close(x.download(), twin, f"n = {n}, degree 2, call {call}: x against the twin's")
+    assert b.download().tobytes() == r_host.tobytes()
 
 
 @pytest.mark.parametrize("scaled", (False, True), ids=["unscaled", "scaled"])
