@@ -19,6 +19,7 @@ LIB_PATH = Path(os.environ.get("SPMV_HIP_SO") or _PKG / "lib" / "libspmv_hip.so"
 FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA = 0, 1, 2, 3, 4
 CSR_AUTO, CSR_VECTOR, CSR_LDSWIN, CSR_SCALAR, CSR_PANEL, CSR_TWOPHASE, CSR_SEGSCAN, CSR_SPLIT, CSR_ELL = 0, 1, 2, 3, 4, 5, 6, 7, 8
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0, PRECOND_CHEBYSHEV, PRECOND_AMG = 0, 1, 2, 3, 4, 5
+SPGEMM_AUTO, SPGEMM_ROWS, SPGEMM_SORT = 0, 1, 2  # spmv_spgemm's method
 FLAG_DPP_REDUCE, FLAG_XCD_REMAP = 1, 2
 
 _i32p = C.POINTER(C.c_int32)
@@ -122,6 +123,8 @@ SIGNATURES = {
     "spmv_amg_info": (C.c_int, [_vp, _i32p, _i64p, _i64p]),
     "spmv_amg_level": (C.c_int, [_vp, _vp, C.c_int32, _i32p, _i32p, _i32p, _f64p]),
     "spmv_amg_solve": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_spgemm": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.POINTER(_vp)]),
+    "spmv_csr_transpose": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_coo_to_csr": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_coo_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_csr_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -595,6 +598,19 @@ class Context:
         it, res = C.c_int32(0), C.c_double(0.0)
         _check(self._lib.spmv_gmres(self.h, A.h, b.h, x.h, restart, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))
         return it.value, res.value
+
+    def spgemm(self, A: "Matrix", B: "Matrix", method: int = 0) -> "Matrix":
+        """C = A B for two CSR handles (spmv_spgemm), synchronous: a structural pattern with ascending columns, every value its
+        products added left to right in stored order.  method: SPGEMM_AUTO, SPGEMM_ROWS (rows in LDS) or SPGEMM_SORT (global sort)"""
+        h = _vp()
+        _check(self._lib.spmv_spgemm(self.h, A.h, B.h, method, C.byref(h)))
+        return Matrix(self, h)
+
+    def csr_transpose(self, A: "Matrix") -> "Matrix":
+        """A^T as a CSR handle of its own (spmv_csr_transpose), synchronous: rows ascending inside a row, duplicates kept in order"""
+        h = _vp()
+        _check(self._lib.spmv_csr_transpose(self.h, A.h, C.byref(h)))
+        return Matrix(self, h)
 
     def coo_to_csr(self, coo: "Matrix") -> "Matrix":
         h = _vp()

@@ -917,6 +917,7 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         return SPMV_OK;
     }
     if (amg_get_param(m, name, value)) return SPMV_OK;  // "amg_ready", "amg_levels", "amg_bytes", "amg_launches", "amg_mis_rounds", "amg_level_kernel"
+    if (spgemm_get_param(m, name, value)) return SPMV_OK;  // "spgemm_products", "spgemm_rows_lds", "spgemm_rows_sorted", "spgemm_lds_products", ...
     if (cheby_get_param(m, name, value)) return SPMV_OK;  // "cheby_ready", "cheby_degree", "cheby_bytes", "cheby_launches", ...
     if (transpose_get_param(m, name, value)) return SPMV_OK;  // "transpose_ready", "transpose_bytes", "transpose_kernel", ...
     if (!strcmp(name, "panel_keep_csr"))
@@ -1558,6 +1559,23 @@ int spmv_chebyshev(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x)
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
     return cheby_smooth(ctx, A, b->d, x->d);
+}
+
+// ---- sparse products (spgemm.hip).  Every check but the two counts is made before the device is touched. ---
+int spmv_spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, spmv_mat** out_C)
+{
+    SPMV_REQUIRE(ctx && A && B && out_C, "spmv_spgemm: null argument");
+    SPMV_TRY(spgemm_check(ctx, A, B, method, "spmv_spgemm"));
+    SPMV_TRY(use_device(ctx));
+    return spgemm(ctx, A, B, method, out_C);
+}
+
+int spmv_csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out_At)
+{
+    SPMV_REQUIRE(ctx && A && out_At, "spmv_csr_transpose: null argument");
+    SPMV_TRY(csr_transpose_check(ctx, A, "spmv_csr_transpose"));
+    SPMV_TRY(use_device(ctx));
+    return csr_transpose(ctx, A, out_At);
 }
 
 // ---- conversions ------------------------------------------------------------------------------------------

@@ -52,6 +52,7 @@
 
 #include "common.hpp"
 #include "solver_host.hpp"
+#include "sorted_runs.hpp"
 #include "wave.hpp"
 
 namespace spmv
@@ -256,34 +257,6 @@ __global__ __launch_bounds__(kBlock) void amg_key_kernel(int64_t n, const int32_
     }
 }
 
-// out[k] = src[idx[k]]
-__global__ __launch_bounds__(kBlock) void amg_gather_kernel(int64_t n, const int32_t* __restrict__ src, const int32_t* __restrict__ idx,
-                                                            int32_t* __restrict__ out)
-{
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock) out[k] = src[idx[k]];
-}
-
-// head[k] = 1 where the k-th entry in (I, J) order starts a run, k < nnz;  head[nnz] = 0
-__global__ __launch_bounds__(kBlock) void amg_head_kernel(int64_t nnz, const int32_t* __restrict__ order, const int32_t* __restrict__ key_i,
-                                                          const int32_t* __restrict__ key_j, int32_t* __restrict__ head)
-{
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k <= nnz; k += (int64_t)gridDim.x * kBlock)
-    {
-        int32_t h = 0;
-        if (k < nnz)
-        {
-            const int32_t e = order[k];
-            h               = 1;
-            if (k > 0)
-            {
-                const int32_t p = order[k - 1];
-                h               = (key_i[e] != key_i[p] || key_j[e] != key_j[p]) ? 1 : 0;
-            }
-        }
-        head[k] = h;
-    }
-}
-
 // every run's start, column and row: seg_start[s] (and seg_start[runs] = nnz), col_c[s] = J, and the entries per coarse row
 __global__ __launch_bounds__(kBlock) void amg_segment_kernel(int64_t nnz, const int32_t* __restrict__ order, const int32_t* __restrict__ key_i,
                                                              const int32_t* __restrict__ key_j, const int32_t* __restrict__ head,
@@ -370,43 +343,6 @@ __global__ __launch_bounds__(kBlock) void amg_dense_apply_kernel(int n, const do
 }
 
 // ---- host helpers ----------------------------------------------------------------------------------------------------------------
-// device memory of a set-up step: freed, behind the stream, when the step returns however it returns
-struct device_pool
-{
-    spmv_ctx*          ctx;
-    const char*        who;
-    std::vector<void*> held;
-    device_pool(spmv_ctx* c, const char* w) : ctx(c), who(w) {}
-    device_pool(const device_pool&)            = delete;
-    device_pool& operator=(const device_pool&) = delete;
-    ~device_pool()
-    {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void* p : held) (void)hipFree(p);
-    }
-    template <typename T>
-    int get(T*& out, size_t count)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            SPMV_FAIL(SPMV_ERR_ALLOC, "%s: out of device memory for %zu bytes of set-up memory", who, count * sizeof(T));
-        }
-        held.push_back(p);
-        out = (T*)p;
-        return SPMV_OK;
-    }
-    void keep(void* p) { held.erase(std::remove(held.begin(), held.end(), p), held.end()); }  // the caller owns p from here on
-};
-
-int key_bits(int64_t values)
-{
-    int bits = 1;
-    while (bits < 31 && ((int64_t)1 << bits) < values) ++bits;
-    return bits;
-}
-
 void free_state(amg_state* st)
 {
     if (!st) return;
@@ -546,12 +482,12 @@ int coarse_operator(spmv_ctx* ctx, const spmv_mat* A, const int32_t* agg, int64_
     hipLaunchKernelGGL(amg_key_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, A->a, A->b, agg, key_i, key_j);
     SPMV_TRY(hip_step(hipGetLastError(), who, "the key map's launch"));
     SPMV_TRY(sort_ids_by_key(ctx, key_j, nnz, bits, ids1));
-    hipLaunchKernelGGL(amg_gather_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)key_i, (const int32_t*)ids1, key_i1);
+    hipLaunchKernelGGL(runs_gather_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)key_i, (const int32_t*)ids1, key_i1);
     SPMV_TRY(sort_ids_by_key(ctx, key_i1, nnz, bits, ids2));
-    hipLaunchKernelGGL(amg_gather_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)ids1, (const int32_t*)ids2, order);
+    hipLaunchKernelGGL(runs_gather_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)ids1, (const int32_t*)ids2, order);
     SPMV_TRY(pool.get(head, (size_t)nnz + 1));
     SPMV_TRY(pool.get(run_of, (size_t)nnz + 1));
-    hipLaunchKernelGGL(amg_head_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)order, (const int32_t*)key_i, (const int32_t*)key_j, head);
+    hipLaunchKernelGGL(runs_head_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)order, (const int32_t*)key_i, (const int32_t*)key_j, head);
     SPMV_TRY(hip_step(hipGetLastError(), who, "the head marking's launch"));
     SPMV_TRY(exclusive_scan_i32(ctx, head, run_of, nnz + 1));
     int32_t runs = 0;

@@ -377,6 +377,10 @@ struct spmv_mat
     // of copies or of the transposed state
     struct spmv::amg_state* amg              = nullptr;
     int32_t                 amg_level_kernel = 0;  // "amg_level_kernel": != 0 forces that CSR kernel id on every coarse handle of the next set-up
+
+    // a handle that spmv_spgemm made (spgemm.hip): what that product did ("spgemm_*"; 0 on every other handle)
+    bool    spgemm_made = false;
+    int64_t spgemm_products = 0, spgemm_rows_lds = 0, spgemm_rows_sorted = 0, spgemm_transient_bytes = 0;
 };
 
 namespace spmv
@@ -579,6 +583,12 @@ int  amg_level_download(spmv_ctx* ctx, const spmv_mat* m, int level, int32_t* ag
 int  amg_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z);  // z = B r, asynchronous; r and z must not overlap
 bool amg_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "amg_*"; false: not one of them
 bool amg_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "amg_level_kernel"; false: not that
+// spgemm.hip: C = A B and A^T as CSR handles of their own
+int  spgemm_check(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, const char* who);  // on the host: every refusal made before the device is touched
+int  csr_transpose_check(const spmv_ctx* ctx, const spmv_mat* A, const char* who);                              // likewise
+int  spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, spmv_mat** out);               // synchronous
+int  csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out);                                           // synchronous
+bool spgemm_get_param(const spmv_mat* m, const char* name, int64_t* value);  // "spgemm_*"; false: not one of them
 // convert_sort.hip
 int sort_ids_by_key(spmv_ctx* ctx, const int32_t* keys, int64_t n, int bits, int32_t* out_ids);
 int coo_place_by_stable_sort(spmv_ctx* ctx, int64_t nnz, int32_t nrow, const int32_t* row, const int32_t* col, const double* val,

@@ -366,8 +366,8 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
  * handle were found to be diagonals and conforming rows read no column index), "symgs_order", "symgs_colours",
  * "symgs_levels_forward", "symgs_levels_backward", "symgs_launches", "symgs_bytes", "symgs_fused" (1: the colouring is proper and
  * the sweep takes one launch per colour), "ilu0_order", "ilu0_ready", "ilu0_colours", "ilu0_levels_forward", "ilu0_levels_backward",
- * "ilu0_launches" (per application), "ilu0_bytes", the "cheby_*" names listed at spmv_chebyshev_setup and the "amg_*" names listed
- * at spmv_amg_setup. */
+ * "ilu0_launches" (per application), "ilu0_bytes", the "cheby_*" names listed at spmv_chebyshev_setup, the "amg_*" names listed
+ * at spmv_amg_setup and the "spgemm_*" names listed at spmv_spgemm. */
 int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value);
 /* ---- plans: a handle's set-up decisions as plain data (plan.hip) ------------------------------------------------------------
  * AUTO is a measurement (spmv_mat_set_kernel above): which kernel a handle runs, in which layout, with which chunk size,
@@ -791,6 +791,41 @@ int spmv_amg_info(const spmv_mat* A, int32_t* levels, int64_t* rows /* levels, o
 int spmv_amg_level(spmv_ctx* ctx, const spmv_mat* A, int32_t level, int32_t* agg_host /* rows[level], or NULL */, int32_t* row_ptr,
                    int32_t* col, double* val /* the operator of `level`, or NULLs */);
 int spmv_amg_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z);
+
+/* ---- sparse products on the device (spgemm.hip) ------------------------------------------------------------------------
+ * spmv_spgemm: C = A B for two CSR handles of one context, A m x k and B k x n, both whole matrices (row_begin 0) that still hold
+ *   their arrays.  The inputs may hold unsorted columns, duplicate entries and stored zeros.  Synchronous; *out_C is an owning CSR
+ *   handle like any other: products, solvers, set-ups, spmv_mat_download, spmv_mat_validate, and an input of another spmv_spgemm.
+ *   It selects its kernel as an uploaded handle does (a plan of the context is not applied to it).
+ *   Pattern: C holds exactly one entry (i, j) for every pair that at least one stored a_ip and stored b_pj reach.  The pattern is
+ *     structural: stored zeros and sums that cancel still give an entry.  Columns ascend strictly inside a row.
+ *   Value: the scalar products of row i are taken in the order (position of the A entry in row i as stored, then position of the B
+ *     entry in its row as stored).  Each is t = a * b, rounded once; c_ij is the sum of its t, from 0.0, left to right in that order,
+ *     in plain additions - no fma, no atomics on doubles, nothing reassociated.  Every method and every run returns the same bytes.
+ *   Empty: an empty row of A, or one that reaches only empty rows of B, is an empty row of C; nnz(C) = 0 is a valid result; m, k or
+ *     n = 0 are allowed as spmv_csr_upload allows them.
+ *   method: SPMV_SPGEMM_ROWS - a row of up to 2048 scalar products is expanded, sorted and added up in LDS by 16 lanes, a wavefront
+ *     or a workgroup (by its number of products); longer rows go through SORT in one batch.  SPMV_SPGEMM_SORT - every row is
+ *     expanded into global memory, ordered by two stable radix passes and added up run by run (40 bytes of transient memory per
+ *     scalar product).  SPMV_SPGEMM_AUTO - ROWS.
+ *   Refused on the host, before any device use: a null argument, a shard, released CSR arrays (panel_keep_csr = 0), a handle of
+ *     another context, A->ncol != B->nrow, a method outside 0 .. 2 (SPMV_ERR_INVALID); a handle that is not CSR
+ *     (SPMV_ERR_UNSUPPORTED).  After counting on the device: more than 2^31 - 1 entries in C, or more than 2^31 - 1 scalar products
+ *     on the sort path, whose ids are int32 (SPMV_ERR_UNSUPPORTED; the message names the count).  A failure frees what it
+ *     allocated and leaves *out_C untouched.
+ *   spmv_mat_get_param on the result: "spgemm_products" (scalar products formed), "spgemm_rows_lds" / "spgemm_rows_sorted" (non-empty
+ *     rows per path), "spgemm_lds_products" (the largest row, in scalar products, that the LDS path takes: 2048),
+ *     "spgemm_transient_bytes" (device memory the call held beside C and the radix sort's own buffers).  0 on any other handle.
+ * spmv_csr_transpose: the n x m CSR handle of A^T.  Row j holds the entries of column j of A in ascending row i; entries with equal
+ *   (j, i) keep A's stored order; duplicates are kept, not summed; values are copied bit for bit.  Same refusals as above. */
+enum
+{
+    SPMV_SPGEMM_AUTO = 0,
+    SPMV_SPGEMM_ROWS = 1,
+    SPMV_SPGEMM_SORT = 2
+};
+int spmv_spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, spmv_mat** out_C);
+int spmv_csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out_At);
 
 /* ---- format conversion on the device (src/matrix.cpp:115-154, :450-500) -------------------------- */
 /* Both keep the COO order of the entries inside each row (stable), like the reference's backward
