@@ -19,9 +19,9 @@
 // Pass 2: every row still free joins the smallest aggregate id among its neighbours as pass 1 left them.  A removed row has a
 // root within two steps of its own row lists, so pass 2 leaves no row free.  Nothing depends on the order of the launches.
 //
-// Coarse operator.  A_c[I, J] = sum of a_ij over ALL stored entries with agg(i) = I and agg(j) = J.  Entry ids are ordered
-// stably by (I, J) (two passes of sort_ids_by_key, J first), runs of equal keys are marked and counted by a scan, and one lane
-// per coarse entry adds its run from 0.0 left to right in that order - plain additions, so the sum is defined.  The result is
+// Coarse operator.  A_c[I, J] = sum of a_ij over ALL stored entries with agg(i) = I and agg(j) = J.  This file writes the key
+// (I, J) of every entry; sorted_runs.hip does the rest: entry ids ordered stably by (I, J), runs of equal keys marked and counted,
+// and one lane per coarse entry adding its run from 0.0 left to right in that order - plain additions, so the sum is defined.  The result is
 // CSR with ascending columns, in a handle of its own that goes through the engine's kernel selection ("amg_level_kernel" != 0
 // forces that kernel id on every coarse handle; an id that a coarse operator cannot run - the LDS-window kernel where a block's
 // window is wider than its tile - fails the set-up with SPMV_ERR_UNSUPPORTED, naming the level).  Beside agg every level keeps the member lists agg_ptr / agg_rows (rows
@@ -257,39 +257,6 @@ __global__ __launch_bounds__(kBlock) void amg_key_kernel(int64_t n, const int32_
     }
 }
 
-// every run's start, column and row: seg_start[s] (and seg_start[runs] = nnz), col_c[s] = J, and the entries per coarse row
-__global__ __launch_bounds__(kBlock) void amg_segment_kernel(int64_t nnz, const int32_t* __restrict__ order, const int32_t* __restrict__ key_i,
-                                                             const int32_t* __restrict__ key_j, const int32_t* __restrict__ head,
-                                                             const int32_t* __restrict__ run_of, int32_t* __restrict__ seg_start,
-                                                             int32_t* __restrict__ col_c, int32_t* __restrict__ row_count)
-{
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k <= nnz; k += (int64_t)gridDim.x * kBlock)
-    {
-        if (k == nnz)
-            seg_start[run_of[k]] = (int32_t)nnz;
-        else if (head[k])
-        {
-            const int32_t s = run_of[k], e = order[k];
-            seg_start[s]    = (int32_t)k;
-            col_c[s]        = key_j[e];
-            atomicAdd(row_count + key_i[e], 1);
-        }
-    }
-}
-
-// one lane per coarse entry: its run from 0.0, left to right, plain additions
-__global__ __launch_bounds__(kBlock) void amg_run_sum_kernel(int64_t runs, const int32_t* __restrict__ seg_start, const int32_t* __restrict__ order,
-                                                             const double* __restrict__ val, double* __restrict__ val_c)
-{
-    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < runs; s += (int64_t)gridDim.x * kBlock)
-    {
-        double    acc = 0.0;
-        const int end = seg_start[s + 1];
-        for (int k = seg_start[s]; k < end; ++k) acc += val[order[k]];
-        val_c[s] = acc;
-    }
-}
-
 // ---- cycle kernels ---------------------------------------------------------------------------------------------------------------
 // b_c[I] = sum over the members i of I, ascending, of (b[i] - w[i]), from 0.0: one lane per aggregate, no atomics
 __global__ __launch_bounds__(kBlock) void amg_restrict_kernel(int64_t nc, const int32_t* __restrict__ agg_ptr, const int32_t* __restrict__ agg_rows,
@@ -469,45 +436,20 @@ int coarse_operator(spmv_ctx* ctx, const spmv_mat* A, const int32_t* agg, int64_
 {
     const char* const who = "spmv_amg_setup";
     const int64_t     n = A->nrow, nnz = A->nnz;
-    hipStream_t       s    = ctx->stream;
-    const int         bits = key_bits(nc), grid_e = stream_grid(nnz + 1);
+    hipStream_t       s = ctx->stream;
     device_pool       pool(ctx, who);
-    int32_t *         key_i, *key_j, *ids1, *key_i1, *ids2, *order, *head, *run_of, *seg_start, *row_count;
+    int32_t *         key_i, *key_j;
+    key_runs          kr;
     SPMV_TRY(pool.get(key_i, (size_t)nnz));
     SPMV_TRY(pool.get(key_j, (size_t)nnz));
-    SPMV_TRY(pool.get(ids1, (size_t)nnz));
-    SPMV_TRY(pool.get(key_i1, (size_t)nnz));
-    SPMV_TRY(pool.get(ids2, (size_t)nnz));
-    SPMV_TRY(pool.get(order, (size_t)nnz));
     hipLaunchKernelGGL(amg_key_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, A->a, A->b, agg, key_i, key_j);
     SPMV_TRY(hip_step(hipGetLastError(), who, "the key map's launch"));
-    SPMV_TRY(sort_ids_by_key(ctx, key_j, nnz, bits, ids1));
-    hipLaunchKernelGGL(runs_gather_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)key_i, (const int32_t*)ids1, key_i1);
-    SPMV_TRY(sort_ids_by_key(ctx, key_i1, nnz, bits, ids2));
-    hipLaunchKernelGGL(runs_gather_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)ids1, (const int32_t*)ids2, order);
-    SPMV_TRY(pool.get(head, (size_t)nnz + 1));
-    SPMV_TRY(pool.get(run_of, (size_t)nnz + 1));
-    hipLaunchKernelGGL(runs_head_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)order, (const int32_t*)key_i, (const int32_t*)key_j, head);
-    SPMV_TRY(hip_step(hipGetLastError(), who, "the head marking's launch"));
-    SPMV_TRY(exclusive_scan_i32(ctx, head, run_of, nnz + 1));
-    int32_t runs = 0;
-    SPMV_TRY(read_scalars(ctx, &runs, run_of + nnz, sizeof(runs), who));
-    SPMV_REQUIRE(runs >= 1 && runs <= nnz, "%s: %d coarse entries from %lld entries", who, runs, (long long)nnz);
-    SPMV_TRY(pool.get(seg_start, (size_t)runs + 1));
-    SPMV_TRY(pool.get(row_count, (size_t)nc + 1));
-    SPMV_TRY(hip_step(hipMemsetAsync(row_count, 0, sizeof(int32_t) * ((size_t)nc + 1), s), who, "clearing the coarse row counts"));
+    SPMV_TRY(runs_by_key_pair(ctx, pool, who, key_i, nc, key_j, nc, nnz, &kr));
     spmv_mat* C = nullptr;
-    SPMV_TRY(mat_alloc(ctx, SPMV_FMT_CSR, (int32_t)nc, (int32_t)nc, runs, 0, (size_t)nc + 1, (size_t)runs, (size_t)runs, &C));
-    hipLaunchKernelGGL(amg_segment_kernel, dim3(grid_e), dim3(kBlock), 0, s, nnz, (const int32_t*)order, (const int32_t*)key_i, (const int32_t*)key_j,
-                       (const int32_t*)head, (const int32_t*)run_of, seg_start, const_cast<int32_t*>(C->b), row_count);
-    int rc = hip_step(hipGetLastError(), who, "the segment kernel's launch");
-    if (rc == SPMV_OK) rc = exclusive_scan_i32(ctx, row_count, const_cast<int32_t*>(C->a), nc + 1);
-    if (rc == SPMV_OK)
-    {
-        hipLaunchKernelGGL(amg_run_sum_kernel, dim3(stream_grid(runs)), dim3(kBlock), 0, s, (int64_t)runs, (const int32_t*)seg_start,
-                           (const int32_t*)order, A->v, const_cast<double*>(C->v));
-        rc = hip_step(hipGetLastError(), who, "the run sum's launch");
-    }
+    SPMV_TRY(mat_alloc(ctx, SPMV_FMT_CSR, (int32_t)nc, (int32_t)nc, kr.runs, 0, (size_t)nc + 1, (size_t)kr.runs, (size_t)kr.runs, &C));
+    int rc = exclusive_scan_i32(ctx, kr.count_i, const_cast<int32_t*>(C->a), nc + 1);
+    // (row_ptr is also the first run of every row: run s lands at s)
+    if (rc == SPMV_OK) rc = runs_sum_into_csr(ctx, who, kr, A->v, C->a, nullptr, C->a, const_cast<int32_t*>(C->b), const_cast<double*>(C->v));
     if (rc == SPMV_OK) rc = hip_step(hipStreamSynchronize(s), who, "waiting for the coarse operator");
     if (rc == SPMV_OK)
     {

@@ -1,6 +1,6 @@
-// sorted_runs.hpp - what the set-up steps that order entries by a key pair and add up runs of equal keys share (amg.hip: the
-// coarse operator; spgemm.hip: the sort path): the scoped owner of a step's device memory, the width of a key, the gather of the
-// second stable pass and the marking of run heads.  Device code; every unit that includes it gets kernels of its own.
+// sorted_runs.hpp - what set-up steps share: the scoped owner of a step's device memory, the width of a sort key, and the
+// pipeline of sorted_runs.hip from values keyed by a pair (i, j) to CSR with the values of equal keys added up (amg.hip: the
+// coarse operator; spgemm.hip: the sort path).  Host declarations only; the kernels live in sorted_runs.hip, once.
 #pragma once
 
 #include <algorithm>
@@ -10,36 +10,6 @@
 
 namespace spmv
 {
-namespace
-{
-// out[k] = src[idx[k]]
-__global__ __launch_bounds__(kBlock) void runs_gather_kernel(int64_t n, const int32_t* __restrict__ src, const int32_t* __restrict__ idx,
-                                                            int32_t* __restrict__ out)
-{
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock) out[k] = src[idx[k]];
-}
-
-// head[k] = 1 where the k-th entry in (I, J) order starts a run, k < nnz;  head[nnz] = 0
-__global__ __launch_bounds__(kBlock) void runs_head_kernel(int64_t nnz, const int32_t* __restrict__ order, const int32_t* __restrict__ key_i,
-                                                          const int32_t* __restrict__ key_j, int32_t* __restrict__ head)
-{
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k <= nnz; k += (int64_t)gridDim.x * kBlock)
-    {
-        int32_t h = 0;
-        if (k < nnz)
-        {
-            const int32_t e = order[k];
-            h               = 1;
-            if (k > 0)
-            {
-                const int32_t p = order[k - 1];
-                h               = (key_i[e] != key_i[p] || key_j[e] != key_j[p]) ? 1 : 0;
-            }
-        }
-        head[k] = h;
-    }
-}
-
 // device memory of a set-up step: freed, behind the stream, when the step returns however it returns
 struct device_pool
 {
@@ -79,5 +49,22 @@ inline int key_bits(int64_t values)
     return bits;
 }
 
-}  // namespace
+// the runs of equal (i, j) among `total` keyed values; every pointer is device memory of the caller's pool
+struct key_runs
+{
+    int32_t  runs      = 0;        // distinct (i, j)
+    int32_t* order     = nullptr;  // [total]    value ids in stable (i, j) order
+    int32_t* seg_start = nullptr;  // [runs + 1] where every run starts in `order`; seg_start[runs] = total
+    int32_t *run_i = nullptr, *run_j = nullptr;  // [runs]
+    int32_t* count_i = nullptr;    // [n_i + 1]  runs per i, count_i[n_i] = 0: ready for exclusive_scan_i32
+};
+
+// key_i[total] < n_i, key_j[total] < n_j, 1 <= total <= INT32_MAX.  Asynchronous but for one read of the number of runs.
+int runs_by_key_pair(spmv_ctx* ctx, device_pool& pool, const char* who, const int32_t* key_i, int64_t n_i, const int32_t* key_j, int64_t n_j,
+                     int64_t total, key_runs* out);
+
+// One lane per run s with i = run_i[s]: at = c_rp[rows ? rows[i] : i] + (s - run_first[i]), c_col[at] = run_j[s], c_val[at] = the sum
+// of t[order[k]] over the run, from 0.0, left to right (__dadd_rn).  run_first is the exclusive scan of count_i.  Asynchronous.
+int runs_sum_into_csr(spmv_ctx* ctx, const char* who, const key_runs& kr, const double* t, const int32_t* run_first, const int32_t* rows,
+                      const int32_t* c_rp, int32_t* c_col, double* c_val);
 }  // namespace spmv

@@ -23,10 +23,9 @@
 // and more read 32 consecutive keys (256 B: no conflict), the distances below read every other group of j keys (2-way).
 //
 // SORT.  The rows beyond the largest capacity (every non-empty row under SPMV_SPGEMM_SORT) are expanded in (row, p, q) order into
-// key_i (the row's place in the list), key_j (the column) and t, ordered stably by (i, j) with two passes of sort_ids_by_key, j
-// first; heads are marked and scanned, and one lane per run adds its t left to right - the way amg.hip builds P^T A P.  The runs are
-// written straight into C at their rows.  40 bytes of transient global memory per product beside the sort's own buffers; the ids
-// are int32, so more than 2^31 - 1 products on this path are refused.
+// key_i (the row's place in the list), key_j (the column) and t; sorted_runs.hip orders them stably by (i, j), marks and counts the
+// runs of equal keys, and one lane per run adds its t left to right, straight into C at the run's row.  40 bytes of transient
+// global memory per product beside the sort's own buffers; the ids are int32, so more than 2^31 - 1 products on this path are refused.
 //
 // The transpose.  A's arrays read as COO with rows and columns swapped are A^T: the row of every entry is written out (4 bytes an
 // entry, transient) and coo_to_csr (convert.hip) groups by row, stable inside a row - ascending i, equal (j, i) in A's order.
@@ -229,52 +228,11 @@ __global__ __launch_bounds__(kBlock) void spgemm_expand_kernel(int64_t nlist, co
     }
 }
 
-// every run's start, listed row and column: seg_start[s] (and seg_start[runs] = total), run_row[s], run_col[s], and the runs per listed row
-__global__ __launch_bounds__(kBlock) void spgemm_segment_kernel(int64_t total, const int32_t* __restrict__ order, const int32_t* __restrict__ key_i,
-                                                                const int32_t* __restrict__ key_j, const int32_t* __restrict__ head,
-                                                                const int32_t* __restrict__ run_of, int32_t* __restrict__ seg_start,
-                                                                int32_t* __restrict__ run_row, int32_t* __restrict__ run_col,
-                                                                int32_t* __restrict__ list_count)
-{
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k <= total; k += (int64_t)gridDim.x * kBlock)
-    {
-        if (k == total)
-            seg_start[run_of[k]] = (int32_t)total;
-        else if (head[k])
-        {
-            const int32_t s = run_of[k], e = order[k];
-            seg_start[s]    = (int32_t)k;
-            run_row[s]      = key_i[e];
-            run_col[s]      = key_j[e];
-            atomicAdd(list_count + key_i[e], 1);
-        }
-    }
-}
-
 // row_count[rows[k]] = list_count[k]
 __global__ __launch_bounds__(kBlock) void spgemm_scatter_counts_kernel(int64_t nlist, const int32_t* __restrict__ rows,
                                                                        const int32_t* __restrict__ list_count, int32_t* __restrict__ row_count)
 {
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < nlist; k += (int64_t)gridDim.x * kBlock) row_count[rows[k]] = list_count[k];
-}
-
-// one lane per run: its place in C, its column, and its t from 0.0, left to right, plain additions
-__global__ __launch_bounds__(kBlock) void spgemm_run_sum_kernel(int64_t runs, const int32_t* __restrict__ seg_start, const int32_t* __restrict__ order,
-                                                                const double* __restrict__ t, const int32_t* __restrict__ run_row,
-                                                                const int32_t* __restrict__ run_col, const int32_t* __restrict__ run_first,
-                                                                const int32_t* __restrict__ rows, const int32_t* __restrict__ c_rp,
-                                                                int32_t* __restrict__ c_col, double* __restrict__ c_val)
-{
-    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < runs; s += (int64_t)gridDim.x * kBlock)
-    {
-        double    acc = 0.0;
-        const int end = seg_start[s + 1];
-        for (int k = seg_start[s]; k < end; ++k) acc = __dadd_rn(acc, t[order[k]]);
-        const int32_t k  = run_row[s];
-        const int64_t at = (int64_t)c_rp[rows[k]] + (s - run_first[k]);
-        c_col[at]        = run_col[s];
-        c_val[at]        = acc;
-    }
 }
 
 // ---- the transpose ----------------------------------------------------------------------------------------------------------------
@@ -291,8 +249,8 @@ __global__ __launch_bounds__(kBlock) void spgemm_entry_rows_kernel(int64_t m, co
 // what the sort path leaves for the second pass
 struct sorted_part
 {
-    int64_t  nlist = 0, runs = 0;
-    int32_t *rows = nullptr, *seg_start = nullptr, *order = nullptr, *run_row = nullptr, *run_col = nullptr, *run_first = nullptr;
+    key_runs kr;  // i: the place in the list of rows, j: the column
+    int32_t *rows = nullptr, *run_first = nullptr;
     double*  t = nullptr;
 };
 
@@ -313,56 +271,24 @@ int sort_path_count(spmv_ctx* ctx, device_pool& pool, const spmv_mat* A, const s
 {
     const char* const who = "spmv_spgemm";
     hipStream_t       s   = ctx->stream;
-    const int         grid_t = stream_grid(total + 1), grid_l = stream_grid(nlist + 1);
-    int32_t *         len, *first, *key_i, *key_j, *ids1, *key_i1, *ids2, *order, *head, *run_of, *seg_start, *run_row, *run_col, *list_count, *run_first;
-    double*           t;
+    const int         grid_l = stream_grid(nlist + 1);
+    int32_t *         len, *first, *key_i, *key_j;
     SPMV_TRY(pool.get(len, (size_t)nlist + 1));
     SPMV_TRY(pool.get(first, (size_t)nlist + 1));
     hipLaunchKernelGGL(spgemm_list_products_kernel, dim3(grid_l), dim3(kBlock), 0, s, nlist, (const int32_t*)rows, ub, len);
     SPMV_TRY(exclusive_scan_i32(ctx, len, first, nlist + 1));
     SPMV_TRY(pool.get(key_i, (size_t)total));
     SPMV_TRY(pool.get(key_j, (size_t)total));
-    SPMV_TRY(pool.get(t, (size_t)total));
-    SPMV_TRY(pool.get(ids1, (size_t)total));
-    SPMV_TRY(pool.get(key_i1, (size_t)total));
-    SPMV_TRY(pool.get(ids2, (size_t)total));
-    SPMV_TRY(pool.get(order, (size_t)total));
+    SPMV_TRY(pool.get(out->t, (size_t)total));
     hipLaunchKernelGGL(spgemm_expand_kernel, dim3(stream_grid(nlist * kExpandLanes)), dim3(kBlock), 0, s, nlist, (const int32_t*)rows, A->a, A->b, A->v,
-                       B->a, B->b, B->v, (const int32_t*)first, key_i, key_j, t);
+                       B->a, B->b, B->v, (const int32_t*)first, key_i, key_j, out->t);
     SPMV_TRY(hip_step(hipGetLastError(), who, "the expansion's launch"));
-    SPMV_TRY(sort_ids_by_key(ctx, key_j, total, key_bits(B->ncol), ids1));
-    hipLaunchKernelGGL(runs_gather_kernel, dim3(grid_t), dim3(kBlock), 0, s, total, (const int32_t*)key_i, (const int32_t*)ids1, key_i1);
-    SPMV_TRY(sort_ids_by_key(ctx, key_i1, total, key_bits(nlist), ids2));
-    hipLaunchKernelGGL(runs_gather_kernel, dim3(grid_t), dim3(kBlock), 0, s, total, (const int32_t*)ids1, (const int32_t*)ids2, order);
-    SPMV_TRY(pool.get(head, (size_t)total + 1));
-    SPMV_TRY(pool.get(run_of, (size_t)total + 1));
-    hipLaunchKernelGGL(runs_head_kernel, dim3(grid_t), dim3(kBlock), 0, s, total, (const int32_t*)order, (const int32_t*)key_i, (const int32_t*)key_j, head);
-    SPMV_TRY(hip_step(hipGetLastError(), who, "the head marking's launch"));
-    SPMV_TRY(exclusive_scan_i32(ctx, head, run_of, total + 1));
-    int32_t runs = 0;
-    SPMV_TRY(read_scalars(ctx, &runs, run_of + total, sizeof(runs), who));
-    SPMV_REQUIRE(runs >= 1 && runs <= total, "%s: %d entries from %lld products", who, runs, (long long)total);
-    SPMV_TRY(pool.get(seg_start, (size_t)runs + 1));
-    SPMV_TRY(pool.get(run_row, (size_t)runs));
-    SPMV_TRY(pool.get(run_col, (size_t)runs));
-    SPMV_TRY(pool.get(list_count, (size_t)nlist + 1));
-    SPMV_TRY(pool.get(run_first, (size_t)nlist + 1));
-    SPMV_TRY(hip_step(hipMemsetAsync(list_count, 0, sizeof(int32_t) * ((size_t)nlist + 1), s), who, "clearing the listed rows' counts"));
-    hipLaunchKernelGGL(spgemm_segment_kernel, dim3(grid_t), dim3(kBlock), 0, s, total, (const int32_t*)order, (const int32_t*)key_i, (const int32_t*)key_j,
-                       (const int32_t*)head, (const int32_t*)run_of, seg_start, run_row, run_col, list_count);
-    SPMV_TRY(hip_step(hipGetLastError(), who, "the segment kernel's launch"));
-    SPMV_TRY(exclusive_scan_i32(ctx, list_count, run_first, nlist + 1));
-    hipLaunchKernelGGL(spgemm_scatter_counts_kernel, dim3(grid_l), dim3(kBlock), 0, s, nlist, (const int32_t*)rows, (const int32_t*)list_count, row_count);
+    SPMV_TRY(runs_by_key_pair(ctx, pool, who, key_i, nlist, key_j, B->ncol, total, &out->kr));
+    SPMV_TRY(pool.get(out->run_first, (size_t)nlist + 1));
+    SPMV_TRY(exclusive_scan_i32(ctx, out->kr.count_i, out->run_first, nlist + 1));
+    hipLaunchKernelGGL(spgemm_scatter_counts_kernel, dim3(grid_l), dim3(kBlock), 0, s, nlist, (const int32_t*)rows, (const int32_t*)out->kr.count_i, row_count);
     SPMV_TRY(hip_step(hipGetLastError(), who, "the counts' launch"));
-    out->nlist     = nlist;
-    out->runs      = runs;
-    out->rows      = rows;
-    out->seg_start = seg_start;
-    out->order     = order;
-    out->run_row   = run_row;
-    out->run_col   = run_col;
-    out->run_first = run_first;
-    out->t         = t;
+    out->rows = rows;
     return SPMV_OK;
 }
 
@@ -457,7 +383,7 @@ int spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, 
             SPMV_TRY(sort_path_count(ctx, pool, A, B, ub, nrows[kSpgemmSort], ids + first[kSpgemmSort], (int64_t)sort_products, row_count, &sp));
         SPMV_TRY(read_scalars(ctx, h, counters, sizeof(h), who));
     }
-    const unsigned long long entries = h[kCntLdsEntries] + (unsigned long long)sp.runs;
+    const unsigned long long entries = h[kCntLdsEntries] + (unsigned long long)sp.kr.runs;
     if (entries > (unsigned long long)INT32_MAX)
         SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the product holds %llu entries, a CSR handle at most %d (int32 offsets)", who, entries, INT32_MAX);
     spmv_mat* C = nullptr;
@@ -468,11 +394,9 @@ int spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, 
         if (nrows[kSpgemmLane16]) launch_rows<kSpgemmLane16, true>(s, nrows[kSpgemmLane16], ids + first[kSpgemmLane16], A, B, ub, nullptr, C, counters);
         if (nrows[kSpgemmWave]) launch_rows<kSpgemmWave, true>(s, nrows[kSpgemmWave], ids + first[kSpgemmWave], A, B, ub, nullptr, C, counters);
         if (nrows[kSpgemmBlock]) launch_rows<kSpgemmBlock, true>(s, nrows[kSpgemmBlock], ids + first[kSpgemmBlock], A, B, ub, nullptr, C, counters);
-        if (sp.runs)
-            hipLaunchKernelGGL(spgemm_run_sum_kernel, dim3(stream_grid(sp.runs)), dim3(kBlock), 0, s, sp.runs, (const int32_t*)sp.seg_start,
-                               (const int32_t*)sp.order, (const double*)sp.t, (const int32_t*)sp.run_row, (const int32_t*)sp.run_col,
-                               (const int32_t*)sp.run_first, (const int32_t*)sp.rows, C->a, const_cast<int32_t*>(C->b), const_cast<double*>(C->v));
         rc = hip_step(hipGetLastError(), who, "a launch of the filling pass");
+        if (rc == SPMV_OK && sp.kr.runs)
+            rc = runs_sum_into_csr(ctx, who, sp.kr, sp.t, sp.run_first, sp.rows, C->a, const_cast<int32_t*>(C->b), const_cast<double*>(C->v));
     }
     if (rc == SPMV_OK) rc = hip_step(hipStreamSynchronize(s), who, "waiting for the product");
     C->pb_trial = A->pb_trial;               // ("panel_trial" of the source handle holds for what is built from it)
