@@ -18,6 +18,7 @@ LIB_PATH = Path(os.environ.get("SPMV_HIP_SO") or _PKG / "lib" / "libspmv_hip.so"
 
 FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA = 0, 1, 2, 3, 4
 CSR_AUTO, CSR_VECTOR, CSR_LDSWIN, CSR_SCALAR, CSR_PANEL, CSR_TWOPHASE, CSR_SEGSCAN, CSR_SPLIT, CSR_ELL = 0, 1, 2, 3, 4, 5, 6, 7, 8
+AMG_RESTRICT_FUSED, AMG_RESTRICT_UNFUSED, AMG_PROLONG_FUSED, AMG_PROLONG_UNFUSED = 0, 1, 2, 3  # spmv_amg_transfer_timed
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0, PRECOND_CHEBYSHEV, PRECOND_AMG = 0, 1, 2, 3, 4, 5
 SPGEMM_AUTO, SPGEMM_ROWS, SPGEMM_SORT = 0, 1, 2  # spmv_spgemm's method
 FLAG_DPP_REDUCE, FLAG_XCD_REMAP = 1, 2
@@ -123,6 +124,9 @@ SIGNATURES = {
     "spmv_amg_info": (C.c_int, [_vp, _i32p, _i64p, _i64p]),
     "spmv_amg_level": (C.c_int, [_vp, _vp, C.c_int32, _i32p, _i32p, _i32p, _f64p]),
     "spmv_amg_solve": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_amg_setup_smoothed": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double]),
+    "spmv_amg_prolongator": (C.c_int, [_vp, _vp, C.c_int32, _i64p, _i32p, _i32p, _f64p]),
+    "spmv_amg_transfer_timed": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _f64p]),
     "spmv_spgemm": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.POINTER(_vp)]),
     "spmv_csr_transpose": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_coo_to_csr": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -522,6 +526,30 @@ class Context:
         smoother of level 0).  0 takes the default: 16 levels, a dense coarsest solve from 256 rows down, smoothing degree 2, every
         stored entry a neighbour, overcorrection 1.5"""
         _check(self._lib.spmv_amg_setup(self.h, A.h, max_levels, coarse_max, smooth_degree, strength, overcorrection))
+
+    def amg_setup_smoothed(self, A: "Matrix", max_levels: int = 0, coarse_max: int = 0, smooth_degree: int = 0, strength: float = 0.0,
+                           overcorrection: float = 0.0, prolong_damping: float = 0.0) -> None:
+        """smoothed-aggregation AMG on a CSR handle (spmv_amg_setup_smoothed), synchronous; replaces earlier AMG state as amg_setup
+        does.  0 takes the default: those of amg_setup but overcorrection 1.0, and prolong_damping 4/3"""
+        _check(self._lib.spmv_amg_setup_smoothed(self.h, A.h, max_levels, coarse_max, smooth_degree, strength, overcorrection, prolong_damping))
+
+    def amg_prolongator(self, A: "Matrix", level: int):
+        """(row_ptr, col, val) of the smoothed prolongator P of one level on the host (rows[level] x rows[level + 1])"""
+        levels, rows, _ = self.amg_info(A)
+        nnz = C.c_int64(0)
+        _check(self._lib.spmv_amg_prolongator(self.h, A.h, level, C.byref(nnz), None, None, None))
+        n, e = int(rows[level]), nnz.value
+        rp, cc, cv = np.zeros(n + 1, dtype=np.int32), np.zeros(e, dtype=np.int32), np.zeros(e, dtype=np.float64)
+        _check(self._lib.spmv_amg_prolongator(self.h, A.h, level, C.byref(nnz), rp.ctypes.data_as(_i32p), cc.ctypes.data_as(_i32p),
+                                              cv.ctypes.data_as(_f64p)))
+        return rp, cc, cv
+
+    def amg_transfer_timed(self, A: "Matrix", level: int, what: int, v: "Vector", reps: int, lanes: int = 0) -> float:
+        """milliseconds of one restriction (what AMG_RESTRICT_FUSED / AMG_RESTRICT_UNFUSED; v: its right-hand side) or prolongation
+        (AMG_PROLONG_FUSED / AMG_PROLONG_UNFUSED; v: the x it adds into) of one level of a smoothed state (spmv_amg_transfer_timed)"""
+        ms = C.c_double(0.0)
+        _check(self._lib.spmv_amg_transfer_timed(self.h, A.h, level, what, lanes, v.h, reps, C.byref(ms)))
+        return ms.value
 
     def amg_info(self, A: "Matrix") -> tuple[int, np.ndarray, np.ndarray]:
         """(levels, rows per level, entries per level) of the handle's hierarchy"""

@@ -1521,6 +1521,50 @@ int spmv_amg_setup(spmv_ctx* ctx, spmv_mat* A, int32_t max_levels, int32_t coars
     return amg_setup(ctx, A, max_levels, coarse_max, smooth_degree, strength, overcorrection);
 }
 
+int spmv_amg_setup_smoothed(spmv_ctx* ctx, spmv_mat* A, int32_t max_levels, int32_t coarse_max, int32_t smooth_degree, double strength,
+                            double overcorrection, double prolong_damping)
+{
+    const char* const who = "spmv_amg_setup_smoothed";
+    SPMV_REQUIRE(ctx && A, "%s: null argument", who);
+    SPMV_TRY(amg_check_setup_smoothed(A, max_levels, coarse_max, smooth_degree, strength, overcorrection, prolong_damping, who));
+    SPMV_REQUIRE(A->ctx == ctx, "%s: the matrix belongs to another context", who);
+    SPMV_TRY(use_device(ctx));
+    return amg_setup_smoothed(ctx, A, max_levels, coarse_max, smooth_degree, strength, overcorrection, prolong_damping);
+}
+
+int spmv_amg_prolongator(spmv_ctx* ctx, const spmv_mat* A, int32_t level, int64_t* nnz, int32_t* row_ptr, int32_t* col, double* val)
+{
+    const char* const who = "spmv_amg_prolongator";
+    SPMV_REQUIRE(ctx && A && nnz, "%s: null argument", who);
+    SPMV_TRY(amg_check_handle(A, who));
+    if (!A->amg) SPMV_FAIL(SPMV_ERR_INVALID, "%s: the handle was not set up (spmv_amg_setup_smoothed)", who);
+    SPMV_TRY(use_device(ctx));
+    return amg_prolongator_download(ctx, A, level, nnz, row_ptr, col, val);
+}
+
+int spmv_amg_transfer_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t level, int32_t what, int32_t lanes, spmv_vec* v, int32_t reps, double* ms_per_call)
+{
+    const char* const who = "spmv_amg_transfer_timed";
+    SPMV_REQUIRE(ctx && A && v && ms_per_call, "%s: null argument", who);
+    SPMV_REQUIRE(reps > 0, "%s: reps=%d", who, reps);
+    SPMV_TRY(amg_check_handle(A, who));
+    SPMV_TRY(amg_check_transfer(A, level, what, lanes, v->n, who));
+    SPMV_TRY(use_device(ctx));
+    void* t = nullptr;
+    if (hipMalloc(&t, sizeof(double) * (size_t)std::max<int64_t>(v->n, 1)) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        SPMV_FAIL(SPMV_ERR_ALLOC, "%s: out of device memory for a work vector of %lld entries", who, (long long)v->n);
+    }
+    float     ms = 0.f;
+    const int rc = time_launches(ctx, reps, [&] { return amg_transfer_launch(ctx, A, level, what, lanes, v->d, (double*)t); }, &ms);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(t);
+    SPMV_TRY(rc);
+    *ms_per_call = ms;
+    return SPMV_OK;
+}
+
 int spmv_amg_info(const spmv_mat* A, int32_t* levels, int64_t* rows, int64_t* nnz)
 {
     SPMV_REQUIRE(A && levels, "spmv_amg_info: null argument");

@@ -47,9 +47,30 @@
 // sums in LDS, which the tests see return equal bits on their small hierarchies) - give equal bits from call to call on a level 0
 // that runs one of them; no such promise under SEGSCAN and SPLIT (atomic adds on y in arrival order) nor under AUTO, where every
 // coarse handle selects for itself - from 64K entries on by a timed trial that may choose any of the eight.
+//
+// Smoothed aggregation (spmv_amg_setup_smoothed; tests/amg_sa_ref.py is its twin).  Aggregates, strength mask and stop rules are
+// the ones above.  On level l:
+//   A^F   theta <= 0: the level's own arrays, no copy.  theta > 0: row i holds, in stored order, every stored diagonal entry and
+//         every entry the mask calls a neighbour; a row with a weak off-diagonal entry ends on one more entry (i, i), the sum of its
+//         weak values from 0.0 left to right (count, exclusive_scan_i32, fill: a transient CSR handle).
+//   d_i   the sum of the diagonal entries of row i of A^F in stored order (amg_diag_kernel); a zero d_i: SPMV_ERR_INVALID.
+//   lam   the row bound of chebyshev.hip over A^F with s_i = 1 / d_i (for theta <= 0 the lmax of the level's smoother).
+//   T     n x nc, one entry 1.0 at (i, agg(i)), row_ptr iota: a transient CSR handle.
+//   P     AT = spgemm(A^F, T); g = prolong_damping / lam on the host; c_i = g / d_i; P[i, J] = e - c_i AT[i, J] with e = 1.0 where
+//         J = agg(i) and 0.0 elsewhere: the product rounded once, then a plain subtraction (amg_smooth_prolongator_kernel, over
+//         AT's own arrays: the handle becomes P).
+//   R     csr_transpose(P);  A_{l+1} = spgemm(R, spgemm(A_l, P)) with the full A_l, under "amg_level_kernel" as above.
+// spgemm.hip defines every sum and the row bound is a maximum: the hierarchy is defined bit for bit.  P and R stay with the level;
+// T, A^F and A P are freed before the next level is built.  The cycle differs in two launches a level, so that it keeps 4 d + 7:
+//   b_{l+1}[I] = sum_k R[I, k] (b_l[i_k] - w[i_k])        amg_restrict_csr_kernel
+//   x_l[i] += omega sum_J P[i, J] x_{l+1}[J]              amg_prolong_csr_kernel
+// A group of g = 2^k lanes serves a row: lane t takes the entries t, t + g, .. left to right (fma), then the xor butterfly of
+// wave.hpp; no atomics, every result is stored once, equal bits from call to call for a given g.  g comes per level and per
+// operator from the mean row length (amg_sa_settings.hpp).
 #include <cmath>
 #include <memory>
 
+#include "amg_sa_settings.hpp"
 #include "common.hpp"
 #include "solver_host.hpp"
 #include "sorted_runs.hpp"
@@ -64,6 +85,8 @@ struct amg_level
     int64_t   nc = 0;       // aggregates (0 on the coarsest level)
     int32_t * agg = nullptr, *agg_ptr = nullptr, *agg_rows = nullptr;  // [n], [nc + 1], [n]; null on the coarsest level
     double *  b = nullptr, *x = nullptr, *w = nullptr;                 // into the slab; b and x null on level 0
+    spmv_mat *P = nullptr, *R = nullptr;  // smoothed aggregation: n x nc and its transpose, owned; null on the coarsest level and in a plain state
+    int       lanes_p = 1, lanes_r = 1;   // the lanes a row of P / R takes in the cycle (amg_sa_settings.hpp)
 };
 
 struct amg_state
@@ -75,6 +98,8 @@ struct amg_state
     double* slab = nullptr;  // the levels' vectors
     int64_t bytes = 0;
     int32_t mis_rounds = 0;
+    bool    smoothed = false;  // built by spmv_amg_setup_smoothed
+    double  damping  = 0.0;    // its prolong_damping
 };
 
 namespace
@@ -309,6 +334,154 @@ __global__ __launch_bounds__(kBlock) void amg_dense_apply_kernel(int n, const do
     if ((threadIdx.x & 63) == 0) x[row] = acc;
 }
 
+// ---- smoothed aggregation: set-up kernels, one lane per row -------------------------------------------------------------------------
+// count[i] = entries of row i of A^F (the diagonal entries, the neighbours, and one more where a weak entry is lumped); count[n] = 0
+__global__ __launch_bounds__(kBlock) void amg_filter_count_kernel(int64_t n, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                                  const double* __restrict__ val, const double* __restrict__ diag, double theta2,
+                                                                  int32_t* __restrict__ count)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= n; i += (int64_t)gridDim.x * kBlock)
+    {
+        int kept = 0, weak = 0;
+        if (i < n)
+        {
+            const int end = row_ptr[i + 1];
+            for (int e = row_ptr[i]; e < end; ++e)
+            {
+                const int j = col[e];
+                if (j == i || amg_neighbour<true>(i, j, val[e], diag, theta2))
+                    ++kept;
+                else
+                    weak = 1;
+            }
+        }
+        count[i] = kept + weak;
+    }
+}
+
+// row i of A^F at f_rp[i]: the kept entries in stored order, then (i, i) with the sum of the weak values from 0.0, left to right
+__global__ __launch_bounds__(kBlock) void amg_filter_fill_kernel(int64_t n, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                                 const double* __restrict__ val, const double* __restrict__ diag, double theta2,
+                                                                 const int32_t* __restrict__ f_rp, int32_t* __restrict__ f_col,
+                                                                 double* __restrict__ f_val)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    {
+        int       at   = f_rp[i];
+        bool      weak = false;
+        double    lump = 0.0;
+        const int end  = row_ptr[i + 1];
+        for (int e = row_ptr[i]; e < end; ++e)
+        {
+            const int    j = col[e];
+            const double a = val[e];
+            if (j == i || amg_neighbour<true>(i, j, a, diag, theta2))
+            {
+                f_col[at] = j;
+                f_val[at] = a;
+                ++at;
+            }
+            else
+            {
+                weak = true;
+                lump = __dadd_rn(lump, a);
+            }
+        }
+        if (weak)
+        {
+            f_col[at] = (int32_t)i;
+            f_val[at] = lump;
+        }
+    }
+}
+
+// T: row_ptr[i] = i (i <= n), col[i] = agg[i], val[i] = 1.0
+__global__ __launch_bounds__(kBlock) void amg_tentative_kernel(int64_t n, const int32_t* __restrict__ agg, int32_t* __restrict__ t_rp,
+                                                               int32_t* __restrict__ t_col, double* __restrict__ t_val)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= n; i += (int64_t)gridDim.x * kBlock)
+    {
+        t_rp[i] = (int32_t)i;
+        if (i < n)
+        {
+            t_col[i] = agg[i];
+            t_val[i] = 1.0;
+        }
+    }
+}
+
+// P[i, J] = e - (g / d_i) AT[i, J] over AT's own values; e = 1.0 where J = agg(i), else 0.0.  One product, one subtraction: no fma
+__global__ __launch_bounds__(kBlock) void amg_smooth_prolongator_kernel(int64_t n, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                                        const int32_t* __restrict__ agg, const double* __restrict__ d, double g,
+                                                                        double* __restrict__ val)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    {
+        const double  c    = g / d[i];
+        const int32_t mine = agg[i];
+        const int     end  = row_ptr[i + 1];
+        for (int e = row_ptr[i]; e < end; ++e) val[e] = __dsub_rn(col[e] == mine ? 1.0 : 0.0, __dmul_rn(c, val[e]));
+    }
+}
+
+// ---- smoothed aggregation: the cycle's two fused kernels ---------------------------------------------------------------------------
+// b_c[I] = sum_k R[I, k] (b[i_k] - w[i_k]): G lanes a row of R, lane t the entries t, t + G, .. left to right, then the fixed
+// butterfly inside the group.  The loop bound is the row's, so every lane of a group runs the same trips of the outer loop and
+// the butterfly never reads a lane outside its group; groups do not straddle a wavefront (G divides 64).
+template <int G>
+__global__ __launch_bounds__(kBlock) void amg_restrict_csr_kernel(int64_t nc, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                                  const double* __restrict__ val, const double* __restrict__ b,
+                                                                  const double* __restrict__ w, double* __restrict__ b_c)
+{
+    constexpr int RPB = kBlock / G;
+    const int     t   = threadIdx.x % G;
+    for (int64_t I = (int64_t)blockIdx.x * RPB + threadIdx.x / G; I < nc; I += (int64_t)gridDim.x * RPB)
+    {
+        double        acc = 0.0;
+        const int64_t end = row_ptr[I + 1];
+        for (int64_t k = (int64_t)row_ptr[I] + t; k < end; k += G)
+        {
+            const int i = col[k];
+            acc         = fma(val[k], b[i] - w[i], acc);
+        }
+        acc = group_sum_swizzle<G>(acc);
+        if (t == 0) b_c[I] = acc;
+    }
+}
+
+// x[i] += omega sum_J P[i, J] x_c[J], the same grouping
+template <int G>
+__global__ __launch_bounds__(kBlock) void amg_prolong_csr_kernel(int64_t n, double omega, const int32_t* __restrict__ row_ptr,
+                                                                 const int32_t* __restrict__ col, const double* __restrict__ val,
+                                                                 const double* __restrict__ x_c, double* __restrict__ x)
+{
+    constexpr int RPB = kBlock / G;
+    const int     t   = threadIdx.x % G;
+    for (int64_t i = (int64_t)blockIdx.x * RPB + threadIdx.x / G; i < n; i += (int64_t)gridDim.x * RPB)
+    {
+        double        acc = 0.0;
+        const int64_t end = row_ptr[i + 1];
+        for (int64_t k = (int64_t)row_ptr[i] + t; k < end; k += G) acc = fma(val[k], x_c[col[k]], acc);
+        acc = group_sum_swizzle<G>(acc);
+        if (t == 0) x[i] = fma(omega, acc, x[i]);
+    }
+}
+
+// one instance per group size: G = 1, 2, 4, .., 64
+#define SPMV_AMG_BY_LANES(lanes, KERNEL, grid, stream, ...)                                                                \
+    switch (lanes)                                                                                                         \
+    {                                                                                                                      \
+        case 1: hipLaunchKernelGGL(KERNEL<1>, grid, dim3(kBlock), 0, stream, __VA_ARGS__); break;                          \
+        case 2: hipLaunchKernelGGL(KERNEL<2>, grid, dim3(kBlock), 0, stream, __VA_ARGS__); break;                          \
+        case 4: hipLaunchKernelGGL(KERNEL<4>, grid, dim3(kBlock), 0, stream, __VA_ARGS__); break;                          \
+        case 8: hipLaunchKernelGGL(KERNEL<8>, grid, dim3(kBlock), 0, stream, __VA_ARGS__); break;                          \
+        case 16: hipLaunchKernelGGL(KERNEL<16>, grid, dim3(kBlock), 0, stream, __VA_ARGS__); break;                        \
+        case 32: hipLaunchKernelGGL(KERNEL<32>, grid, dim3(kBlock), 0, stream, __VA_ARGS__); break;                        \
+        default: hipLaunchKernelGGL(KERNEL<64>, grid, dim3(kBlock), 0, stream, __VA_ARGS__); break;                        \
+    }
+// workgroups of a grid-stride kernel over `rows` rows, `lanes` lanes each
+inline dim3 group_grid(int64_t rows, int lanes) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, ceil_div(rows, kBlock / lanes)))); }
+
 // ---- host helpers ----------------------------------------------------------------------------------------------------------------
 void free_state(amg_state* st)
 {
@@ -319,6 +492,8 @@ void free_state(amg_state* st)
         for (void* p : {(void*)L.agg, (void*)L.agg_ptr, (void*)L.agg_rows})
             if (p) (void)hipFree(p);
         if (l > 0 && L.A) mat_free(L.A);
+        if (L.P) mat_free(L.P);
+        if (L.R) mat_free(L.R);
     }
     if (st->inv) (void)hipFree(st->inv);
     if (st->slab) (void)hipFree(st->slab);
@@ -476,6 +651,129 @@ int coarse_operator(spmv_ctx* ctx, const spmv_mat* A, const int32_t* agg, int64_
     return SPMV_OK;
 }
 
+// a transient handle of a set-up step: freed when the step returns however it returns
+struct mat_holder
+{
+    spmv_mat* m = nullptr;
+    mat_holder() = default;
+    mat_holder(const mat_holder&)            = delete;
+    mat_holder& operator=(const mat_holder&) = delete;
+    ~mat_holder() { reset(); }
+    void reset()
+    {
+        if (m) mat_free(m);
+        m = nullptr;
+    }
+    spmv_mat* release()
+    {
+        spmv_mat* p = m;
+        m           = nullptr;
+        return p;
+    }
+};
+
+// A^F of a level under theta > 0, as a CSR handle of its own (not analysed: only spgemm and the set-up kernels read it)
+int filtered_operator(spmv_ctx* ctx, const spmv_mat* A, double theta, int level, const char* who, spmv_mat** out)
+{
+    const int64_t n = A->nrow;
+    hipStream_t   s = ctx->stream;
+    const double  theta2 = theta * theta;
+    device_pool   pool(ctx, who);
+    double*       diag;
+    int32_t *     count, *f_rp, *zeros;
+    SPMV_TRY(pool.get(diag, (size_t)n));
+    SPMV_TRY(pool.get(count, (size_t)n + 1));
+    SPMV_TRY(pool.get(f_rp, (size_t)n + 1));
+    SPMV_TRY(pool.get(zeros, 1));
+    SPMV_TRY(hip_step(hipMemsetAsync(zeros, 0, sizeof(int32_t), s), who, "clearing the counter"));
+    hipLaunchKernelGGL(amg_diag_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, A->a, A->b, A->v, diag, zeros);  // (aggregate() saw no zero)
+    hipLaunchKernelGGL(amg_filter_count_kernel, dim3(stream_grid(n + 1)), dim3(kBlock), 0, s, n, A->a, A->b, A->v, (const double*)diag, theta2, count);
+    SPMV_TRY(hip_step(hipGetLastError(), who, "the filter's counting launch"));
+    SPMV_TRY(exclusive_scan_i32(ctx, count, f_rp, n + 1));
+    int32_t entries = 0;
+    SPMV_TRY(read_scalars(ctx, &entries, f_rp + n, sizeof(entries), who));
+    SPMV_REQUIRE(entries >= 0 && entries <= A->nnz + n, "%s: the filtered operator of level %d counts %d entries", who, level, entries);
+    spmv_mat* F = nullptr;
+    SPMV_TRY(mat_alloc(ctx, SPMV_FMT_CSR, (int32_t)n, (int32_t)n, entries, 0, (size_t)n + 1, (size_t)entries, (size_t)entries, &F));
+    int rc = hip_step(hipMemcpyAsync(const_cast<int32_t*>(F->a), f_rp, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToDevice, s), who,
+                      "copying the filtered row offsets");
+    if (rc == SPMV_OK)
+    {
+        hipLaunchKernelGGL(amg_filter_fill_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, A->a, A->b, A->v, (const double*)diag, theta2, F->a,
+                           const_cast<int32_t*>(F->b), const_cast<double*>(F->v));
+        rc = hip_step(hipGetLastError(), who, "the filter's filling launch");
+    }
+    if (rc == SPMV_OK) rc = hip_step(hipStreamSynchronize(s), who, "waiting for the filtered operator");
+    if (rc != SPMV_OK)
+    {
+        mat_free(F);
+        return rc;
+    }
+    *out = F;
+    return SPMV_OK;
+}
+
+// One level of smoothed aggregation: P, R = P^T and A_c = R A P (`level`: the level of A).  The transients - A^F, T, A P - are gone
+// when it returns; the set-up's own handles run the row-parallel kernel and take no trial: only A_c selects (or takes level_kernel)
+int smoothed_level(spmv_ctx* ctx, const spmv_mat* A, const int32_t* agg, int64_t nc, double theta, double damping, int32_t level_kernel, int level,
+                   spmv_mat** P_out, spmv_mat** R_out, spmv_mat** C_out)
+{
+#pragma clang fp contract(off)
+    const char* const who = "spmv_amg_setup_smoothed";
+    const int64_t     n   = A->nrow;
+    hipStream_t       s   = ctx->stream;
+    mat_holder        F, T, P, R, AP, C;
+    const spmv_mat*   AF = A;
+    if (theta > 0.0)
+    {
+        SPMV_TRY(filtered_operator(ctx, A, theta, level, who, &F.m));
+        AF = F.m;
+    }
+    device_pool pool(ctx, who);
+    double *    d, *sv;
+    int32_t*    zeros;
+    SPMV_TRY(pool.get(d, (size_t)n));
+    SPMV_TRY(pool.get(sv, (size_t)n));
+    SPMV_TRY(pool.get(zeros, 1));
+    SPMV_TRY(hip_step(hipMemsetAsync(zeros, 0, sizeof(int32_t), s), who, "clearing the counter"));
+    hipLaunchKernelGGL(amg_diag_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, AF->a, AF->b, AF->v, d, zeros);
+    SPMV_TRY(hip_step(hipGetLastError(), who, "the filtered diagonal's launch"));
+    int32_t nzero = 0;
+    SPMV_TRY(read_scalars(ctx, &nzero, zeros, sizeof(nzero), who));
+    SPMV_REQUIRE(nzero == 0, "%s: the filtered operator of level %d has %d rows with a zero diagonal (the weak entries cancel it)", who, level, nzero);
+    SPMV_TRY(jacobi_inverse_diagonal(ctx, AF, sv, who, "the prolongator's Jacobi scaling"));
+    double lam = 0.0;
+    SPMV_TRY(cheby_row_bound(ctx, AF, sv, &lam));
+    SPMV_REQUIRE(std::isfinite(lam) && lam > 0.0, "%s: the row bound of level %d is %g: the operator is zero or not finite", who, level, lam);
+    const double g = damping / lam;
+    // T
+    SPMV_TRY(mat_alloc(ctx, SPMV_FMT_CSR, (int32_t)n, (int32_t)nc, n, 0, (size_t)n + 1, (size_t)n, (size_t)n, &T.m));
+    hipLaunchKernelGGL(amg_tentative_kernel, dim3(stream_grid(n + 1)), dim3(kBlock), 0, s, n, agg, const_cast<int32_t*>(T.m->a),
+                       const_cast<int32_t*>(T.m->b), const_cast<double*>(T.m->v));
+    SPMV_TRY(hip_step(hipGetLastError(), who, "the tentative prolongator's launch"));
+    // P over the arrays of A^F T
+    SPMV_TRY(spgemm(ctx, AF, T.m, SPMV_SPGEMM_AUTO, &P.m, SPMV_CSR_VECTOR));
+    hipLaunchKernelGGL(amg_smooth_prolongator_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, P.m->a, P.m->b, agg, (const double*)d, g,
+                       const_cast<double*>(P.m->v));
+    SPMV_TRY(hip_step(hipGetLastError(), who, "the prolongator's launch"));
+    SPMV_TRY(hip_step(hipStreamSynchronize(s), who, "waiting for the prolongator"));
+    T.reset();
+    F.reset();
+    SPMV_TRY(csr_transpose(ctx, P.m, &R.m, SPMV_CSR_VECTOR));
+    SPMV_TRY(spgemm(ctx, A, P.m, SPMV_SPGEMM_AUTO, &AP.m, SPMV_CSR_VECTOR));
+    SPMV_TRY(spgemm(ctx, R.m, AP.m, SPMV_SPGEMM_AUTO, &C.m, level_kernel));
+    AP.reset();
+    if (C.m->kernel_forced && C.m->kernel == SPMV_CSR_LDSWIN && !csr_ldswin_fits(C.m))
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED,
+                  "%s: amg_level_kernel=%d (the LDS-window kernel) cannot run the operator of level %d (%lld rows): its widest block window is %d "
+                  "columns, the tile holds %d",
+                  who, level_kernel, level + 1, (long long)nc, C.m->win_max_span, csr_ldswin_capacity());
+    *P_out = P.release();
+    *R_out = R.release();
+    *C_out = C.release();
+    return SPMV_OK;
+}
+
 // the inverse of the coarsest operator (n <= 1024): LU with partial pivoting on the host, in double
 int dense_inverse(spmv_ctx* ctx, const spmv_mat* A, double** inv_out)
 {
@@ -576,6 +874,17 @@ int amg_check_setup(const spmv_mat* m, int max_levels, int coarse_max, int smoot
     return amg_check_handle(m, who);
 }
 
+int amg_check_setup_smoothed(const spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection,
+                             double prolong_damping, const char* who)
+{
+    // (the words of amg_check_setup but for the two defaults that differ)
+    SPMV_REQUIRE(overcorrection == 0.0 || (overcorrection > 0.0 && overcorrection < 2.0), "%s: overcorrection=%g, must be inside (0, 2) (0: 1)", who,
+                 overcorrection);
+    SPMV_REQUIRE(prolong_damping == 0.0 || (prolong_damping > 0.0 && prolong_damping < 2.0), "%s: prolong_damping=%g, must be inside (0, 2) (0: 4/3)",
+                 who, prolong_damping);
+    return amg_check_setup(m, max_levels, coarse_max, smooth_degree, strength, overcorrection, who);
+}
+
 // ---- the state in the handle -----------------------------------------------------------------------------------------------------
 void amg_free(spmv_mat* m)
 {
@@ -585,17 +894,21 @@ void amg_free(spmv_mat* m)
     m->amg = nullptr;
 }
 
-int amg_setup(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection)
+// the set-up behind both entries (the arguments are checked); smoothed: P, R and A_c = R A P per level in place of the member lists
+// and the sums over aggregates
+static int amg_build(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double omega, bool smoothed,
+                     double damping)
 {
-    const char* const who = "spmv_amg_setup";
-    SPMV_TRY(amg_check_setup(m, max_levels, coarse_max, smooth_degree, strength, overcorrection, who));
+    const char* const who = smoothed ? "spmv_amg_setup_smoothed" : "spmv_amg_setup";
     auto deleter = [](amg_state* p) { free_state(p); };
     std::unique_ptr<amg_state, decltype(deleter)> st(new amg_state(), deleter);
     st->max_levels = max_levels ? max_levels : 16;
     st->coarse_max = coarse_max ? coarse_max : 256;
     st->degree     = smooth_degree ? smooth_degree : 2;
     st->strength   = strength > 0.0 ? strength : 0.0;
-    st->omega      = overcorrection != 0.0 ? overcorrection : 1.5;
+    st->omega      = omega;
+    st->smoothed   = smoothed;
+    st->damping    = damping;
     st->lv.emplace_back();
     st->lv[0].A   = m;
     st->lv[0].n   = m->nrow;
@@ -618,6 +931,8 @@ int amg_setup(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int sm
                 (void)hipFree(count);
                 break;
             }
+            spmv_mat* C = nullptr;
+            if (!smoothed)
             {
                 amg_level& L = st->lv[(size_t)l];
                 L.agg        = agg;
@@ -627,9 +942,21 @@ int amg_setup(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int sm
                 (void)hipFree(count);
                 SPMV_TRY(rc);
                 st->bytes += (int64_t)sizeof(int32_t) * (2 * n + nc + 1);
+                SPMV_TRY(coarse_operator(ctx, st->lv[(size_t)l].A, agg, nc, m->amg_level_kernel, l + 1, &C));
             }
-            spmv_mat* C = nullptr;
-            SPMV_TRY(coarse_operator(ctx, st->lv[(size_t)l].A, agg, nc, m->amg_level_kernel, l + 1, &C));
+            else  // (no member lists: the restriction runs over R)
+            {
+                amg_level& L = st->lv[(size_t)l];
+                L.agg        = agg;
+                L.nc         = nc;
+                (void)hipStreamSynchronize(ctx->stream);
+                (void)hipFree(count);
+                st->bytes += (int64_t)sizeof(int32_t) * n;
+                SPMV_TRY(smoothed_level(ctx, L.A, agg, nc, st->strength, damping, m->amg_level_kernel, l, &L.P, &L.R, &C));
+                L.lanes_p = amg_sa_group_lanes(L.P->nnz, L.P->nrow);
+                L.lanes_r = amg_sa_group_lanes(L.R->nnz, L.R->nrow);
+                st->bytes += L.P->device_bytes + L.R->device_bytes;
+            }
             st->lv.emplace_back();
             amg_level& N = st->lv.back();
             N.A          = C;
@@ -678,6 +1005,20 @@ int amg_setup(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int sm
     return SPMV_OK;
 }
 
+int amg_setup(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection)
+{
+    SPMV_TRY(amg_check_setup(m, max_levels, coarse_max, smooth_degree, strength, overcorrection, "spmv_amg_setup"));
+    return amg_build(ctx, m, max_levels, coarse_max, smooth_degree, strength, overcorrection != 0.0 ? overcorrection : 1.5, false, 0.0);
+}
+
+int amg_setup_smoothed(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection,
+                       double prolong_damping)
+{
+    SPMV_TRY(amg_check_setup_smoothed(m, max_levels, coarse_max, smooth_degree, strength, overcorrection, prolong_damping, "spmv_amg_setup_smoothed"));
+    return amg_build(ctx, m, max_levels, coarse_max, smooth_degree, strength, overcorrection != 0.0 ? overcorrection : 1.0, true,
+                     prolong_damping != 0.0 ? prolong_damping : 4.0 / 3.0);
+}
+
 int amg_info(const spmv_mat* m, int32_t* levels, int64_t* rows, int64_t* nnz)
 {
     const amg_state* st = m->amg;
@@ -709,6 +1050,78 @@ int amg_level_download(spmv_ctx* ctx, const spmv_mat* m, int level, int32_t* agg
     return hip_step(e, who, "downloading the level");
 }
 
+int amg_prolongator_download(spmv_ctx* ctx, const spmv_mat* m, int level, int64_t* nnz, int32_t* row_ptr, int32_t* col, double* val)
+{
+    const char* const who = "spmv_amg_prolongator";
+    const amg_state*  st  = m->amg;
+    if (!st) SPMV_FAIL(SPMV_ERR_INVALID, "%s: the handle was not set up (spmv_amg_setup_smoothed)", who);
+    SPMV_REQUIRE(st->smoothed, "%s: the hierarchy is plain aggregation (spmv_amg_setup): its prolongator is the aggregates of spmv_amg_level", who);
+    SPMV_REQUIRE(level >= 0 && level < (int)st->lv.size(), "%s: level=%d, the hierarchy has %d", who, level, (int)st->lv.size());
+    const amg_level& L = st->lv[(size_t)level];
+    SPMV_REQUIRE(L.P, "%s: level %d is the coarsest: it has no prolongator", who, level);
+    *nnz          = L.P->nnz;
+    hipStream_t s = ctx->stream;
+    hipError_t  e = hipSuccess;
+    if (row_ptr) e = hipMemcpyAsync(row_ptr, L.P->a, sizeof(int32_t) * ((size_t)L.n + 1), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && col && L.P->nnz) e = hipMemcpyAsync(col, L.P->b, sizeof(int32_t) * (size_t)L.P->nnz, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && val && L.P->nnz) e = hipMemcpyAsync(val, L.P->v, sizeof(double) * (size_t)L.P->nnz, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return hip_step(e, who, "downloading the prolongator");
+}
+
+// ---- one transfer of a smoothed level by itself, for measurements (spmv_amg_transfer_timed) -------------------------------------------
+int amg_check_transfer(const spmv_mat* m, int level, int what, int lanes, int64_t v_entries, const char* who)
+{
+    const amg_state* st = m->amg;
+    if (!st) SPMV_FAIL(SPMV_ERR_INVALID, "%s: the handle was not set up (spmv_amg_setup_smoothed)", who);
+    SPMV_REQUIRE(st->smoothed, "%s: the hierarchy is plain aggregation (spmv_amg_setup): it has no P and R", who);
+    SPMV_REQUIRE(level >= 0 && level + 1 < (int)st->lv.size(), "%s: level=%d, the hierarchy has %d and the coarsest has no P and R", who, level,
+                 (int)st->lv.size());
+    SPMV_REQUIRE(what >= SPMV_AMG_RESTRICT_FUSED && what <= SPMV_AMG_PROLONG_UNFUSED, "%s: what=%d, must be 0 .. 3", who, what);
+    SPMV_REQUIRE(lanes == 0 || (lanes >= 1 && lanes <= kAmgSaMaxLanes && (lanes & (lanes - 1)) == 0),
+                 "%s: lanes=%d, must be 0 (the level's own) or a power of two in 1 .. 64", who, lanes);
+    SPMV_REQUIRE(v_entries == st->lv[(size_t)level].n, "%s: the vector has %lld entries, level %d has %lld rows", who, (long long)v_entries, level,
+                 (long long)st->lv[(size_t)level].n);
+    return SPMV_OK;
+}
+
+// One restriction (v is b; w and b_c are the level's own) or one prolongation (v is x; x_c is the next level's own) of `level`:
+// the cycle's fused kernel with the level's lanes or `lanes`, or the same step as a vector pass and a product through the
+// handle of R or P (t: a work vector of the level's rows).  Asynchronous.
+int amg_transfer_launch(spmv_ctx* ctx, const spmv_mat* m, int level, int what, int lanes, double* v, double* t)
+{
+    const amg_state* st = m->amg;
+    const amg_level& L  = st->lv[(size_t)level];
+    const amg_level& N  = st->lv[(size_t)level + 1];
+    hipStream_t      s  = ctx->stream;
+    apply_extra      over;
+    over.overwrite = true;
+    switch (what)
+    {
+        case SPMV_AMG_RESTRICT_FUSED:
+        {
+            const int g = lanes ? lanes : L.lanes_r;
+            SPMV_AMG_BY_LANES(g, amg_restrict_csr_kernel, group_grid(L.nc, g), s, L.nc, L.R->a, L.R->b, L.R->v, (const double*)v, (const double*)L.w, N.b);
+            break;
+        }
+        case SPMV_AMG_RESTRICT_UNFUSED:
+            SPMV_TRY(vec_axpby(ctx, 1.0, v, -1.0, L.w, t, L.n));
+            SPMV_TRY(mat_apply_ex(ctx, L.R, t, N.b, over));
+            break;
+        case SPMV_AMG_PROLONG_FUSED:
+        {
+            const int g = lanes ? lanes : L.lanes_p;
+            SPMV_AMG_BY_LANES(g, amg_prolong_csr_kernel, group_grid(L.n, g), s, L.n, st->omega, L.P->a, L.P->b, L.P->v, (const double*)N.x, v);
+            break;
+        }
+        default:
+            SPMV_TRY(mat_apply_ex(ctx, L.P, N.x, t, over));
+            SPMV_TRY(vec_axpby(ctx, st->omega, t, 1.0, v, v, L.n));
+            break;
+    }
+    return hip_step(hipGetLastError(), "spmv_amg_transfer_timed", "a launch of the transfer");
+}
+
 static int64_t amg_launches(const amg_state* st, const spmv_mat* m)
 {
     if (!st || m->nrow == 0) return 0;
@@ -738,6 +1151,15 @@ bool amg_get_param(const spmv_mat* m, const char* name, int64_t* value)
         *value = st ? st->mis_rounds : 0;
     else if (!strcmp(name, "amg_level_kernel"))
         *value = m->amg_level_kernel;
+    else if (!strcmp(name, "amg_smoothed"))
+        *value = st && st->smoothed ? 1 : 0;
+    else if (!strncmp(name, "amg_lanes_p", 11) || !strncmp(name, "amg_lanes_r", 11))  // "amg_lanes_p<level>", "amg_lanes_r<level>"
+    {
+        char*      end   = nullptr;
+        const long level = name[11] ? strtol(name + 11, &end, 10) : -1;
+        if (level < 0 || (end && *end) || !st || !st->smoothed || level + 1 >= (long)st->lv.size()) return false;
+        *value = name[10] == 'p' ? st->lv[(size_t)level].lanes_p : st->lv[(size_t)level].lanes_r;
+    }
     else
         return false;
     return true;
@@ -784,6 +1206,12 @@ int amg_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z)
         }
         SPMV_TRY(cheby_apply(ctx, L.A, b, x));
         SPMV_TRY(mat_apply_ex(ctx, L.A, x, L.w, over));
+        if (st->smoothed)
+        {
+            SPMV_AMG_BY_LANES(L.lanes_r, amg_restrict_csr_kernel, group_grid(L.nc, L.lanes_r), s, L.nc, L.R->a, L.R->b, L.R->v, b, (const double*)L.w,
+                              st->lv[l + 1].b);
+            continue;
+        }
         hipLaunchKernelGGL(amg_restrict_kernel, dim3(stream_grid(L.nc)), dim3(kBlock), 0, s, L.nc, (const int32_t*)L.agg_ptr, (const int32_t*)L.agg_rows,
                            b, (const double*)L.w, st->lv[l + 1].b);
     }
@@ -792,7 +1220,12 @@ int amg_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z)
         const amg_level& L = st->lv[l];
         const double*    b = l == 0 ? r : L.b;
         double*          x = l == 0 ? z : L.x;
-        if (wide_ok(x, L.n))
+        if (st->smoothed)
+        {
+            SPMV_AMG_BY_LANES(L.lanes_p, amg_prolong_csr_kernel, group_grid(L.n, L.lanes_p), s, L.n, st->omega, L.P->a, L.P->b, L.P->v,
+                              (const double*)st->lv[l + 1].x, x);
+        }
+        else if (wide_ok(x, L.n))
             hipLaunchKernelGGL(amg_prolong_add_kernel<true>, dim3(pair_grid(L.n)), dim3(kBlock), 0, s, L.n, st->omega, (const int32_t*)L.agg,
                                (const double*)st->lv[l + 1].x, x);
         else

@@ -413,6 +413,8 @@ int row_bound(spmv_ctx* ctx, const spmv_mat* m, const double* s, double* bound)
 }
 }  // namespace
 
+int cheby_row_bound(spmv_ctx* ctx, const spmv_mat* m, const double* s, double* bound) { return row_bound(ctx, m, s, bound); }
+
 // ---- the coefficient table: host only ------------------------------------------------------------------------------------------
 int cheby_coefficients(int degree, double lmin, double lmax, double* c0, double* c1, double* c2)
 {

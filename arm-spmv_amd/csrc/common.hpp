@@ -571,12 +571,21 @@ int  cheby_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z); 
 int  cheby_smooth(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x);  // x += M^-1 (b - A x), asynchronous
 int  cheby_lanczos(spmv_ctx* ctx, const spmv_mat* A, int scaled, int steps, uint64_t seed, double* ritz_min, double* ritz_max, double* alpha,
                    double* beta, int32_t* steps_done);  // synchronous; alpha, beta: host arrays of `steps` entries or null
+int  cheby_row_bound(spmv_ctx* ctx, const spmv_mat* m, const double* s, double* bound);  // max_i |s_i| sum_j |a_ij| of a CSR handle's arrays (s null: 1); synchronous
 bool cheby_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "cheby_*"; false: not one of them
 bool cheby_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "cheby_*"; false: not one of them
 // amg.hip: aggregation AMG, one V(1,1) cycle z = B r (SPMV_PRECOND_AMG)
 int  amg_check_handle(const spmv_mat* m, const char* who);  // on the host: UNSUPPORTED (not CSR) / INVALID (a shard, not square, arrays released)
 int  amg_check_setup(const spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection, const char* who);
 int  amg_setup(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection);  // synchronous; 0: the default
+// smoothed aggregation: the prolongators P = (I - g D^-1 A^F) T and R = P^T as CSR handles of every level, A_c = R A P by spgemm
+int  amg_check_setup_smoothed(const spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection,
+                              double prolong_damping, const char* who);
+int  amg_setup_smoothed(spmv_ctx* ctx, spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection,
+                        double prolong_damping);  // synchronous; 0: the default
+int  amg_check_transfer(const spmv_mat* m, int level, int what, int lanes, int64_t v_entries, const char* who);  // on the host
+int  amg_transfer_launch(spmv_ctx* ctx, const spmv_mat* m, int level, int what, int lanes, double* v, double* t);  // one restriction / prolongation by itself; asynchronous
+int  amg_prolongator_download(spmv_ctx* ctx, const spmv_mat* m, int level, int64_t* nnz, int32_t* row_ptr, int32_t* col, double* val);
 void amg_free(spmv_mat* m);
 int  amg_info(const spmv_mat* m, int32_t* levels, int64_t* rows, int64_t* nnz);
 int  amg_level_download(spmv_ctx* ctx, const spmv_mat* m, int level, int32_t* agg_host, int32_t* row_ptr, int32_t* col, double* val);
@@ -586,8 +595,9 @@ bool amg_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "
 // spgemm.hip: C = A B and A^T as CSR handles of their own
 int  spgemm_check(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, const char* who);  // on the host: every refusal made before the device is touched
 int  csr_transpose_check(const spmv_ctx* ctx, const spmv_mat* A, const char* who);                              // likewise
-int  spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, spmv_mat** out);               // synchronous
-int  csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out);                                           // synchronous
+// (force_kernel != 0: the product's handle runs that CSR kernel id instead of selecting one, for a caller that builds it for itself)
+int  spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, spmv_mat** out, int32_t force_kernel = 0);  // synchronous
+int  csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out, int32_t force_kernel = 0);                              // synchronous
 bool spgemm_get_param(const spmv_mat* m, const char* name, int64_t* value);  // "spgemm_*"; false: not one of them
 // convert_sort.hip
 int sort_ids_by_key(spmv_ctx* ctx, const int32_t* keys, int64_t n, int bits, int32_t* out_ids);

@@ -339,7 +339,7 @@ bool spgemm_get_param(const spmv_mat* m, const char* name, int64_t* value)
 }
 
 // ---- C = A B; synchronous ----------------------------------------------------------------------------------------------------------
-int spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, spmv_mat** out)
+int spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, spmv_mat** out, int32_t force_kernel)
 {
     const char* const who = "spmv_spgemm";
     SPMV_TRY(spgemm_check(ctx, A, B, method, who));
@@ -400,6 +400,11 @@ int spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, 
     }
     if (rc == SPMV_OK) rc = hip_step(hipStreamSynchronize(s), who, "waiting for the product");
     C->pb_trial = A->pb_trial;               // ("panel_trial" of the source handle holds for what is built from it)
+    if (force_kernel != SPMV_CSR_AUTO)       // (a caller that builds the handle for itself: amg.hip)
+    {
+        C->kernel_forced = true;
+        C->kernel        = force_kernel;
+    }
     if (rc == SPMV_OK) rc = csr_analyse(C);  // the engine's usual selection
     if (rc != SPMV_OK)
     {
@@ -416,7 +421,7 @@ int spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, 
 }
 
 // ---- A^T as a CSR handle of its own; synchronous -------------------------------------------------------------------------------------
-int csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out)
+int csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out, int32_t force_kernel)
 {
     const char* const who = "spmv_csr_transpose";
     SPMV_TRY(csr_transpose_check(ctx, A, who));
@@ -434,6 +439,6 @@ int csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out)
     coo.a      = A->b;
     coo.b      = row;
     coo.v      = A->v;
-    return coo_to_csr(ctx, &coo, out);
+    return coo_to_csr(ctx, &coo, out, force_kernel);
 }
 }  // namespace spmv

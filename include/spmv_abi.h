@@ -775,7 +775,7 @@ int spmv_chebyshev(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x);
  *   SPMV_ERR_INVALID) and the operator of `level` as CSR (NULLs, or arrays of rows + 1, entries, entries).
  * spmv_amg_solve, spmv_amg_level and spmv_amg_info on a handle that was not set up: SPMV_ERR_INVALID.
  * spmv_mat_get_param: "amg_ready", "amg_levels", "amg_bytes" (counted in device_bytes), "amg_launches" (per application: 4 d + 7 a
- *   level and 1 or 2 d + 1 at the coarsest), "amg_mis_rounds" (summed over the levels).  spmv_mat_set_param "amg_level_kernel": a CSR
+ *   level and 1 or 2 d + 1 at the coarsest), "amg_mis_rounds" (summed over the levels), "amg_smoothed" (below).  spmv_mat_set_param "amg_level_kernel": a CSR
  *   kernel id forced on every coarse handle of the next set-up (0, the default: each selects its own).  A forced id that a coarse
  *   operator cannot run - the LDS-window kernel where a block of 256 rows spans more columns than its tile holds - fails the set-up
  *   with SPMV_ERR_UNSUPPORTED (the message names the level, the id, the window and the capacity), leaving the earlier state.  The
@@ -791,6 +791,59 @@ int spmv_amg_info(const spmv_mat* A, int32_t* levels, int64_t* rows /* levels, o
 int spmv_amg_level(spmv_ctx* ctx, const spmv_mat* A, int32_t level, int32_t* agg_host /* rows[level], or NULL */, int32_t* row_ptr,
                    int32_t* col, double* val /* the operator of `level`, or NULLs */);
 int spmv_amg_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z);
+
+/* ---- smoothed aggregation (amg.hip) -------------------------------------------------------------------------------------
+ * spmv_amg_setup_smoothed builds the hierarchy of spmv_amg_setup with smoothed prolongators: the same rules, refusals, stop rules,
+ *   aggregates and "a failed set-up leaves the earlier state"; an argument of 0 takes its default, which here is 1.0 for
+ *   overcorrection (inside (0, 2)) and 4/3 for prolong_damping (inside (0, 2); NaN or outside: SPMV_ERR_INVALID on the host, before
+ *   any device use).  It replaces whatever AMG state the handle holds; a later spmv_amg_setup replaces it with a plain one.
+ *   The method, on level l with agg and the strength mask of spmv_amg_setup:
+ *     A^F  theta <= 0: the level's own arrays.  theta > 0: row i holds, in stored order, every stored diagonal entry and every entry
+ *          the mask calls a neighbour; a row with at least one weak off-diagonal entry ends on one more entry (i, i), the sum of its
+ *          weak values from 0.0, left to right.
+ *     d_i  the sum of the diagonal entries of row i of A^F in stored order; a zero d_i: SPMV_ERR_INVALID, the message names the level.
+ *     lam  max_i |1 / d_i| sum_j |A^F_ij| over every stored entry (the row bound of spmv_chebyshev_setup; for theta <= 0 the lmax
+ *          of the level's smoother).
+ *     T    n x nc, one entry 1.0 at (i, agg(i)).
+ *     P    AT = spmv_spgemm(A^F, T) (every row i holds column agg(i): the diagonal is stored); g = prolong_damping / lam on the host;
+ *          c_i = g / d_i; P[i, J] = e - c_i AT[i, J] with e = 1.0 where J = agg(i) and 0.0 elsewhere: the product rounded once,
+ *          then a plain subtraction, no fma.  P has AT's pattern (ascending columns; an entry that comes out 0.0 stays).
+ *     R    spmv_csr_transpose(P);  A_{l+1} = spmv_spgemm(R, spmv_spgemm(A_l, P)) with the full A_l, selected or forced
+ *          ("amg_level_kernel", the refused LDS window included) as the coarse operators of spmv_amg_setup are.
+ *   spmv_spgemm defines every sum and the row bound is a maximum: the hierarchy is defined bit for bit.  The cycle is that of
+ *   spmv_amg_setup with b_{l+1} = R (b_l - A_l x_l) and x_l += omega P x_{l+1}, each one launch (a group of 2^k lanes a row, the
+ *   entries of a lane left to right, a fixed tree: no atomics, equal bits from call to call): "amg_launches" keeps its formula.  R
+ *   is P^T exactly, so B stays symmetric positive definite for such an A.  P and R persist per level; T, A^F and A P are freed
+ *   before the next level is built.  spmv_amg_solve and SPMV_PRECOND_AMG apply the state as it stands; spmv_amg_info and
+ *   spmv_amg_level work unchanged (aggregates on every level but the coarsest).  Measured: about a third to half
+ *   the iterations of the plain hierarchy on large Laplacians at the same cost of a cycle and 2 - 3 times the set-up and the
+ *   state; on a large convection-dominated (first-order upwind) system the smoothed cycle did not converge where the plain one
+ *   does - R = P^T smooths the restriction with A, not A^T - so spmv_amg_setup stays the one for those.
+ * spmv_amg_prolongator: to the host, the entries of P of `level` in *nnz and, where the pointers are not NULL, P as CSR (arrays of
+ *   rows[level] + 1, *nnz, *nnz: ask for nnz alone first).  A plain state, the coarsest level, a handle that was not set up:
+ *   SPMV_ERR_INVALID.
+ * spmv_mat_get_param: "amg_smoothed" (1 under a smoothed state, else 0); "amg_bytes" counts the P and R handles of every level (and
+ *   no member lists: the restriction runs over R). */
+int spmv_amg_setup_smoothed(spmv_ctx* ctx, spmv_mat* A, int32_t max_levels, int32_t coarse_max, int32_t smooth_degree, double strength,
+                            double overcorrection, double prolong_damping);
+int spmv_amg_prolongator(spmv_ctx* ctx, const spmv_mat* A, int32_t level, int64_t* nnz, int32_t* row_ptr, int32_t* col,
+                         double* val /* P of `level`, or NULLs */);
+/* spmv_amg_transfer_timed: for measurements (tools/bench_amg.py) - one transfer of `level` of a smoothed state by itself,
+ *   `reps` times between two events, milliseconds per call.  v has rows[level] entries: the right-hand side b of a restriction (read;
+ *   w and the result are the level's own vectors) or the x of a prolongation (added into).  what: the cycle's fused kernel
+ *   (RESTRICT_FUSED, PROLONG_FUSED; lanes 0: the lanes the set-up chose, "amg_lanes_r<level>" / "amg_lanes_p<level>" of
+ *   spmv_mat_get_param, else a power of two in 1 .. 64) or the same step as a vector pass and a product through the handle of R or P
+ *   (RESTRICT_UNFUSED: t = b - w, then R t; PROLONG_UNFUSED: t = P x_c, then x += omega t).  A plain state, the coarsest level, a
+ *   vector of another length: SPMV_ERR_INVALID on the host. */
+enum
+{
+    SPMV_AMG_RESTRICT_FUSED   = 0,
+    SPMV_AMG_RESTRICT_UNFUSED = 1,
+    SPMV_AMG_PROLONG_FUSED    = 2,
+    SPMV_AMG_PROLONG_UNFUSED  = 3
+};
+int spmv_amg_transfer_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t level, int32_t what, int32_t lanes, spmv_vec* v, int32_t reps,
+                            double* ms_per_call);
 
 /* ---- sparse products on the device (spgemm.hip) ------------------------------------------------------------------------
  * spmv_spgemm: C = A B for two CSR handles of one context, A m x k and B k x n, both whole matrices (row_begin 0) that still hold
