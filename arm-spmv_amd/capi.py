@@ -107,6 +107,9 @@ SIGNATURES = {
     "spmv_cgls": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_double, C.POINTER(C.c_int32), _f64p, _f64p]),
     "spmv_bicgstab": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_gmres": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
+    "spmv_block_gram": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.c_int32, _vp, C.c_int64, _f64p]),
+    "spmv_block_combine": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.c_int32, _f64p, _vp, C.c_int64]),
+    "spmv_lobpcg": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_double, C.c_int32, _f64p, _f64p, C.POINTER(C.c_int32)]),
     "spmv_symgs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32]),
     "spmv_symgs_setup": (C.c_int, [_vp, _vp]),
     "spmv_symgs_order": (C.c_int, [_vp, _vp, _i32p]),
@@ -626,6 +629,34 @@ class Context:
         it, res = C.c_int32(0), C.c_double(0.0)
         _check(self._lib.spmv_gmres(self.h, A.h, b.h, x.h, restart, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))
         return it.value, res.value
+
+    def block_gram(self, n: int, p: int, U: "Vector", ldu: int, q: int, V: "Vector", ldv: int) -> np.ndarray:
+        """G = U^T V (p, q) of two column-major blocks (column c at c * ld, ld >= n; rows n .. ld - 1 are padding that is never
+        touched), synchronous; 1 <= p, q <= 96.  Deterministic, and exactly symmetric where U and V are the same block"""
+        G = np.zeros((max(int(p), 0), max(int(q), 0)), dtype=np.float64)
+        buf = G if G.size else np.zeros(1)
+        _check(self._lib.spmv_block_gram(self.h, n, p, U.h, ldu, q, V.h, ldv, buf.ctypes.data_as(_f64p)))
+        return G
+
+    def block_combine(self, n: int, p: int, S: "Vector", lds: int, q: int, Cm, Out: "Vector", ldo: int) -> None:
+        """Out[i, :] = S[i, :] Cm for every row of a column-major block, Cm (p, q) on the host, asynchronous; every output is
+        fma(S[i][k], Cm[k][j], .) from 0.0 in ascending k.  Out may be S itself (same start, same ld)"""
+        c = _host(Cm, np.float64)
+        if c.shape != (p, q):
+            raise ValueError(f"block_combine: Cm has shape {c.shape}, not ({p}, {q})")
+        _check(self._lib.spmv_block_combine(self.h, n, p, S.h, lds, q, c.ctypes.data_as(_f64p), Out.h, ldo))
+
+    def lobpcg(self, A: "Matrix", X: "Vector", k: int, nev: int | None = None, largest: bool = False, max_iter: int = 500, tol: float = 1e-8,
+               precond: int | None = None):
+        """the nev (default k) smallest - largest: largest - eigenvalues of a symmetric A and their vectors by LOBPCG with a block of
+        k <= 16 vectors, synchronous.  X: nrow * k entries, column-major; holds the start block (gen_vector(nrow * k)) and receives
+        the unit vectors.  precond: gmres's set (None: PRECOND_NONE), applied column by column; it must be positive definite.
+        Stops when resid_j = ||A x_j - theta_j x_j|| <= tol for the first nev columns, or after max_iter iterations (no error).
+        Returns (theta[k], resid[k], iterations)"""
+        theta, resid, it = np.zeros(max(int(k), 1)), np.zeros(max(int(k), 1)), C.c_int32(0)
+        _check(self._lib.spmv_lobpcg(self.h, A.h, k, k if nev is None else nev, 1 if largest else 0, X.h, max_iter, tol, 0 if precond is None else precond,
+                                     theta.ctypes.data_as(_f64p), resid.ctypes.data_as(_f64p), C.byref(it)))
+        return theta[:k], resid[:k], it.value
 
     def spgemm(self, A: "Matrix", B: "Matrix", method: int = 0) -> "Matrix":
         """C = A B for two CSR handles (spmv_spgemm), synchronous: a structural pattern with ascending columns, every value its

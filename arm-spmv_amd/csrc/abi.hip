@@ -384,6 +384,7 @@ int spmv_ctx_destroy(spmv_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
+    block_ops_free(ctx);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->stage_x) (void)hipFree(ctx->stage_x);
     if (ctx->stage_y) (void)hipFree(ctx->stage_y);
@@ -1384,6 +1385,45 @@ int spmv_gmres(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x,
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
     return gmres_solve(ctx, A, b->d, x->d, restart == 0 ? 30 : restart, max_iter, rel_tol, check_every, precond, iters, rel_resid);
+}
+
+// blocks: G = U^T V and Out = S C (block_ops.hip)
+int spmv_block_gram(spmv_ctx* ctx, int64_t n, int32_t p, const spmv_vec* U, int64_t ldu, int32_t q, const spmv_vec* V, int64_t ldv, double* G_host)
+{
+    SPMV_TRY(block_gram_check(ctx, n, p, U, ldu, q, V, ldv, G_host));
+    if (n > 0) SPMV_TRY(use_device(ctx));
+    return block_gram(ctx, n, p, U->d, ldu, q, V->d, ldv, G_host);
+}
+
+int spmv_block_combine(spmv_ctx* ctx, int64_t n, int32_t p, const spmv_vec* S, int64_t lds, int32_t q, const double* C_host, spmv_vec* Out, int64_t ldo)
+{
+    SPMV_TRY(block_combine_check(ctx, n, p, S, lds, q, C_host, Out, ldo));
+    if (n == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return block_combine(ctx, n, p, S->d, lds, q, C_host, Out->d, ldo);
+}
+
+// extreme eigenpairs of a symmetric matrix by LOBPCG (solver_lobpcg.hip)
+static const solver_rules kLobpcgRules = {"spmv_lobpcg", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr};
+
+int spmv_lobpcg(spmv_ctx* ctx, const spmv_mat* A, int32_t k, int32_t nev, int32_t largest, spmv_vec* X, int32_t max_iter, double tol, int32_t precond,
+                double* theta, double* resid, int32_t* iters)
+{
+    const solver_rules& S = kLobpcgRules;
+    SPMV_REQUIRE(ctx && A && X && theta && resid && iters, "%s: null argument", S.who);
+    SPMV_REQUIRE(A->nrow == A->ncol, "%s: %s is %d x %d, not square", S.who, S.matrix, A->nrow, A->ncol);
+    SPMV_REQUIRE(k >= 1 && k <= SPMV_LOBPCG_MAX_K, "%s: k = %d vectors in the block, must be 1 .. %d", S.who, k, SPMV_LOBPCG_MAX_K);
+    SPMV_REQUIRE(nev >= 1 && nev <= k, "%s: nev = %d wanted pairs, must be 1 .. k = %d", S.who, nev, k);
+    SPMV_REQUIRE(A->nrow == 0 || A->nrow >= 3 * k, "%s: the matrix has %d rows, fewer than 3 k = %d: the basis [X P W] would not fit", S.who, A->nrow, 3 * k);
+    SPMV_REQUIRE(X->n == (int64_t)A->nrow * k, "%s: X has %lld entries, nrow * k = %d * %d", S.who, (long long)X->n, A->nrow, k);
+    SPMV_REQUIRE(max_iter >= 0 && tol >= 0.0, "%s: max_iter=%d tol=%g", S.who, max_iter, tol);
+    SPMV_TRY(check_known_preconditioner(S.who, precond));
+    SPMV_TRY(check_preconditioner(S, A, precond));
+    *iters = 0;
+    for (int j = 0; j < k; ++j) theta[j] = resid[j] = 0.0;
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return lobpcg_solve(ctx, A, k, nev, largest != 0, X->d, max_iter, tol, precond, theta, resid, iters);
 }
 
 int spmv_symgs_setup(spmv_ctx* ctx, spmv_mat* A)

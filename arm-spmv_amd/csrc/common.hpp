@@ -136,6 +136,12 @@ struct spmv_ctx
     void*  arena       = nullptr;
     size_t arena_bytes = 0;
     int    arena_users = 0;  // trials holding pointers into it (it is not re-allocated while > 0)
+    // spmv_block_gram / spmv_block_combine (block_ops.hip): a ticket, the small matrix and the partial sums on the device (grown on
+    // demand), the small matrix once more in pinned host memory, and the event behind the last copy out of it; freed with the context
+    void*      block_dev       = nullptr;
+    size_t     block_dev_bytes = 0;
+    double*    block_pinned    = nullptr;
+    hipEvent_t block_ev        = nullptr;
 };
 
 namespace spmv
@@ -495,6 +501,25 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
 // (restart: 1 .. 64; precond: NONE, JACOBI, ILU0, CHEBYSHEV, AMG)
 int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int restart, int max_iter, double rel_tol, int check_every,
                 int precond, int* iters, double* rel_resid);
+// solver_lobpcg.hip: LOBPCG for the k smallest (largest) eigenpairs of a symmetric A over one forward product per active column and
+// iteration (k: 1 .. 16; precond: NONE, JACOBI, ILU0, CHEBYSHEV, AMG); X: n x k, column-major, ld = n
+int lobpcg_solve(spmv_ctx* ctx, const spmv_mat* A, int k, int nev, bool largest, double* X, int max_iter, double tol, int precond, double* theta,
+                 double* resid, int* iters);
+// block_ops.hip: G = U^T V and Out = S C for column-major blocks of up to kBlockMaxCols columns (the layout and the contracts: there)
+constexpr int kBlockMaxCols = 96;
+int    block_gram_check(const spmv_ctx* ctx, int64_t n, int p, const spmv_vec* U, int64_t ldu, int q, const spmv_vec* V, int64_t ldv, const double* G_host);
+int    block_combine_check(const spmv_ctx* ctx, int64_t n, int p, const spmv_vec* S, int64_t lds, int q, const double* C_host, const spmv_vec* Out, int64_t ldo);
+int    block_gram(spmv_ctx* ctx, int64_t n, int p, const double* U, int64_t ldu, int q, const double* V, int64_t ldv, double* G_host);      // synchronous
+int    block_combine(spmv_ctx* ctx, int64_t n, int p, const double* S, int64_t lds, int q, const double* C_host, double* Out, int64_t ldo);  // asynchronous
+size_t block_gram_part_doubles(int64_t n, int p, int q);  // the partial sums a launch on n rows stores
+size_t block_gram_part_bound(int cols);                   // at least that for every n and every p, q <= cols
+// the launches by themselves, on device memory of the caller's: G (p q doubles), part (block_gram_part_doubles), a ticket that is 0
+// and is left 0; C (p q doubles) on the device.  Out may be any block whose row i lies in S's row i (the same ld, a whole number of
+// columns apart), or lie apart from S
+int  block_gram_launch(spmv_ctx* ctx, int64_t n, int p, const double* U, int64_t ldu, int q, const double* V, int64_t ldv, double* G, double* part,
+                       uint32_t* ticket);
+int  block_combine_launch(spmv_ctx* ctx, int64_t n, int p, const double* S, int64_t lds, int q, const double* C, double* Out, int64_t ldo);
+void block_ops_free(spmv_ctx* ctx);
 // kernels_ell.hip (what a product launches: ell_settings.hpp)
 int ell_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int ell_analyse(spmv_mat* m);

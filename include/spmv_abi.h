@@ -640,6 +640,65 @@ int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec*
  *   the size in the message. */
 int spmv_gmres(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t restart, int32_t max_iter, double rel_tol,
                int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
+/* Blocks: the dense tall-skinny arithmetic of a block method (block_ops.hip).  A BLOCK is p columns of n doubles held
+ *   column-major in one spmv_vec: column c starts at entry c * ld, ld >= n, and the vector holds at least (p - 1) * ld + n entries.
+ *   Rows n .. ld - 1 of a column are padding: never read, never written.  1 <= p, q <= 96 (SPMV_BLOCK_MAX_COLS) in both calls; blocks
+ *   need only be 8-byte aligned.
+ * spmv_block_gram: G = U^T V, p x q, row-major, into host memory; one sweep over the rows, every column read once (U and V the same
+ *   block - same start, same ld, p = q - is read once altogether).  Synchronous.  Deterministic: no double is added in arrival order;
+ *   per-workgroup partial sums are added in buffer order by the workgroup that finishes last, the grid depends on n alone, and two calls
+ *   on the same data give the same bits.  With U = V the result is exactly symmetric (both triangles take the same additions; fma is
+ *   commutative in its factors).  n = 0: all zeros, nothing is launched.
+ * spmv_block_combine: Out[i, :] = S[i, :] C for every row i, C p x q row-major in host memory, Out a block of q columns.  Asynchronous
+ *   (C_host may be reused on return: it is copied to pinned memory of the context and reaches the device through the stream).
+ *   Out[i][j] starts from 0.0 and takes fma(S[i][k], C[k][j], .) for k = 0 .. p - 1 in that order: a function of the row alone.  Out may be
+ *   S itself - the same start and the same ld; a row is read completely before any of it is written - and must not overlap it otherwise.
+ * Refused on the host before any device use with SPMV_ERR_INVALID: null pointers (G_host, C_host among them), p or q outside 1 .. 96,
+ *   n < 0, an ld below n, a vector too short for its block, Out overlapping S other than exactly in place. */
+#define SPMV_BLOCK_MAX_COLS 96
+int spmv_block_gram(spmv_ctx* ctx, int64_t n, int32_t p, const spmv_vec* U, int64_t ldu, int32_t q, const spmv_vec* V, int64_t ldv,
+                    double* G_host);
+int spmv_block_combine(spmv_ctx* ctx, int64_t n, int32_t p, const spmv_vec* S, int64_t lds, int32_t q, const double* C_host, spmv_vec* Out,
+                       int64_t ldo);
+/* spmv_lobpcg: the nev smallest (largest != 0: largest) eigenvalues of a symmetric A and their vectors by LOBPCG, Knyazev's locally
+ *   optimal block preconditioned conjugate gradients, with a block of k >= nev vectors (solver_lobpcg.hip).  Synchronous.
+ *   A is any handle spmv_bicgstab takes (all five formats, square); it is meant to be symmetric and nothing checks that.
+ *   1 <= nev <= k <= 16 (SPMV_LOBPCG_MAX_K) and nrow >= 3 k.  X: nrow * k entries, column-major with ld = nrow; it holds the start
+ *   block (for example spmv_gen_vec_uniform over nrow * k entries) and receives the vectors.  precond: spmv_gmres's set with the same
+ *   refusals, applied column by column; it must be symmetric positive definite for the method to make sense.
+ *   Algorithm, with the thresholds as constants of solver_lobpcg.hip (and of its NumPy twin, tests/lobpcg_ref.py):
+ *   ORTHONORMALISE(B): G = B^T B; d = diag(G)^-1/2; d G d = L L^T; a pivot (the diagonal entry before its square root) below a
+ *   threshold is rank loss; B <- B d L^-T.  RAYLEIGH-RITZ: the symmetric problem of the Gram matrices, solved on the host by cyclic
+ *   Jacobi rotations (small_dense.hpp; no LAPACK).
+ *   Start: orthonormalise X (threshold 1e-6, kLobpcgRankPivot; rank loss: SPMV_ERR_INVALID, "start block"); AX by k forward products
+ *   through the handle's own kernel; Rayleigh-Ritz on X^T A X; X and AX rotated by its vectors.
+ *   Iteration: (1) R = AX - X diag(theta) and resid_j = ||R_j||, one fused deterministic launch; (2) the host looks: active = the
+ *   columns with resid_j > tol, every iteration anew; no active column among the first nev, or max_iter iterations run: stop;
+ *   (3) W = M^-1 R_active; W -= X (X^T W), twice; orthonormalise W (rank loss: SPMV_ERR_INVALID, and X, theta, resid hold the last
+ *   iterate); AW by one product per active column; (4) P, where it exists, is orthonormalised and AP transformed alike; rank loss
+ *   drops P for this iteration; (5) S = [X P W], AS = [AX AP AW]; GB = S^T S and GA = S^T AS (symmetrised); GB's smallest pivot below
+ *   1e-4 (kLobpcgBasisPivot) with P in use: the step is redone without P; (6) the host solves GA c = theta GB c and takes the k
+ *   lowest (largest: highest) values and their vectors C; (7) X <- S C, AX <- AS C, P <- S C0[:, active], AP <- AS C0[:, active],
+ *   C0 = C with the rows of X cleared.  GB is always computed: nothing rests on the blocks being orthonormal to rounding.
+ *   Outputs: theta[k] ascending (largest: descending); resid[j] = ||A x_j - theta_j x_j||_2 of the returned unit vectors, an absolute
+ *   number (a caller who wants a relative one divides by a norm estimate such as the Chebyshev row bound); *iters = iterations run.
+ *   max_iter = 0 returns the Rayleigh-Ritz of the start block.  Reaching max_iter unconverged is SPMV_OK: the residuals tell.  nrow = 0
+ *   (then k = nev = 1 .. 16 and an empty X): SPMV_OK, *iters = 0, nothing is launched.  A non-finite theta or residual:
+ *   SPMV_ERR_INVALID naming the quantity.
+ *   Refused before any device use with SPMV_ERR_INVALID: null pointers, nrow != ncol, k outside 1 .. 16, nev outside 1 .. k,
+ *   0 < nrow < 3 k, X with other than nrow * k entries, max_iter < 0, tol < 0 or NaN, an unknown precond, Jacobi on a CSR handle
+ *   without its arrays; SPMV_PRECOND_SYMGS and Jacobi on a non-CSR handle: SPMV_ERR_UNSUPPORTED.
+ *   The handle's kernel, copies, plan and device_bytes stay as they were (a preconditioner that is set up on first use stays in the
+ *   handle, as in the other solvers).  Deterministic: every sum over the rows is a fixed chain per workgroup and the workgroups' sums
+ *   are added in buffer order; a solve is exactly as reproducible as the product its handle runs.
+ *   Device memory: seven blocks of nrow x k doubles (S = [X P W] and AS = [AX AP AW] of 3 k columns each, R of k; a column a padded
+ *   vector apart), nrow more for Jacobi, and the partial sums (512 x 9 k^2 doubles: 2.4 MB at k = 8), for the duration of the call, released on every path.  Per iteration
+ *   with a active columns and P in use: a preconditioner applications and a products, 1 residual launch, 6 Gram launches (X^T W
+ *   twice, W^T W, P^T P, S^T S, S^T AS) and 7 combine launches (W twice, W, P, AP, S, AS); the host looks six times (the residual
+ *   norms and five Gram results: S^T S and S^T AS are read together). */
+#define SPMV_LOBPCG_MAX_K 16
+int spmv_lobpcg(spmv_ctx* ctx, const spmv_mat* A, int32_t k, int32_t nev, int32_t largest, spmv_vec* X, int32_t max_iter, double tol,
+                int32_t precond, double* theta, double* resid, int32_t* iters);
 /* spmv_symgs: `sweeps` symmetric Gauss-Seidel sweeps on A*x = b, x updated in place: forward over the rows in sweep
  *   order with the newest x, then backward — the sweep the reference's `diagonal // for SymGS` fields were reserved
  *   for (include/matrix.h:36,81) and that it never wrote.  A: CSR handle holding the whole square matrix with a non-zero
