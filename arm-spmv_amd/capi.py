@@ -132,6 +132,14 @@ SIGNATURES = {
     "spmv_amg_transfer_timed": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _f64p]),
     "spmv_spgemm": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.POINTER(_vp)]),
     "spmv_csr_transpose": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "spmv_perm_create": (C.c_int, [_vp, C.c_int64, _i32p, C.POINTER(_vp)]),
+    "spmv_perm_rcm": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "spmv_perm_download": (C.c_int, [_vp, _i32p, _i32p]),
+    "spmv_perm_info": (C.c_int, [_vp, C.c_char_p, _i64p]),
+    "spmv_perm_destroy": (C.c_int, [_vp]),
+    "spmv_csr_permute": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "spmv_vec_permute": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp]),
+    "spmv_csr_bandwidth": (C.c_int, [_vp, _vp, _i64p, _i64p]),
     "spmv_coo_to_csr": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_coo_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_csr_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -671,6 +679,39 @@ class Context:
         _check(self._lib.spmv_csr_transpose(self.h, A.h, C.byref(h)))
         return Matrix(self, h)
 
+    # ---- reordering
+    def perm(self, order) -> "Perm":
+        """the permutation order[k] = the old index that takes new position k (spmv_perm_create): uploaded, checked and inverted on
+        the device; anything that is not a permutation of 0 .. n-1 raises, naming the smallest offending position"""
+        o = _host(order, np.int32)
+        h = _vp()
+        _check(self._lib.spmv_perm_create(self.h, o.size, o.ctypes.data_as(_i32p) if o.size else None, C.byref(h)))
+        return Perm(self, h, o.size)
+
+    def perm_rcm(self, A: "Matrix") -> "Perm":
+        """the reverse Cuthill-McKee ordering of a square CSR handle's graph (the pattern of A + A^T), computed on the device
+        (spmv_perm_rcm), synchronous; a fixed permutation: every run returns the same integers"""
+        h = _vp()
+        _check(self._lib.spmv_perm_rcm(self.h, A.h, C.byref(h)))
+        return Perm(self, h, A.info.nrow)
+
+    def csr_permute(self, A: "Matrix", rows: "Perm | None" = None, cols: "Perm | None" = None) -> "Matrix":
+        """B[k][l] = A[rows.order[k]][cols.order[l]] as a CSR handle of its own (spmv_csr_permute), synchronous: ascending columns
+        inside a row, duplicates kept in stored order, values bit for bit; None is the identity"""
+        h = _vp()
+        _check(self._lib.spmv_csr_permute(self.h, A.h, rows.h if rows is not None else None, cols.h if cols is not None else None, C.byref(h)))
+        return Matrix(self, h)
+
+    def vec_permute(self, p: "Perm", src: "Vector", dst: "Vector", back: bool = False) -> None:
+        """dst[k] = src[order[k]] (back: dst[order[k]] = src[k]) in one launch, asynchronous; src and dst must not overlap"""
+        _check(self._lib.spmv_vec_permute(self.h, p.h, 1 if back else 0, src.h, dst.h))
+
+    def csr_bandwidth(self, A: "Matrix") -> tuple[int, int]:
+        """(bandwidth, profile) of a CSR handle: max |i - j| over its entries, and the sum over its non-empty rows of max(0, i - min j)"""
+        b, q = C.c_int64(0), C.c_int64(0)
+        _check(self._lib.spmv_csr_bandwidth(self.h, A.h, C.byref(b), C.byref(q)))
+        return b.value, q.value
+
     def coo_to_csr(self, coo: "Matrix") -> "Matrix":
         h = _vp()
         _check(self._lib.spmv_coo_to_csr(self.h, coo.h, C.byref(h)))
@@ -723,6 +764,35 @@ class Comm:
             raise ValueError(f"Comm.allgather: {n} participants need {n} vectors and {n + 1} offsets, got {len(vecs)} and {off.size}")
         arr = (_vp * n)(*[v.h for v in vecs])
         _check(self._lib.spmv_comm_allgather(self.h, arr, off.ctypes.data_as(_i64p)))
+
+
+class Perm:
+    """a permutation on the device (spmv_perm): order[k] is the old index that takes new position k, inverse[order[k]] = k"""
+
+    def __init__(self, ctx: Context, h, n: int):
+        self.ctx, self.h, self.n = ctx, h, n
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.ctx._lib.spmv_perm_destroy(self.h)
+        except Exception:
+            pass
+        self.h = None
+
+    def download(self) -> tuple[np.ndarray, np.ndarray]:
+        """(order, inverse) on the host"""
+        o, i = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.int32)
+        if self.n:
+            _check(self.ctx._lib.spmv_perm_download(self.h, o.ctypes.data_as(_i32p), i.ctypes.data_as(_i32p)))
+        return o, i
+
+    def info(self, name: str) -> int:
+        """one counter by name (spmv_perm_info): "n", and what perm_rcm did - "rcm_isolated", "rcm_components", "rcm_levels", "rcm_bfs",
+        "rcm_launches", "rcm_transient_bytes" (0 for a permutation made by perm)"""
+        v = C.c_int64(0)
+        _check(self.ctx._lib.spmv_perm_info(self.h, name.encode(), C.byref(v)))
+        return v.value
 
 
 class Vector:

@@ -939,6 +939,58 @@ enum
 int spmv_spgemm(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, spmv_mat** out_C);
 int spmv_csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out_At);
 
+/* ---- reordering (reorder.hip) ------------------------------------------------------------------------------------------
+ * A permutation is an object of a context: n, and order and inverse on the device (8 n bytes).  The convention is that of
+ *   spmv_symgs_order: order[k] is the old index that takes new position k, and inverse[order[k]] = k.
+ * spmv_perm_create: uploads order_host[n] and builds the inverse on the device.  Synchronous.  Anything that is not a permutation of
+ *   0 .. n-1 is refused with SPMV_ERR_INVALID; the message names the smallest position k whose value is out of range or stands at an
+ *   earlier position already.  n = 0 is valid (order_host may be NULL) and touches no device.
+ * spmv_perm_rcm: the reverse Cuthill-McKee ordering of a square CSR handle (the whole matrix, arrays still held), computed on the
+ *   device.  Synchronous; only order and inverse stay allocated when it returns.
+ *   Graph: vertices 0 .. n-1; i ~ j for i != j if (i, j) or (j, i) is stored - the pattern of A + A^T.  Stored zeros count, duplicates
+ *     count once, self-loops are ignored.  deg(i) is the number of distinct neighbours.
+ *   Sequence cm: (1) all vertices of degree 0, in ascending index.  (2) While unnumbered vertices remain, a root r: the unnumbered
+ *     vertex of smallest (deg, index), refined by George and Liu's rule - build the level structure of r over the unnumbered
+ *     vertices, let c be the vertex of its last level with smallest (deg, index), build c's level structure; if it has more levels
+ *     than r's, c becomes r and the rule is applied again, at most 8 times per component in all (kRcmRootRepeats of
+ *     reorder_settings.hpp).  (3) r is numbered, then level by level: the next level is the set of unnumbered neighbours of the
+ *     current one, ordered by (smallest position in cm among its neighbours in the current level, deg, index).  That is the queue
+ *     algorithm (pop v, append its unnumbered neighbours in ascending (deg, index)).
+ *   Result: order[k] = cm[n-1-k].  Every run returns the same integers; tests/rcm_ref.py is the NumPy twin.
+ *   Refused on the host: a null argument, a shard, released CSR arrays, a handle of another context, a matrix that is not square
+ *     (SPMV_ERR_INVALID); a handle that is not CSR (SPMV_ERR_UNSUPPORTED).  After counting on the device: more than 2^31 - 1 keys of
+ *     the symmetrised adjacency, two per stored off-diagonal entry, whose ids are int32 (SPMV_ERR_UNSUPPORTED).
+ * spmv_perm_download: order and / or inverse to the host (n entries each; NULL skips one).  Synchronous.
+ * spmv_perm_info: "n"; and what spmv_perm_rcm did, 0 for a permutation made by spmv_perm_create: "rcm_isolated" (vertices of degree
+ *   0), "rcm_components" (components with at least one edge), "rcm_levels" (levels of the numbering passes, the roots' included, summed
+ *   over the components), "rcm_bfs" (level structures built, root searches included), "rcm_launches" (kernel launches, scans, sorts
+ *   and device copies the call issued), "rcm_transient_bytes" (device memory the call held beside the permutation and the radix
+ *   sort's own buffers).  An unknown name: SPMV_ERR_INVALID.
+ * spmv_perm_destroy: waits for the context's stream and frees the permutation.  NULL is allowed.
+ * spmv_csr_permute: B = P_r A P_c^T, B[k][l] = A[order_r[k]][order_c[l]], as an owning CSR handle like spmv_spgemm's result: it selects
+ *   its kernel as an uploaded handle does (a plan of the context is not applied to it).  Synchronous.  Row k of B holds the entries
+ *   of row order_r[k] of A with column j renamed inverse_c[j], in ascending new column; entries of equal new column keep A's stored
+ *   order; duplicates are kept, not summed; values are copied bit for bit.  A NULL permutation is the identity (the columns of a row
+ *   are still put in ascending order).  A may be rectangular: rows->n = nrow, cols->n = ncol.  Refused on the host: what
+ *   spmv_csr_transpose refuses, a permutation of another size, a permutation of another context (SPMV_ERR_INVALID).
+ * spmv_vec_permute: back = 0: dst[k] = src[order[k]] (a vector in the old numbering becomes one in the new numbering); back = 1:
+ *   dst[order[k]] = src[k] (and back again).  One launch, asynchronous on the context's stream.  The values travel as 64-bit words:
+ *   NaN payloads and -0.0 arrive as they left.  Refused on the host: a null argument, back outside 0 .. 1, a permutation or a
+ *   vector of another context, src or dst of another length than the permutation, src and dst that overlap (SPMV_ERR_INVALID).  n = 0: nothing is
+ *   launched.
+ * spmv_csr_bandwidth: bandwidth = max |i - j| over the stored entries of a CSR handle (0 without entries), profile = the sum over the
+ *   non-empty rows of max(0, i - min j).  One reduction kernel, synchronous.  Refusals as spmv_csr_transpose.
+ * Solving in the new numbering: INTEGRATION.md ("Solving in another numbering"). */
+typedef struct spmv_perm spmv_perm;
+int spmv_perm_create(spmv_ctx* ctx, int64_t n, const int32_t* order_host, spmv_perm** out);
+int spmv_perm_rcm(spmv_ctx* ctx, const spmv_mat* A, spmv_perm** out);
+int spmv_perm_download(const spmv_perm* p, int32_t* order_host, int32_t* inverse_host);
+int spmv_perm_info(const spmv_perm* p, const char* name, int64_t* value);
+int spmv_perm_destroy(spmv_perm* p);
+int spmv_csr_permute(spmv_ctx* ctx, const spmv_mat* A, const spmv_perm* rows, const spmv_perm* cols, spmv_mat** out_B);
+int spmv_vec_permute(spmv_ctx* ctx, const spmv_perm* p, int32_t back, const spmv_vec* src, spmv_vec* dst);
+int spmv_csr_bandwidth(spmv_ctx* ctx, const spmv_mat* A, int64_t* bandwidth, int64_t* profile);
+
 /* ---- format conversion on the device (src/matrix.cpp:115-154, :450-500) -------------------------- */
 /* Both keep the COO order of the entries inside each row (stable), like the reference's backward
  * scatter, so the result is identical to the reference's arrays, not merely equivalent. */
