@@ -16,7 +16,7 @@ import numpy as np
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("SPMV_HIP_SO") or _PKG / "lib" / "libspmv_hip.so")  # override: A/B against another build
 
-FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA = 0, 1, 2, 3, 4
+FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA, FMT_BSR = 0, 1, 2, 3, 4, 5
 CSR_AUTO, CSR_VECTOR, CSR_LDSWIN, CSR_SCALAR, CSR_PANEL, CSR_TWOPHASE, CSR_SEGSCAN, CSR_SPLIT, CSR_ELL = 0, 1, 2, 3, 4, 5, 6, 7, 8
 AMG_RESTRICT_FUSED, AMG_RESTRICT_UNFUSED, AMG_PROLONG_FUSED, AMG_PROLONG_UNFUSED = 0, 1, 2, 3  # spmv_amg_transfer_timed
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0, PRECOND_CHEBYSHEV, PRECOND_AMG = 0, 1, 2, 3, 4, 5
@@ -143,6 +143,10 @@ SIGNATURES = {
     "spmv_coo_to_csr": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_coo_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_csr_to_ell": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "spmv_bsr_upload": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "spmv_bsr_wrap_device": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "spmv_csr_to_bsr": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(_vp)]),
+    "spmv_bsr_to_csr": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(_vp)]),
     "spmv_csr_split_columns": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.POINTER(_vp), C.POINTER(_vp)]),
     "spmv_partition_rows": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, _i64p, _i64p]),
     "spmv_partition_rows_balanced": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp]),
@@ -345,6 +349,13 @@ class Context:
         _check(self._lib.spmv_ell_upload(self.h, nrow, ncol, k, nnz, _ptr(c), _ptr(v), C.byref(h)))
         return Matrix(self, h)
 
+    def bsr(self, nrow, ncol, bs, brow_ptr, bcol, val) -> "Matrix":
+        """block CSR (spmv_bsr_upload): blocks of bs x bs values, row-major inside a block; nrow, ncol are scalar dimensions"""
+        rp, c, v = _host(brow_ptr, np.int32), _host(bcol, np.int32), _host(val, np.float64)
+        h = _vp()
+        _check(self._lib.spmv_bsr_upload(self.h, nrow, ncol, bs, _ptr(rp), _ptr(c), _ptr(v), C.byref(h)))
+        return Matrix(self, h)
+
     def csc(self, nrow, ncol, col_ptr, row, val) -> "Matrix":
         cp, r, v = _host(col_ptr, np.int32), _host(row, np.int32), _host(val, np.float64)
         h = _vp()
@@ -363,6 +374,13 @@ class Context:
         _check(self._lib.spmv_csr_wrap_device(self.h, nrow, ncol, _ptr(d_row_ptr), _ptr(d_col), _ptr(d_val), C.byref(h)))
         m = Matrix(self, h)
         m._keep = (d_row_ptr, d_col, d_val)
+        return m
+
+    def wrap_bsr(self, nrow, ncol, bs, d_brow_ptr, d_bcol, d_val) -> "Matrix":
+        h = _vp()
+        _check(self._lib.spmv_bsr_wrap_device(self.h, nrow, ncol, bs, _ptr(d_brow_ptr), _ptr(d_bcol), _ptr(d_val), C.byref(h)))
+        m = Matrix(self, h)
+        m._keep = (d_brow_ptr, d_bcol, d_val)
         return m
 
     def wrap_coo(self, nrow, ncol, nnz, d_row, d_col, d_val) -> "Matrix":
@@ -733,6 +751,18 @@ class Context:
         _check(self._lib.spmv_csr_to_ell(self.h, csr.h, C.byref(h)))
         return Matrix(self, h)
 
+    def csr_to_bsr(self, A: "Matrix", bs: int) -> "Matrix":
+        """the BSR handle of a CSR handle (spmv_csr_to_bsr), on the device: block columns ascending, duplicates added in stored order"""
+        h = _vp()
+        _check(self._lib.spmv_csr_to_bsr(self.h, A.h, bs, C.byref(h)))
+        return Matrix(self, h)
+
+    def bsr_to_csr(self, A: "Matrix", drop_zeros: bool = True) -> "Matrix":
+        """the CSR handle of a BSR handle (spmv_bsr_to_csr), on the device: the positions inside nrow x ncol, columns ascending"""
+        h = _vp()
+        _check(self._lib.spmv_bsr_to_csr(self.h, A.h, 1 if drop_zeros else 0, C.byref(h)))
+        return Matrix(self, h)
+
 
 class Comm:
     """exchange between several contexts of this process (spmv_comm_*): the x all-gather of the sharded drivers"""
@@ -902,6 +932,8 @@ class Matrix:
             na, nb, nv = 0, i.nrow * i.ell_k, i.nrow * i.ell_k
         elif fmt == FMT_CSC:
             na, nb, nv = i.ncol + 1, i.nnz, i.nnz
+        elif fmt == FMT_BSR:  # block row pointer, block columns, nnzb * bs * bs values (ell_k holds bs)
+            na, nb, nv = -(-i.nrow // i.ell_k) + 1, i.nnz // (i.ell_k * i.ell_k), i.nnz
         else:
             na, nb, nv = i.ell_k, 0, i.nrow * i.ell_k
         a = np.empty(na, dtype=np.int32)

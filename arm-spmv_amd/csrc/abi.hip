@@ -159,6 +159,7 @@ static int finish(spmv_mat* m, spmv_mat** out)
     if (rc == SPMV_OK && m->format == SPMV_FMT_COO) rc = coo_analyse(m);
     if (rc == SPMV_OK && m->format == SPMV_FMT_CSC) rc = csc_analyse(m);
     if (rc == SPMV_OK && m->format == SPMV_FMT_ELL) rc = ell_analyse(m);
+    if (rc == SPMV_OK && m->format == SPMV_FMT_BSR) rc = bsr_analyse(m);
     if (rc != SPMV_OK)
     {
         mat_free(m);
@@ -648,6 +649,67 @@ int spmv_dia_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int32_t ndiags, c
     return finish(m, out);
 }
 
+// ---- block CSR: k holds bs, nnz the stored values (blocks * bs * bs) ------------------------------------------------------------
+static int check_bsr_shape(const char* who, const spmv_ctx* ctx, const void* out, int32_t nrow, int32_t ncol, int32_t bs, const int32_t* brow_ptr)
+{
+    SPMV_REQUIRE(ctx && out && brow_ptr, "%s: null argument", who);
+    SPMV_REQUIRE(nrow >= 0 && ncol >= 0 && nrow <= INT32_MAX - 64 && ncol <= INT32_MAX - 64, "%s: bad size %d x %d", who, nrow, ncol);
+    return bsr_check_bs(bs, who);
+}
+
+int spmv_bsr_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int32_t bs, const int32_t* brow_ptr, const int32_t* bcol, const double* values,
+                    spmv_mat** out)
+{
+    SPMV_TRY(check_bsr_shape("spmv_bsr_upload", ctx, out, nrow, ncol, bs, brow_ptr));
+    const int64_t mb = ceil_div(nrow, bs), nnzb = (int64_t)brow_ptr[mb] - brow_ptr[0];
+    SPMV_REQUIRE(brow_ptr[0] == 0 && nnzb >= 0 && (nnzb == 0 || (bcol && values)), "spmv_bsr_upload: brow_ptr[0]=%d, %lld blocks", brow_ptr[0], (long long)nnzb);
+    SPMV_TRY(use_device(ctx));
+    plan_arm  arm(ctx);
+    spmv_mat* m = nullptr;
+    SPMV_TRY(mat_alloc(ctx, SPMV_FMT_BSR, nrow, ncol, nnzb * bs * bs, bs, (size_t)mb + 1, (size_t)nnzb, (size_t)(nnzb * bs * bs), &m));
+    SPMV_TRY(upload_arrays(m, brow_ptr, (size_t)mb + 1, bcol, (size_t)nnzb, values, (size_t)(nnzb * bs * bs)));
+    return finish(m, out);
+}
+
+int spmv_bsr_wrap_device(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int32_t bs, const int32_t* d_brow_ptr, const int32_t* d_bcol,
+                         const double* d_values, spmv_mat** out)
+{
+    SPMV_TRY(check_bsr_shape("spmv_bsr_wrap_device", ctx, out, nrow, ncol, bs, d_brow_ptr));
+    SPMV_TRY(use_device(ctx));
+    plan_arm      arm(ctx);
+    const int64_t mb      = ceil_div(nrow, bs);
+    int32_t       ends[2] = {0, 0};
+    SPMV_HIP(hipMemcpyAsync(&ends[0], d_brow_ptr, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SPMV_HIP(hipMemcpyAsync(&ends[1], d_brow_ptr + mb, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SPMV_HIP(hipStreamSynchronize(ctx->stream));
+    SPMV_REQUIRE(ends[0] == 0 && ends[1] >= 0 && (ends[1] == 0 || (d_bcol && d_values)), "spmv_bsr_wrap_device: brow_ptr[0]=%d brow_ptr[mb]=%d", ends[0], ends[1]);
+    spmv_mat* m = nullptr;
+    SPMV_TRY(wrap(ctx, SPMV_FMT_BSR, nrow, ncol, (int64_t)ends[1] * bs * bs, bs, d_brow_ptr, d_bcol, d_values, &m));
+    return finish(m, out);
+}
+
+int spmv_csr_to_bsr(spmv_ctx* ctx, const spmv_mat* csr, int32_t bs, spmv_mat** out_bsr)
+{
+    SPMV_REQUIRE(ctx && csr && out_bsr, "spmv_csr_to_bsr: null argument");
+    SPMV_TRY(csr_to_bsr_check(ctx, csr, bs, "spmv_csr_to_bsr"));
+    SPMV_TRY(use_device(ctx));
+    plan_arm  arm(ctx);
+    spmv_mat* m = nullptr;
+    SPMV_TRY(csr_to_bsr(ctx, csr, bs, &m));
+    return finish(m, out_bsr);  // validates and analyses like an uploaded handle (frees on failure)
+}
+
+int spmv_bsr_to_csr(spmv_ctx* ctx, const spmv_mat* bsr, int32_t drop_zeros, spmv_mat** out_csr)
+{
+    SPMV_REQUIRE(ctx && bsr && out_csr, "spmv_bsr_to_csr: null argument");
+    SPMV_TRY(bsr_to_csr_check(ctx, bsr, "spmv_bsr_to_csr"));
+    SPMV_TRY(use_device(ctx));
+    plan_arm  arm(ctx);
+    spmv_mat* m = nullptr;
+    SPMV_TRY(bsr_to_csr(ctx, bsr, drop_zeros, &m));
+    return finish(m, out_csr);
+}
+
 int spmv_mat_destroy(spmv_mat* m)
 {
     if (!m) return SPMV_OK;
@@ -685,6 +747,7 @@ int spmv_mat_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes_per_row)
 {
     SPMV_REQUIRE(m, "null matrix");
     SPMV_REQUIRE(kernel >= SPMV_CSR_AUTO && kernel <= SPMV_CSR_ELL, "unknown kernel id %d", kernel);
+    if (m->format == SPMV_FMT_BSR) return bsr_set_kernel(m, kernel, lanes_per_row);  // (its lanes per block row are multiples of bs * bs)
     SPMV_REQUIRE(lanes_per_row == 0 || (lanes_per_row >= 1 && lanes_per_row <= 64 &&
                                         (lanes_per_row & (lanes_per_row - 1)) == 0),
                  "lanes_per_row must be 0 or a power of two in 1..64, got %d", lanes_per_row);
@@ -1023,6 +1086,7 @@ int spmv_mat_download(const spmv_mat* m, int32_t* a, int32_t* b, double* v)
         case SPMV_FMT_ELL: nb = nv = (size_t)m->nrow * (size_t)m->k; break;
         case SPMV_FMT_CSC: na = (size_t)m->ncol + 1; nb = nv = (size_t)m->nnz; break;
         case SPMV_FMT_DIA: na = (size_t)m->k; nv = (size_t)m->nrow * (size_t)m->k; break;
+        case SPMV_FMT_BSR: na = (size_t)ceil_div(m->nrow, m->k) + 1; nb = (size_t)(m->nnz / (m->k * m->k)); nv = (size_t)m->nnz; break;
         default: SPMV_FAIL(SPMV_ERR_INVALID, "unknown format %d", m->format);
     }
     SPMV_REQUIRE(!((b && nb && !m->b) || (v && nv && !m->v)), "spmv_mat_download: this handle gave up its arrays (panel_keep_csr = 0)");
@@ -1763,6 +1827,8 @@ int spmv_partition_rows_balanced(int64_t nrow, const int64_t* row_ptr64, int32_t
 int spmv_mat_partition_rows(const spmv_mat* m, int32_t nparts, int32_t balance_entries, int64_t* bounds)
 {
     SPMV_REQUIRE(m && nparts > 0 && bounds, "spmv_mat_partition_rows: bad argument");
+    if (m->format == SPMV_FMT_BSR && balance_entries)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_mat_partition_rows: a BSR handle is not sharded: no partition by entries (balance_entries = 1)");
     const int64_t n = m->format == SPMV_FMT_CSC ? m->ncol : m->nrow;
     // padded formats store the same number of slots for every row: equal rows ARE equal work
     if (!balance_entries || m->format == SPMV_FMT_ELL || m->format == SPMV_FMT_DIA || n == 0)

@@ -190,11 +190,11 @@ struct spmv_mat
     int32_t   format    = 0;
     int32_t   nrow      = 0;
     int32_t   ncol      = 0;
-    int32_t   k         = 0;  // ELL slots / DIA ndiags
+    int32_t   k         = 0;  // ELL slots / DIA ndiags / BSR block size bs
     int64_t   nnz       = 0;
     int64_t   row_begin = 0;
-    // a: row_ptr | row_ind | -       | col_ptr | offsets
-    // b: col_ind | col_ind | col_ind | row_ind | -
+    // a: row_ptr | row_ind | -       | col_ptr | offsets | block row_ptr
+    // b: col_ind | col_ind | col_ind | row_ind | -       | block col_ind   (CSR | COO | ELL | CSC | DIA | BSR)
     const int32_t* a = nullptr;
     const int32_t* b = nullptr;
     const double*  v = nullptr;
@@ -367,7 +367,8 @@ struct spmv_mat
     int32_t                 ilu_order = 1;  // "ilu0_order": 1 multicolour (default), 0 the matrix's own row order
 
     // the transposed product (transpose.hip): a companion handle of A^T over A's arrays, or the DIA transposed kernel's set-up;
-    // built by spmv_mat_transpose_setup, no part of the forward state (kernel, copies, device_bytes, plan)
+    // built by spmv_mat_transpose_setup, no part of the forward state (kernel, copies, device_bytes, plan) - but for a BSR handle, whose
+    // companion owns its arrays and is counted in device_bytes
     struct spmv::transpose_state* tr            = nullptr;
     int32_t                       tr_kernel_req = SPMV_CSR_AUTO;  // "transpose_kernel": handed to spmv_mat_set_kernel on the companion
 
@@ -564,6 +565,18 @@ int vec_copy2(spmv_ctx* ctx, double* dst0, const double* src0, int64_t n0, doubl
 int vec_dot(spmv_ctx* ctx, const double* x, const double* y, int64_t n, double* result);
 int vec_axpby(spmv_ctx* ctx, double alpha, const double* x, double beta, const double* y, double* w,
               int64_t n);
+// kernels_bsr.hip: block CSR (what a product launches: bsr_settings.hpp); nnz counts stored values, nnz / bs^2 blocks
+int bsr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
+int bsr_analyse(spmv_mat* m);
+int bsr_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes);  // spmv_mat_set_kernel on a BSR handle
+int bsr_apply_plan(spmv_mat* m);
+// convert_bsr.hip: the conversions and the handle of A^T (each check on the host, before the device is touched)
+int bsr_check_bs(int32_t bs, const char* who);
+int csr_to_bsr_check(const spmv_ctx* ctx, const spmv_mat* csr, int32_t bs, const char* who);
+int bsr_to_csr_check(const spmv_ctx* ctx, const spmv_mat* bsr, const char* who);
+int csr_to_bsr(spmv_ctx* ctx, const spmv_mat* csr, int32_t bs, spmv_mat** out);             // synchronous; analysed by the caller
+int bsr_to_csr(spmv_ctx* ctx, const spmv_mat* bsr, int32_t drop_zeros, spmv_mat** out);    // synchronous; analysed by the caller
+int bsr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out);                       // synchronous; analysed
 // validate.hip
 int mat_validate(const spmv_mat* m);
 // convert.hip

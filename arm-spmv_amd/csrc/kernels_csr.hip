@@ -605,6 +605,7 @@ int mat_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, c
         case SPMV_FMT_COO: return coo_apply(ctx, A, x, y);
         case SPMV_FMT_CSC: return csc_apply(ctx, A, x, y);
         case SPMV_FMT_DIA: return dia_apply(ctx, A, x, y);
+        case SPMV_FMT_BSR: return bsr_apply(ctx, A, x, y);
         default: SPMV_FAIL(SPMV_ERR_INVALID, "unknown format %d", A->format);
     }
 }

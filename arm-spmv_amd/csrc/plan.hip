@@ -73,6 +73,7 @@ int collect(const spmv_mat* m, std::vector<plan_node>& out)
         n.ell_tiled      = own && m->ell_tval ? 1 : 0;
         if (!own) n.lanes_per_row = 0;
     }
+    if (m->format == SPMV_FMT_BSR) n.flags = 0;  // (one kernel, one node: the lanes per block row are all it reads)
     if (m->format == SPMV_FMT_COO) n.coo_bins_per_xcd = m->kernel == SPMV_CSR_PANEL ? 0 : m->cb_bins / 8;
     if (m->format == SPMV_FMT_COO || m->format == SPMV_FMT_CSC || m->format == SPMV_FMT_DIA) n.lanes_per_row = 0, n.flags = m->format == SPMV_FMT_DIA ? m->flags : 0;
     if (runs_from_rowgrouped(m)) n.child_rowgrouped = collect(m->rowgrouped, out);
@@ -99,10 +100,11 @@ int check_blob(const void* buf, int64_t len, std::vector<plan_node>* out)
     memcpy(n.data(), (const unsigned char*)buf + sizeof(plan_header), (size_t)h.nnodes * sizeof(plan_node));
     for (uint32_t i = 0; i < h.nnodes; ++i)
     {
-        SPMV_REQUIRE(n[i].format >= SPMV_FMT_COO && n[i].format <= SPMV_FMT_DIA, "plan: node %u has format %d", i, n[i].format);
+        SPMV_REQUIRE(n[i].format >= SPMV_FMT_COO && n[i].format <= SPMV_FMT_BSR, "plan: node %u has format %d", i, n[i].format);
         SPMV_REQUIRE(n[i].kernel >= SPMV_CSR_AUTO && n[i].kernel <= SPMV_CSR_ELL, "plan: node %u has kernel %d", i, n[i].kernel);
-        SPMV_REQUIRE(n[i].lanes_per_row >= 0 && n[i].lanes_per_row <= 64 && (n[i].lanes_per_row & (n[i].lanes_per_row - 1)) == 0, "plan: node %u has %d lanes per row", i,
-                     n[i].lanes_per_row);
+        // (a BSR node's lanes per block row are a multiple of bs * bs, not a power of two: bsr_apply_plan holds them against the handle's bs)
+        SPMV_REQUIRE(n[i].lanes_per_row >= 0 && n[i].lanes_per_row <= 64 && (n[i].format == SPMV_FMT_BSR || (n[i].lanes_per_row & (n[i].lanes_per_row - 1)) == 0),
+                     "plan: node %u has %d lanes per row", i, n[i].lanes_per_row);
         for (const int32_t c : {n[i].child_rowgrouped, n[i].child_long, n[i].child_ell})
             // children come after their parent (collect writes them so): no cycles
             SPMV_REQUIRE(c == -1 || (c > (int32_t)i && c < (int32_t)h.nnodes), "plan: node %u names child %d of %u nodes", i, c, h.nnodes);
@@ -147,6 +149,7 @@ int plan_apply(spmv_mat* m)
         case SPMV_FMT_COO: return coo_apply_plan(m);
         case SPMV_FMT_CSC: return csc_apply_plan(m);
         case SPMV_FMT_ELL: return ell_apply_plan(m);
+        case SPMV_FMT_BSR: return bsr_apply_plan(m);
         default: return SPMV_OK;  // DIA: one kernel, nothing to plan
     }
 }

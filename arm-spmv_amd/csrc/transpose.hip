@@ -5,7 +5,8 @@
 // arrays swapped is A^T.  So the transposed state of such a handle is an internal companion handle that borrows A's arrays
 // (owned = false: it never frees them) and picks its own kernel like any handle of its format - a CSC companion chooses between
 // the scatter and the row-grouped copy (which is the CSR of A^T, and picks panel or another CSR kernel itself), a CSR companion
-// runs all of CSR AUTO.  An ELL handle becomes a COO companion: its rows are ELL's col_ind (borrowed), its columns the row of every
+// runs all of CSR AUTO.  A BSR handle gets a BSR handle of A^T with arrays of its own (convert_bsr.hip: blocks in stable order by
+// block column, each transposed as it is copied) and the forward kernel runs on that.  An ELL handle becomes a COO companion: its rows are ELL's col_ind (borrowed), its columns the row of every
 // slot (an array made here, owned by the transposed state, not by the companion), its values ELL's.  Every slot counts, padding
 // included (0.0 * x_i into y[pad column]), as the forward ELL product counts it.
 //
@@ -27,6 +28,7 @@ struct transpose_state
     int32_t   dia_chunks = 0;
     int32_t   dia_rows   = 0;        // DIA: rows of the LDS window of the tiled kernel (256 + widest chunk spread); 0: the general kernel
     int64_t   bytes      = 0;        // device memory held here (the companion's own counts on top)
+    int64_t   counted_in_owner = 0;  // BSR: the companion's bytes as they were added to the owner's device_bytes
 };
 
 namespace
@@ -265,6 +267,13 @@ int transpose_build(spmv_mat* A, transpose_state* st)
             return make_companion(A, SPMV_FMT_COO, A->ncol, A->nrow, total, A->b, st->slot_rows, A->v, &st->comp);
         }
         case SPMV_FMT_DIA: return dia_transpose_setup(A, st);
+        case SPMV_FMT_BSR:
+            // a BSR handle of A^T with arrays of its own (convert_bsr.hip), run by the forward kernel; unlike the borrowed companions
+            // above it is real memory of the handle's: counted in A's device_bytes until transpose_free
+            SPMV_TRY(bsr_transpose(A->ctx, A, &st->comp));
+            st->counted_in_owner = st->comp->device_bytes;
+            A->device_bytes += st->counted_in_owner;
+            return SPMV_OK;
         default: SPMV_FAIL(SPMV_ERR_INVALID, "spmv_mat_transpose_setup: unknown format %d", A->format);
     }
 }
@@ -316,7 +325,8 @@ void transpose_free(spmv_mat* A)
     transpose_state* st = A->tr;
     if (!st) return;
     if (st->comp || st->slot_rows || st->dia_bounds) (void)hipStreamSynchronize(A->ctx->stream);
-    if (st->comp) mat_free(st->comp);  // (its own layouts and copies; A's arrays it only borrowed)
+    if (st->comp) mat_free(st->comp);  // (its own layouts and copies; A's arrays it only borrowed - a BSR companion owns its own)
+    A->device_bytes -= st->counted_in_owner;
     if (st->slot_rows) (void)hipFree(st->slot_rows);
     if (st->dia_bounds) (void)hipFree(st->dia_bounds);
     delete st;
@@ -328,6 +338,8 @@ int transpose_set_kernel(spmv_mat* A, int64_t kernel)
     const bool csr_companion = A->format == SPMV_FMT_CSC;
     if (A->format == SPMV_FMT_DIA)
         SPMV_REQUIRE(kernel == SPMV_CSR_AUTO || kernel == SPMV_CSR_VECTOR, "transpose_kernel: a DIA handle has one transposed kernel: AUTO (0) or VECTOR (1)");
+    else if (A->format == SPMV_FMT_BSR)
+        SPMV_REQUIRE(kernel == SPMV_CSR_AUTO || kernel == SPMV_CSR_VECTOR, "transpose_kernel: the BSR handle of A^T has one kernel: AUTO (0) or VECTOR (1)");
     else if (csr_companion)
         SPMV_REQUIRE(kernel >= SPMV_CSR_AUTO && kernel <= SPMV_CSR_ELL, "transpose_kernel: a CSR kernel id (0 .. 8) for the CSR companion of a CSC handle");
     else

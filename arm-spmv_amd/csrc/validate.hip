@@ -71,6 +71,14 @@ int mat_validate(const spmv_mat* m)
             if (total) hipLaunchKernelGGL(check_range_kernel, dim3(stream_grid(total)), dim3(kBlock), 0, s, m->b, total, m->ncol, flags);
             break;
         }
+        case SPMV_FMT_BSR:
+        {
+            // the block row pointer runs from 0 to the number of blocks and never decreases; every block column is < ceil(ncol / bs)
+            const int64_t mb = ceil_div(m->nrow, m->k), nnzb = nnz / (m->k * m->k);
+            hipLaunchKernelGGL(check_offsets_kernel, dim3(stream_grid(mb)), dim3(kBlock), 0, s, m->a, mb, nnzb, flags);
+            if (nnzb) hipLaunchKernelGGL(check_range_kernel, dim3(stream_grid(nnzb)), dim3(kBlock), 0, s, m->b, nnzb, (int32_t)ceil_div(m->ncol, m->k), flags);
+            break;
+        }
         case SPMV_FMT_DIA: break;  // the product bounds every column by min(nrow, ncol) itself (kernels_misc.hip)
         default: SPMV_FAIL(SPMV_ERR_INVALID, "unknown format %d", m->format);
     }

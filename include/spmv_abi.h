@@ -54,7 +54,8 @@ typedef enum spmv_format
     SPMV_FMT_CSR = 1, /* include/matrix.h:27-47 */
     SPMV_FMT_CSC = 2, /* include/matrix.h:49-68 */
     SPMV_FMT_ELL = 3, /* include/matrix.h:70-92, column-major: (row i, slot k) at i + k*nrow */
-    SPMV_FMT_DIA = 4  /* include/matrix.h:117-138, row-major: (row i, diag d) at i*ndiags + d */
+    SPMV_FMT_DIA = 4, /* include/matrix.h:117-138, row-major: (row i, diag d) at i*ndiags + d */
+    SPMV_FMT_BSR = 5  /* block CSR, square blocks of bs x bs values, 2 <= bs <= 8 (no counterpart in the reference): spmv_bsr_upload */
 } spmv_format;
 
 /* CSR kernel selection (spmv_mat_set_kernel).  AUTO (csrc/select.hip) is decided when the handle is
@@ -148,14 +149,14 @@ typedef struct spmv_mat_info
     int32_t format;   /* spmv_format */
     int32_t nrow;     /* rows held by this handle (a shard holds its own rows only) */
     int32_t ncol;     /* columns = length of x (always global: x is a full replica, mat_vec.cpp:257) */
-    int32_t ell_k;    /* ELL: slots per row (nonzeros_in_row); DIA: ndiags; else 0 */
-    int64_t nnz;      /* stored nonzeros (ELL: true nnz given at creation, not nrow*k) */
+    int32_t ell_k;    /* ELL: slots per row (nonzeros_in_row); DIA: ndiags; BSR: the block size bs; else 0 */
+    int64_t nnz;      /* stored nonzeros (ELL: true nnz given at creation, not nrow*k; BSR: stored values, blocks * bs * bs) */
     int64_t row_begin; /* first global row of this shard (0 for an unsharded matrix) */
-    int32_t max_row_nnz;
+    int32_t max_row_nnz; /* (BSR: the most blocks in a block row, times bs) */
     int32_t kernel;   /* CSR: the spmv_csr_kernel in effect.  COO / ELL / CSC: 1 = the format's own kernel (segmented scan / lanes
                          over rows / scatter over columns), 4 = the product runs from the handle's row-grouped CSR copy, whichever
                          kernel that copy runs (spmv_mat_get_param "rowgrouped_kernel") */
-    int32_t lanes_per_row; /* CSR vector kernel: lanes cooperating on one row */
+    int32_t lanes_per_row; /* CSR vector kernel: lanes cooperating on one row; BSR: lanes cooperating on one block row */
     int32_t sorted_rows;   /* COO: 1 if row indices are non-decreasing */
     int64_t device_bytes;  /* bytes of device memory owned by the handle */
 } spmv_mat_info;
@@ -997,6 +998,40 @@ int spmv_csr_bandwidth(spmv_ctx* ctx, const spmv_mat* A, int64_t* bandwidth, int
 int spmv_coo_to_csr(spmv_ctx* ctx, const spmv_mat* coo, spmv_mat** out_csr);
 int spmv_coo_to_ell(spmv_ctx* ctx, const spmv_mat* coo, spmv_mat** out_ell);
 int spmv_csr_to_ell(spmv_ctx* ctx, const spmv_mat* csr, spmv_mat** out_ell);
+
+/* ---- block CSR (BSR): csrc/kernels_bsr.hip, csrc/convert_bsr.hip ------------------------------------------------------------
+ * Square blocks of bs x bs values, 2 <= bs <= 8 (any other bs: SPMV_ERR_UNSUPPORTED).  nrow and ncol are SCALAR dimensions and
+ * need not be multiples of bs: there are mb = ceil(nrow / bs) block rows and nbc = ceil(ncol / bs) block columns.  Arrays (in
+ * the order of spmv_mat_download / spmv_mat_device_ptrs): a = the block row pointer, mb + 1 entries from 0 to nnzb; b = the block
+ * column of every block, nnzb entries < nbc; v = nnzb * bs * bs doubles, the blocks one after the other, row-major inside a
+ * block.  Positions of a stored block outside nrow x ncol are ABSENT: they are never multiplied (whatever the caller left
+ * there), x is never read at or beyond ncol and y never written at or beyond nrow.
+ * spmv_mat_get_info: format 5, ell_k = bs, nnz = nnzb * bs * bs, max_row_nnz = the most blocks in a block row times bs,
+ * kernel 1, lanes_per_row = the lanes a block row gets - bs * bs times a divisor of 64 / (bs * bs), chosen at creation from the
+ * mean number of blocks per block row; spmv_mat_set_kernel takes AUTO (0: choose again) or VECTOR (1) with 0 or such a number.
+ * The product y += A x (spmv_apply, _timed, _host, _dot and every solver under SPMV_PRECOND_NONE / _CHEBYSHEV) adds a scalar
+ * row's sums in a fixed order without atomics: the same bits at every launch.  spmv_apply_transpose runs the same kernel on a
+ * BSR handle of A^T that spmv_mat_transpose_setup builds on the device (blocks in stable order by block column, each block
+ * transposed); that handle's memory is counted in device_bytes and freed with the handle.
+ * Refused: spmv_apply_multi and spmv_cg_multi, spmv_mat_partition_rows(balance_entries = 1) (SPMV_ERR_UNSUPPORTED), and
+ * every entry point that needs a CSR handle (ILU(0), SymGS, AMG, SpGEMM, the reorderings, the Jacobi preconditioner), as for
+ * an ELL handle.  The way there is spmv_bsr_to_csr. */
+int spmv_bsr_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int32_t bs, const int32_t* brow_ptr, const int32_t* bcol, const double* values,
+                    spmv_mat** out);
+int spmv_bsr_wrap_device(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int32_t bs, const int32_t* d_brow_ptr, const int32_t* d_bcol,
+                         const double* d_values, spmv_mat** out);
+/* Both conversions run on the device, synchronously; the caller owns the result.
+ * spmv_csr_to_bsr: any unsharded CSR handle with its arrays.  The blocks are those that hold an entry; block columns ascend
+ *   inside a block row; a stored position is the sum of the CSR entries that fall on it, added in stored order from 0.0
+ *   (duplicates are added, a single entry comes through unchanged), a position without an entry is 0.0.
+ * spmv_bsr_to_csr: the stored positions inside nrow x ncol, columns ascending (blocks of one block row in stable order by
+ *   block column); drop_zeros != 0 leaves out the values equal to 0.0.
+ * For a CSR handle with ascending columns, no duplicates and no zero values, bsr_to_csr(csr_to_bsr(A, bs), 1) is A, array for
+ * array.  Refused on the host: null arguments, a bs outside 2 .. 8, a handle of the wrong format (SPMV_ERR_UNSUPPORTED), a
+ * shard, a handle of another context, a CSR handle without its arrays (SPMV_ERR_INVALID). */
+int spmv_csr_to_bsr(spmv_ctx* ctx, const spmv_mat* csr, int32_t bs, spmv_mat** out_bsr);
+int spmv_bsr_to_csr(spmv_ctx* ctx, const spmv_mat* bsr, int32_t drop_zeros, spmv_mat** out_csr);
+
 /* Split a CSR handle (a row shard) by column range, on the device: `inside` holds the entries with a column in
  * [col_begin, col_end), REBASED to 0 (it multiplies the caller's own slice of x: ncol = col_end - col_begin);
  * `outside` holds the others with their global columns.  A*x = inside*x[col_begin:col_end] + outside*x, rows and the
