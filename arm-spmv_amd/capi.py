@@ -20,6 +20,8 @@ FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA, FMT_BSR = 0, 1, 2, 3, 4, 5
 CSR_AUTO, CSR_VECTOR, CSR_LDSWIN, CSR_SCALAR, CSR_PANEL, CSR_TWOPHASE, CSR_SEGSCAN, CSR_SPLIT, CSR_ELL = 0, 1, 2, 3, 4, 5, 6, 7, 8
 AMG_RESTRICT_FUSED, AMG_RESTRICT_UNFUSED, AMG_PROLONG_FUSED, AMG_PROLONG_UNFUSED = 0, 1, 2, 3  # spmv_amg_transfer_timed
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0, PRECOND_CHEBYSHEV, PRECOND_AMG = 0, 1, 2, 3, 4, 5
+PRECOND_FSAI = 6
+FSAI_MAX_ROW = 64  # SPMV_FSAI_MAX_ROW: the cap on the pattern columns of a row of G
 SPGEMM_AUTO, SPGEMM_ROWS, SPGEMM_SORT = 0, 1, 2  # spmv_spgemm's method
 FLAG_DPP_REDUCE, FLAG_XCD_REMAP = 1, 2
 
@@ -130,6 +132,10 @@ SIGNATURES = {
     "spmv_amg_setup_smoothed": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double]),
     "spmv_amg_prolongator": (C.c_int, [_vp, _vp, C.c_int32, _i64p, _i32p, _i32p, _f64p]),
     "spmv_amg_transfer_timed": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _f64p]),
+    "spmv_fsai_setup": (C.c_int, [_vp, _vp, C.c_int32]),
+    "spmv_fsai_solve": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_fsai_info": (C.c_int, [_vp, _i32p, _i64p, _i32p]),
+    "spmv_fsai_factor": (C.c_int, [_vp, _vp, _i64p, _i32p, _i32p, _f64p]),
     "spmv_spgemm": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.POINTER(_vp)]),
     "spmv_csr_transpose": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "spmv_perm_create": (C.c_int, [_vp, C.c_int64, _i32p, C.POINTER(_vp)]),
@@ -603,13 +609,39 @@ class Context:
         """z = B r, one V(1,1) cycle of the handle's hierarchy (amg_setup first), asynchronous; r and z must not overlap"""
         _check(self._lib.spmv_amg_solve(self.h, A.h, r.h, z.h))
 
+    def fsai_setup(self, A: "Matrix", level: int = 0) -> None:
+        """FSAI of a symmetric positive definite CSR handle (spmv_fsai_setup), synchronous; replaces earlier state: the lower-triangular
+        G with G A G^T ~ I on the pattern of tril(A^level), level 1 .. 3 (0: the handle's "fsai_level", default 1); a row of more than
+        FSAI_MAX_ROW pattern columns is refused"""
+        _check(self._lib.spmv_fsai_setup(self.h, A.h, level))
+
+    def fsai_solve(self, A: "Matrix", r: "Vector", z: "Vector") -> None:
+        """z = G^T (G r) with the handle's FSAI factor (fsai_setup first): two products, asynchronous; r and z must not overlap"""
+        _check(self._lib.spmv_fsai_solve(self.h, A.h, r.h, z.h))
+
+    def fsai_info(self, A: "Matrix") -> tuple[int, int, int]:
+        """(level, entries of G, pattern columns of its longest row) of the handle's FSAI state"""
+        level, nnz, longest = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        _check(self._lib.spmv_fsai_info(A.h, C.byref(level), C.byref(nnz), C.byref(longest)))
+        return level.value, nnz.value, longest.value
+
+    def fsai_factor(self, A: "Matrix"):
+        """(row_ptr, col, val) of the FSAI factor G on the host: lower triangular, columns ascending, the diagonal last in its row"""
+        nnz = C.c_int64(0)
+        _check(self._lib.spmv_fsai_factor(self.h, A.h, C.byref(nnz), None, None, None))
+        n, e = A.info.nrow, nnz.value
+        rp, cc, cv = np.zeros(n + 1, dtype=np.int32), np.zeros(e, dtype=np.int32), np.zeros(e, dtype=np.float64)
+        _check(self._lib.spmv_fsai_factor(self.h, A.h, C.byref(nnz), rp.ctypes.data_as(_i32p), cc.ctypes.data_as(_i32p), cv.ctypes.data_as(_f64p)))
+        return rp, cc, cv
+
     def cg(self, A: "Matrix", b: "Vector", x: "Vector", max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
            jacobi: bool = False, symgs: bool = False, precond: int | None = None):
         """conjugate gradients on the device from the x passed in (jacobi: diagonal preconditioner, symgs: one symmetric
         Gauss-Seidel sweep per iteration; CSR handles); returns (iterations, ||r|| / ||b||).  precond, if given, is passed as it
         is (PRECOND_*; PRECOND_ILU0: the ILU(0) factors of a CSR handle, set up on first use; PRECOND_CHEBYSHEV: the handle's Chebyshev
         polynomial, set up on first use with the defaults unless chebyshev_setup was called; PRECOND_AMG: one cycle of the handle's
-        aggregation AMG hierarchy, likewise unless amg_setup was called)"""
+        aggregation AMG hierarchy, likewise unless amg_setup was called; PRECOND_FSAI: the handle's FSAI factor, likewise unless
+        fsai_setup was called)"""
         it, res = C.c_int32(0), C.c_double(0.0)
         pc = precond if precond is not None else (PRECOND_SYMGS if symgs else (PRECOND_JACOBI if jacobi else PRECOND_NONE))
         _check(self._lib.spmv_cg(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, pc, C.byref(it), C.byref(res)))

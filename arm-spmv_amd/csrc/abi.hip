@@ -106,6 +106,7 @@ void mat_free(spmv_mat* m)
     ilu0_free(m);
     cheby_free(m);
     amg_free(m);
+    fsai_free(m);
     if (m->rowgrouped) mat_free(m->rowgrouped);
     coo_free_bins(m);
     delete m;
@@ -884,6 +885,10 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
     {
         if (arc != SPMV_OK) return arc;
     }
+    else if (int frc = SPMV_OK; fsai_set_param(m, name, value, &frc))  // "fsai_level": at the next set-up of a solver's own
+    {
+        if (frc != SPMV_OK) return frc;
+    }
     else if (int crc = SPMV_OK; cheby_set_param(m, name, value, &crc))  // "cheby_degree", "cheby_ratio", "cheby_lanczos_steps": at the next set-up
         return crc;
     else if (!strcmp(name, "twophase_panel_cols"))  // takes effect at the next spmv_mat_set_kernel(TWOPHASE)
@@ -981,6 +986,7 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
         return SPMV_OK;
     }
     if (amg_get_param(m, name, value)) return SPMV_OK;  // "amg_ready", "amg_levels", "amg_bytes", "amg_launches", "amg_mis_rounds", "amg_level_kernel"
+    if (fsai_get_param(m, name, value)) return SPMV_OK;  // "fsai_level", "fsai_ready", "fsai_bytes", "fsai_max_row"
     if (spgemm_get_param(m, name, value)) return SPMV_OK;  // "spgemm_products", "spgemm_rows_lds", "spgemm_rows_sorted", "spgemm_lds_products", ...
     if (cheby_get_param(m, name, value)) return SPMV_OK;  // "cheby_ready", "cheby_degree", "cheby_bytes", "cheby_launches", ...
     if (transpose_get_param(m, name, value)) return SPMV_OK;  // "transpose_ready", "transpose_bytes", "transpose_kernel", ...
@@ -1371,10 +1377,10 @@ int spmv_apply_dot(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec
 
 // The five solves.  Every check is made before the device is touched, so that they hold (and are tested) on a machine without one;
 // the checks they share and what each solver's refusals depend on (solver_rules) are solver_host.hpp's.
-static const solver_rules kCgRules       = {"spmv_cg", "the matrix", true, nullptr, nullptr, solver_rules::jacobi_arrays_unsupported, nullptr, nullptr};
-static const solver_rules kCgMultiRules  = {"spmv_cg_multi", "the matrix", false, "k columns", "k columns", solver_rules::jacobi_arrays_elsewhere, "k columns", "k columns"};
-static const solver_rules kBicgstabRules = {"spmv_bicgstab", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr};
-static const solver_rules kGmresRules    = {"spmv_gmres", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr};
+static const solver_rules kCgRules       = {"spmv_cg", "the matrix", true, nullptr, nullptr, solver_rules::jacobi_arrays_unsupported, nullptr, nullptr, nullptr};
+static const solver_rules kCgMultiRules  = {"spmv_cg_multi", "the matrix", false, "k columns", "k columns", solver_rules::jacobi_arrays_elsewhere, "k columns", "k columns", "k columns"};
+static const solver_rules kBicgstabRules = {"spmv_bicgstab", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr, nullptr};
+static const solver_rules kGmresRules    = {"spmv_gmres", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr, nullptr};
 
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
             int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
@@ -1468,7 +1474,7 @@ int spmv_block_combine(spmv_ctx* ctx, int64_t n, int32_t p, const spmv_vec* S, i
 }
 
 // extreme eigenpairs of a symmetric matrix by LOBPCG (solver_lobpcg.hip)
-static const solver_rules kLobpcgRules = {"spmv_lobpcg", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr};
+static const solver_rules kLobpcgRules = {"spmv_lobpcg", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr, nullptr};
 
 int spmv_lobpcg(spmv_ctx* ctx, const spmv_mat* A, int32_t k, int32_t nev, int32_t largest, spmv_vec* X, int32_t max_iter, double tol, int32_t precond,
                 double* theta, double* resid, int32_t* iters)
@@ -1695,6 +1701,50 @@ int spmv_amg_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
     return amg_apply(ctx, A, r->d, z->d);
+}
+
+// FSAI (fsai.hip).  Every check is made before the device is touched and reads the leading fields of the handle alone.
+int spmv_fsai_setup(spmv_ctx* ctx, spmv_mat* A, int32_t level)
+{
+    const char* const who = "spmv_fsai_setup";
+    SPMV_REQUIRE(ctx && A, "%s: null argument", who);
+    SPMV_TRY(fsai_check_level(level, who));
+    SPMV_TRY(fsai_check_handle(A, who));
+    SPMV_REQUIRE(A->ctx == ctx, "%s: the matrix belongs to another context", who);
+    if (A->nrow > 0) SPMV_TRY(use_device(ctx));
+    return fsai_setup(ctx, A, level);
+}
+
+int spmv_fsai_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z)
+{
+    const char* const who = "spmv_fsai_solve";
+    SPMV_REQUIRE(ctx && A && r && z, "%s: null argument", who);
+    SPMV_TRY(fsai_check_handle(A, who));
+    SPMV_REQUIRE(A->ctx == ctx, "%s: the matrix belongs to another context", who);
+    SPMV_REQUIRE(r->n == A->nrow && z->n == A->nrow, "%s: r has %lld and z %lld entries, the matrix %d rows", who, (long long)r->n, (long long)z->n,
+                 A->nrow);
+    SPMV_REQUIRE(vectors_disjoint(r, z), "%s: r and z must not overlap", who);
+    if (!A->fsai) SPMV_FAIL(SPMV_ERR_INVALID, "%s: the handle was not set up (spmv_fsai_setup)", who);
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return fsai_apply(ctx, A, r->d, z->d);
+}
+
+int spmv_fsai_info(const spmv_mat* A, int32_t* level, int64_t* nnz, int32_t* max_row)
+{
+    SPMV_REQUIRE(A && level && nnz && max_row, "spmv_fsai_info: null argument");
+    return fsai_info(A, level, nnz, max_row);
+}
+
+int spmv_fsai_factor(spmv_ctx* ctx, const spmv_mat* A, int64_t* nnz, int32_t* row_ptr, int32_t* col, double* val)
+{
+    const char* const who = "spmv_fsai_factor";
+    SPMV_REQUIRE(ctx && A && nnz, "%s: null argument", who);
+    SPMV_TRY(fsai_check_handle(A, who));
+    SPMV_REQUIRE(A->ctx == ctx, "%s: the matrix belongs to another context", who);
+    if (!A->fsai) SPMV_FAIL(SPMV_ERR_INVALID, "%s: the handle was not set up (spmv_fsai_setup)", who);
+    if (A->nrow > 0) SPMV_TRY(use_device(ctx));
+    return fsai_factor_download(ctx, A, nnz, row_ptr, col, val);
 }
 
 int spmv_chebyshev(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x)

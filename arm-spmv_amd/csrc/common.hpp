@@ -150,6 +150,7 @@ struct symgs_plan;
 struct ilu0_plan;
 struct cheby_state;
 struct amg_state;
+struct fsai_state;
 struct transpose_state;
 // ---- plans (plan.hip): the decisions a handle's set-up made - by model or by timing - as plain data ------------------------------
 // One node per handle, children by index (the row-grouped copy of a COO / CSC / ELL handle or the short-row copy of a split,
@@ -384,6 +385,11 @@ struct spmv_mat
     // of copies or of the transposed state
     struct spmv::amg_state* amg              = nullptr;
     int32_t                 amg_level_kernel = 0;  // "amg_level_kernel": != 0 forces that CSR kernel id on every coarse handle of the next set-up
+
+    // FSAI (fsai.hip): the factor G and G^T as CSR handles of their own and one work vector; built by spmv_fsai_setup (or by the first
+    // solve with SPMV_PRECOND_FSAI), no part of the forward state, of plans, of trials, of copies, of device_bytes or of the transposed state
+    struct spmv::fsai_state* fsai       = nullptr;
+    int32_t                  fsai_level = 1;  // "fsai_level": the pattern of tril(A^level) that a solver's own set-up takes, 1 .. 3
 
     // a handle that spmv_spgemm made (spgemm.hip): what that product did ("spgemm_*"; 0 on every other handle)
     bool    spgemm_made = false;
@@ -630,6 +636,16 @@ int  amg_level_download(spmv_ctx* ctx, const spmv_mat* m, int level, int32_t* ag
 int  amg_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z);  // z = B r, asynchronous; r and z must not overlap
 bool amg_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "amg_*"; false: not one of them
 bool amg_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "amg_level_kernel"; false: not that
+// fsai.hip: the factorised sparse approximate inverse G A G^T ~ I of an SPD CSR handle, z = G^T (G r) (SPMV_PRECOND_FSAI)
+int  fsai_check_handle(const spmv_mat* m, const char* who);  // on the host: UNSUPPORTED (not CSR) / INVALID (a shard, not square, arrays released)
+int  fsai_check_level(int32_t level, const char* who);       // on the host: 0 .. 3
+int  fsai_setup(spmv_ctx* ctx, spmv_mat* m, int32_t level);  // synchronous; 0: the handle's "fsai_level"; replaces earlier state
+void fsai_free(spmv_mat* m);
+int  fsai_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z);  // asynchronous; r and z must not overlap
+int  fsai_info(const spmv_mat* m, int32_t* level, int64_t* nnz, int32_t* max_row);
+int  fsai_factor_download(spmv_ctx* ctx, const spmv_mat* m, int64_t* nnz, int32_t* row_ptr, int32_t* col, double* val);
+bool fsai_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "fsai_*"; false: not one of them
+bool fsai_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "fsai_level"; false: not that
 // spgemm.hip: C = A B and A^T as CSR handles of their own
 int  spgemm_check(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* B, int32_t method, const char* who);  // on the host: every refusal made before the device is touched
 int  csr_transpose_check(const spmv_ctx* ctx, const spmv_mat* A, const char* who);                              // likewise

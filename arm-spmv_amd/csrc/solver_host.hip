@@ -59,7 +59,7 @@ int check_limits(const char* who, int max_iter, double rel_tol)
 int check_known_preconditioner(const char* who, int precond)
 {
     SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0 ||
-                     precond == SPMV_PRECOND_CHEBYSHEV || precond == SPMV_PRECOND_AMG,
+                     precond == SPMV_PRECOND_CHEBYSHEV || precond == SPMV_PRECOND_AMG || precond == SPMV_PRECOND_FSAI,
                  "%s: unknown preconditioner %d", who, precond);
     return SPMV_OK;
 }
@@ -97,6 +97,11 @@ int check_preconditioner(const solver_rules& S, const spmv_mat* A, int precond)
     {
         if (S.amg_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the AMG preconditioner is not built for %s", S.who, S.amg_not_built_for);
         return amg_check_handle(A, S.who);
+    }
+    if (precond == SPMV_PRECOND_FSAI)
+    {
+        if (S.fsai_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the FSAI preconditioner is not built for %s", S.who, S.fsai_not_built_for);
+        return fsai_check_handle(A, S.who);
     }
     if (precond != SPMV_PRECOND_JACOBI) return SPMV_OK;
     // Jacobi reads the diagonal from the handle's own CSR arrays (the plain solve needs the product alone and takes a handle that
@@ -175,6 +180,8 @@ int setup_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, double* 
             return A->cheby ? SPMV_OK : cheby_setup(ctx, const_cast<spmv_mat*>(A), A->cheby_degree, /*scaled=*/1, 0.0, 0.0);
         case SPMV_PRECOND_AMG:  // likewise; 0: every default
             return A->amg ? SPMV_OK : amg_setup(ctx, const_cast<spmv_mat*>(A), 0, 0, 0, 0.0, 0.0);
+        case SPMV_PRECOND_FSAI:  // likewise; 0: the handle's "fsai_level"
+            return A->fsai ? SPMV_OK : fsai_setup(ctx, const_cast<spmv_mat*>(A), 0);
         default: return SPMV_OK;
     }
 }
@@ -186,6 +193,7 @@ int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const do
         case SPMV_PRECOND_ILU0: return ilu0_apply(ctx, A, r, z);
         case SPMV_PRECOND_CHEBYSHEV: return cheby_apply(ctx, A, r, z);
         case SPMV_PRECOND_AMG: return amg_apply(ctx, A, r, z);
+        case SPMV_PRECOND_FSAI: return fsai_apply(ctx, A, r, z);
         default: return symgs_sweep(ctx, A, r, z, true);
     }
 }

@@ -25,6 +25,7 @@ struct solver_rules
     } jacobi_arrays;
     const char* cheby_not_built_for;  // nullptr: the Chebyshev polynomial is built (cheby_check_handle decides on the handle); else the end of the refusal
     const char* amg_not_built_for;    // nullptr: AMG is built (amg_check_handle decides on the handle); else the end of the refusal
+    const char* fsai_not_built_for;   // nullptr: FSAI is built (fsai_check_handle decides on the handle); else the end of the refusal
 };
 
 bool vectors_disjoint(const spmv_vec* b, const spmv_vec* x);  // an empty vector overlaps nothing
@@ -74,15 +75,19 @@ private:
 
 // ---- the preconditioner --------------------------------------------------------------------------------------------------------
 // Before a solve's first launch: the state that stays in the handle (symgs_setup, ilu0_setup: built once; cheby_setup and amg_setup
-// with the defaults unless the handle was set up before), or dinv[i] = 1 / a_ii of
+// and fsai_setup with the defaults unless the handle was set up before), or dinv[i] = 1 / a_ii of
 // a CSR handle for Jacobi (synchronous; a zero or missing diagonal entry is `who`'s error).  SPMV_PRECOND_NONE: nothing.
 int setup_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, double* dinv, const char* who);
 // dinv[i] = 1 / a_ii of a CSR handle (duplicates summed; synchronous); a zero or missing entry: INVALID, "<who>: ... (<what>)"
 int jacobi_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, const char* who, const char* what = "Jacobi preconditioner");
 // a preconditioner that is a launch sequence of its own (a work vector z between the product and the updates), not a diagonal
-inline bool applied_by_launches(int precond) { return precond == SPMV_PRECOND_ILU0 || precond == SPMV_PRECOND_CHEBYSHEV || precond == SPMV_PRECOND_AMG; }
+inline bool applied_by_launches(int precond)
+{
+    return precond == SPMV_PRECOND_ILU0 || precond == SPMV_PRECOND_CHEBYSHEV || precond == SPMV_PRECOND_AMG || precond == SPMV_PRECOND_FSAI;
+}
 // z = M^-1 r for the preconditioners that are launch sequences of their own: the two triangular solves of ILU(0) (ilu0.hip), one
-// symmetric Gauss-Seidel sweep from z = 0 (symgs.hip), the Chebyshev polynomial in the handle (chebyshev.hip), or one AMG cycle (amg.hip)
+// symmetric Gauss-Seidel sweep from z = 0 (symgs.hip), the Chebyshev polynomial in the handle (chebyshev.hip), one AMG cycle (amg.hip), or
+// the two products of FSAI (fsai.hip)
 int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const double* r, double* z);
 
 // ---- width and grids -----------------------------------------------------------------------------------------------------------

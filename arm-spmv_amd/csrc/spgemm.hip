@@ -439,6 +439,7 @@ int csr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out, int32_t forc
     coo.a      = A->b;
     coo.b      = row;
     coo.v      = A->v;
+    coo.pb_trial = A->pb_trial;  // ("panel_trial" of the source handle holds for what is built from it)
     return coo_to_csr(ctx, &coo, out, force_kernel);
 }
 }  // namespace spmv

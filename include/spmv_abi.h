@@ -349,6 +349,8 @@ int spmv_mat_set_flags(spmv_mat* m, uint32_t flags);
  *   "amg_level_kernel"   a CSR kernel id (1 .. 8) that the next spmv_amg_setup forces on every coarse handle; 0 (default): each selects.
  *                    An id that a coarse operator cannot run (LDSWIN: a block window wider than the tile) fails that set-up
  *                    (SPMV_ERR_UNSUPPORTED); no other kernel takes its place
+ *   "fsai_level"     the pattern tril(A^level) that a solver's own set-up of SPMV_PRECOND_FSAI, and spmv_fsai_setup with level 0, take:
+ *                    1 (default) .. 3
  *   "panel_two_per_cu"   0 = never two workgroups per CU (default 1: two when their accumulators fit the LDS twice) */
 int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
 /* What is in effect: "panel_rows", "panel_width", "panel_sort", "panel_groups", "panel_layout", "panel_unroll",
@@ -368,7 +370,7 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
  * "symgs_levels_forward", "symgs_levels_backward", "symgs_launches", "symgs_bytes", "symgs_fused" (1: the colouring is proper and
  * the sweep takes one launch per colour), "ilu0_order", "ilu0_ready", "ilu0_colours", "ilu0_levels_forward", "ilu0_levels_backward",
  * "ilu0_launches" (per application), "ilu0_bytes", the "cheby_*" names listed at spmv_chebyshev_setup, the "amg_*" names listed
- * at spmv_amg_setup and the "spgemm_*" names listed at spmv_spgemm. */
+ * at spmv_amg_setup, the "fsai_*" names listed at spmv_fsai_setup and the "spgemm_*" names listed at spmv_spgemm. */
 int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value);
 /* ---- plans: a handle's set-up decisions as plain data (plan.hip) ------------------------------------------------------------
  * AUTO is a measurement (spmv_mat_set_kernel above): which kernel a handle runs, in which layout, with which chunk size,
@@ -510,10 +512,14 @@ enum spmv_precond
                                 that was not is set up on first use with degree "cheby_degree" (4), Jacobi scaling and estimated
                                 bounds, which needs a CSR handle with its arrays.  spmv_cg, spmv_bicgstab and spmv_gmres, with the
                                 work vectors and arrangement of SPMV_PRECOND_ILU0; spmv_cg_multi: SPMV_ERR_UNSUPPORTED */
-    SPMV_PRECOND_AMG = 5 /* z = B r, one V(1,1) cycle of aggregation AMG on a CSR handle (spmv_amg_setup below).  A handle that was set up
+    SPMV_PRECOND_AMG = 5, /* z = B r, one V(1,1) cycle of aggregation AMG on a CSR handle (spmv_amg_setup below).  A handle that was set up
                             is used as it stands; one that was not is set up on first use with every default.  spmv_cg, spmv_bicgstab
                             and spmv_gmres, with the work vectors and arrangement of SPMV_PRECOND_ILU0; spmv_cg_multi:
                             SPMV_ERR_UNSUPPORTED */
+    SPMV_PRECOND_FSAI = 6 /* z = G^T (G r), the factorised sparse approximate inverse of a symmetric positive definite CSR handle
+                             (spmv_fsai_setup below): two forward products.  A handle that was set up is used as it stands; one that was
+                             not is set up on first use at level "fsai_level" (1).  spmv_cg, spmv_bicgstab, spmv_gmres and spmv_lobpcg,
+                             with the work vectors and arrangement of SPMV_PRECOND_ILU0; spmv_cg_multi: SPMV_ERR_UNSUPPORTED */
 };
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter,
             double rel_tol, int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
@@ -904,6 +910,46 @@ enum
 };
 int spmv_amg_transfer_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t level, int32_t what, int32_t lanes, spmv_vec* v, int32_t reps,
                             double* ms_per_call);
+
+/* ---- FSAI: a factorised sparse approximate inverse applied by two products (fsai.hip) ---------------------------------
+ * For a symmetric positive definite A, a sparse lower-triangular G with G A G^T ~ I (Kolotilina-Yeremin); the preconditioner is
+ * z = G^T (G r).  Handles: those of spmv_ilu0_setup - a CSR handle (BSR and every other format: SPMV_ERR_UNSUPPORTED) holding the whole
+ * square matrix, of this context, with its arrays (a shard, a rectangle, another context's handle, arrays released by
+ * panel_keep_csr = 0: SPMV_ERR_INVALID) - checked on the host before any device use.  n = 0: SPMV_OK, nothing is launched.
+ *
+ *   Pattern.  S is the lower triangle, diagonal included, of the structural pattern of A^level, level 1, 2 or 3.  Every stored entry
+ *   counts, zeros included.  Each row of S holds distinct columns in ascending order, and its last column is the row itself: a row
+ *   without a stored diagonal entry is SPMV_ERR_INVALID naming the (smallest such) row.  Level 1 is tril(A) with duplicates merged;
+ *   levels 2 and 3 come from spmv_spgemm's structural pattern (A A, then (A A) A) cut to the lower triangle on the device.
+ *   Row i, with J = S_i and m = |J|.  M = A[J, J], of which only the LOWER triangle of A is read: entry (p, q), q <= p, is the sum of
+ *   the stored entries (J_p, J_q) of row J_p of A, from 0.0, duplicates in stored order.  Symmetry is NOT checked, as in any Cholesky
+ *   routine: the upper triangle of A is never looked at.  M = C C^T (right-looking: c_kk = sqrt(m_kk), c_pk = m_pk / c_kk, then
+ *   m_pq = fma(-c_pk, c_qk, m_pq) for k < q <= p); row i of G is the solution g of C^T g = e_m, from the last unknown up
+ *   (g_p = t_p / c_pp, then t_a = fma(-c_pa, g_p, t_a) for a < p), so g_ii = 1 / c_mm.  A pivot m_kk that is not finite or not
+ *   positive is SPMV_ERR_INVALID: the message names the smallest such row, and nothing is left in the handle.
+ *   Cap.  m <= 64.  A longer row is SPMV_ERR_UNSUPPORTED; the message names the first such row, its m and the cap, and the state of
+ *   an earlier set-up stays in the handle (a missing diagonal entry or a bad pivot leave none).
+ *   Application.  z = G^T (G r): G and G^T are two internal CSR handles, G^T built by the path of spmv_csr_transpose, each with its
+ *   own AUTO kernel choice ("panel_trial" of A holds for both); two product launches that overwrite their outputs, one work vector
+ *   of n.  Two set-ups give the same bits of G; two applications of one state give the same bits of z, and so do two states whose
+ *   handles chose the same kernels (always, where the choice is the model's: below 65,536 entries, or under "panel_trial" 0).
+ *
+ * spmv_fsai_setup: synchronous; level 0 means the handle's "fsai_level"; anything outside 0 .. 3 is SPMV_ERR_INVALID on the host.
+ *   Called again, it rebuilds.  spmv_fsai_solve: asynchronous; r and z overlapping, wrong lengths or a handle that was not set up:
+ *   SPMV_ERR_INVALID on the host.  spmv_fsai_info: level, entries of G and the longest row of a state.  spmv_fsai_factor: to the host,
+ *   the entries of G in *nnz and, where the pointers are not NULL, G as CSR (arrays of nrow + 1, *nnz, *nnz: ask for nnz alone first).
+ * spmv_mat_get_param: "fsai_level" (what a solver's own set-up takes), "fsai_ready", "fsai_bytes" (both handles and the work vector;
+ *   NOT counted in device_bytes), "fsai_max_row", and the wall time of the last set-up in microseconds by phase: "fsai_setup_us_pattern"
+ *   (the sparse products, the cut, G's offsets and columns), "fsai_setup_us_rows" (the row kernel), "fsai_setup_us_handles" (the analysis
+ *   of G, the transpose and its analysis).  The state is no part of the forward state, of plans, trials, copies or the
+ *   transposed state, and is freed with the handle.
+ * Not built here: thresholded or adaptive patterns, rows truncated at the cap, a two-factor variant for nonsymmetric matrices, FSAI as
+ *   an AMG smoother, FSAI under spmv_cg_multi or the sharded solver (both possible, since the application is products only). */
+#define SPMV_FSAI_MAX_ROW 64
+int spmv_fsai_setup(spmv_ctx* ctx, spmv_mat* A, int32_t level);
+int spmv_fsai_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z);
+int spmv_fsai_info(const spmv_mat* A, int32_t* level, int64_t* nnz, int32_t* max_row);
+int spmv_fsai_factor(spmv_ctx* ctx, const spmv_mat* A, int64_t* nnz, int32_t* row_ptr, int32_t* col, double* val /* G, or NULLs */);
 
 /* ---- sparse products on the device (spgemm.hip) ------------------------------------------------------------------------
  * spmv_spgemm: C = A B for two CSR handles of one context, A m x k and B k x n, both whole matrices (row_begin 0) that still hold
