@@ -276,6 +276,39 @@ def diagonal_powers_of_four(n=37):
     return n, np.arange(n + 1, dtype=np.int32), np.arange(n, dtype=np.int32), d
 
 
+# ---- rows that take a later trip over the grid (tests/tiled.py) ---------------------------------------------------------------------
+# per lane class of fsai_rows_kernel the smallest base with rows of that class, and its level: the 5-point Laplacian on 3 x 3
+# (m = 1 .. 3), on 8 x 8 at level 2 (m up to 7) and 3 (m up to 13), dense blocks with every m up to 64
+GRID_LOOP_BASES = {
+    4: (lambda: laplacian_2d(3), 1),
+    8: (lambda: laplacian_2d(8), 2),
+    16: (lambda: laplacian_2d(8), 3),
+    32: (lambda: dense_blocks((64, 47, 27))[:4], 1),
+    64: (lambda: dense_blocks((64, 47, 27))[:4], 1),
+}
+
+
+def grid_loop_case(lanes):
+    """The base of GRID_LOOP_BASES[lanes] in as many block-diagonal copies as take the groups of `lanes` lanes past kMaxGrid
+    workgroups: a dict of the base matrix, its twin, the copies, the rows of the class a copy, the groups a workgroup, and
+    where(copy, row) for tiled.tiled_mismatch.  Every threshold comes from the settings headers."""
+    import tiled
+
+    build, level = GRID_LOOP_BASES[lanes]
+    n, rp, cc, cv = build()
+    ref = Fsai(n, rp, cc, cv, level)
+    m = np.diff(ref.rp)
+    all_lanes = tiled.fsai_lanes()
+    cls = np.array([tiled.fsai_class_of(x) for x in m])
+    groups = {c: tiled.fsai_groups_per_block(L) for c, L in enumerate(all_lanes)}
+    mine = all_lanes.index(lanes)
+    rows, grid = int(np.sum(cls == mine)), tiled.max_grid()
+    assert rows > 0, f"no row of {lanes} lanes in the base"
+    trips = tiled.describe_trips(cls, groups, grid, {c: f"of {L} lanes" for c, L in enumerate(all_lanes)})
+    return dict(n=n, rp=rp, cc=cc, cv=cv, level=level, ref=ref, m=m, rows=rows, groups=groups[mine], grid=grid,
+                copies=groups[mine] * grid // rows + 1, where=lambda copy, row: f"m = {int(m[row])}, {trips(copy, row)}")
+
+
 # ---- the two systems whose iteration counts the GPU test compares with --------------------------------------------------------------
 REL_TOL = 1e-9
 SOLVER_SYSTEMS = ("laplacian_2d_33", "laplacian_3d_12")

@@ -253,6 +253,29 @@ def star(leaves: int):
     return from_edges(leaves + 1, np.zeros(leaves, dtype=np.int64), np.arange(1, leaves + 1))
 
 
+def broom(children: int, seed: int):
+    """a root (vertex 0) with `children` children, every child with 0, 1 or 2 leaves of its own: a tree of mean degree 2 whose level
+    structures hold two levels about as wide as `children`"""
+    leaves = np.random.default_rng(seed).integers(0, 3, children)
+    child = np.arange(1, children + 1, dtype=np.int64)
+    n = 1 + children + int(leaves.sum())
+    a = np.concatenate([np.zeros(children, dtype=np.int64), np.repeat(child, leaves)])
+    b = np.concatenate([child, np.arange(1 + children, n, dtype=np.int64)])
+    return from_edges(n, a, b)
+
+
+def hairy_star(children: int, sibling_edges: int, seed: int):
+    """a root (vertex 0) with `children` children, one leaf under every child, and random edges among the children: the edges among
+    siblings raise the mean degree without changing who alone reaches a leaf - its parent, wherever that stands in its frontier"""
+    rng = np.random.default_rng(seed)
+    child = np.arange(1, children + 1, dtype=np.int64)
+    s, t = rng.integers(1, children + 1, sibling_edges), rng.integers(1, children + 1, sibling_edges)
+    keep = s != t
+    a = np.concatenate([np.zeros(children, dtype=np.int64), child, s[keep]])
+    b = np.concatenate([child, child + children, t[keep]])
+    return from_edges(1 + 2 * children, a, b)
+
+
 def complete(n: int):
     a, b = np.triu_indices(n, 1)
     return from_edges(n, a, b)
@@ -272,6 +295,52 @@ def band(n: int, half: int, per_row: int, seed: int):
     c = np.clip(r + rng.integers(-half, half + 1, n * per_row), 0, n - 1)
     key = np.unique(r * n + c)
     return csr_from_entries(n, key // n, key % n, 1.0 + (key % 7))
+
+
+# Graphs whose widest frontier takes the breadth-first kernels (rcm_claim / count / fill_kernel<LANES>) on a second trip over their
+# grid, for every lane count - name: (the graph, the lanes its mean degree selects) - and, the first two, with more rows than one trip
+# of the 16-lanes-a-row kernels takes (the adjacency, the permutation's keys, the bandwidth).  tests/test_rcm_ref.py holds their widths and
+# lane counts to the settings on the CPU, tests/test_gpu_reorder.py runs them.
+GRID_LOOP_GRAPHS = {
+    "broom131200": (lambda: shuffled(broom(131_200, 5), 6), 4),
+    "random100000_deg10": (lambda: random_graph(100_000, 500_000, 7), 16),
+    "random20000_deg40": (lambda: random_graph(20_000, 400_000, 8), 64),
+    # in random20000_deg40 every vertex behind the wide frontier has about 29 parents in it, the first of them on the first trip: the
+    # later trip claims, counts and fills nothing.  Here the last of 8299 parents each own a leaf that nobody else reaches
+    "hairy8300_deg38": (lambda: shuffled(hairy_star(8300, 300_000, 9), 10), 64),
+}
+
+
+def later_trip_children(n, row_ptr, col, order, widths, one_trip):
+    """the vertices of a one-component ordering whose first parent - the neighbour that claims them, the one of smallest place in
+    the level before - stands at place one_trip or beyond in its level: what a later trip of the breadth-first kernels has to find"""
+    adj_rp, adj = adjacency(n, row_ptr, col)
+    cm = np.asarray(order, dtype=np.int64)[::-1]
+    w = widths[0]
+    start = n - sum(w) + np.concatenate([[0], np.cumsum(w)])  # (the vertices without neighbours come first)
+    place = np.empty(n, dtype=np.int64)
+    place[cm] = np.arange(n)
+    found = 0
+    for lv in range(1, len(w)):
+        level = cm[start[lv]:start[lv + 1]]
+        parent, nb = _neighbours(adj_rp, adj, level)
+        ok = (place[nb] >= start[lv - 1]) & (place[nb] < start[lv])
+        first = np.full(len(level), n, dtype=np.int64)
+        np.minimum.at(first, parent[ok], place[nb[ok]] - start[lv - 1])
+        assert np.all(first < n), "every vertex of a level has a parent in the level before"
+        found += int(np.sum(first >= one_trip))
+    return found
+
+
+def grid_loop_facts(n, row_ptr, col, widths, isolated):
+    """(the lanes the device picks for this graph, its widest frontier, the frontier beyond which those lanes loop, the rows beyond
+    which the 16-lanes-a-row kernels loop): from the settings headers (tests/tiled.py)"""
+    import tiled
+
+    adj_rp, _ = adjacency(n, row_ptr, col)
+    lanes = tiled.rcm_lanes(int(adj_rp[-1]) / (n - isolated))  # the mean degree of the vertices with neighbours
+    per_block = tiled.block_lanes() // lanes
+    return lanes, max(max(w) for w in widths), per_block * tiled.max_grid(), tiled.block_lanes() // tiled.rcm_row_lanes() * tiled.max_grid()
 
 
 def shuffled(A, seed: int):

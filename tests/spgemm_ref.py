@@ -218,3 +218,49 @@ def hub_case(hub_len=5000, hub_rows=200, short_rows=300, n=6000, seed=31):
     bcol = np.concatenate([rng.permutation(n)[:hub_len], rng.integers(0, n, 4 * (k - 1))])
     B = csr_of(k, brow, bcol, rng.uniform(-1, 1, len(brow)))
     return m, k, n, A, B
+
+
+# ---- rows that take a later trip over the grid (tests/tiled.py) ---------------------------------------------------------------------
+# the scalar products of the rows of class_edge_pair: both edges of the wavefront class (129 .. 512) and of the workgroup class
+# (513 .. 2048), either side of a power of two in each - the sorting network exactly full and one over - a 16-lane row, an empty one
+CLASS_EDGE_UB = (129, 513, 40, 200, 700, 0, 256, 1024, 257, 1025, 512, 2048)
+
+
+def class_edge_pair(ubs=CLASS_EDGE_UB, ncol=400, seed=61):
+    """(m, k, n, A, B): row i of A has exactly ubs[i] scalar products.  B has 40 rows of lengths 1 .. 40 with random columns
+    (unsorted, repeats) and values in (-1, 1); a row of A names random rows of B, repeats among them, until their lengths add up:
+    runs of several addends whose order matters"""
+    rng = np.random.default_rng(seed)
+    brow = np.repeat(np.arange(40, dtype=np.int64), np.arange(1, 41))
+    B = csr_of(40, brow, rng.integers(0, ncol, len(brow)), rng.uniform(-1, 1, len(brow)))
+    row, col = [], []
+    for i, ub in enumerate(ubs):
+        left = int(ub)
+        while left > 0:
+            length = int(rng.integers(1, min(40, left) + 1))
+            row.append(i)
+            col.append(length - 1)  # (row p of B holds p + 1 entries)
+            left -= length
+    A = csr_of(len(ubs), row, col, rng.uniform(-1, 1, len(row)))
+    return len(ubs), 40, ncol, A, B
+
+
+def grid_loop_case():
+    """class_edge_pair in as many block-diagonal copies as take the wavefront class and the workgroup class of spgemm_rows_kernel
+    past kMaxGrid workgroups: a dict of the base pair, its twin, the copies k, per looping class (name, rows a copy, rows a
+    workgroup), and where(copy, row) for tiled.tiled_mismatch.  Every threshold comes from the settings headers."""
+    import tiled
+
+    grid = tiled.max_grid()
+    classes = tiled.spgemm_classes()  # ascending: 16 lanes, the wavefront, the workgroup
+    caps = [cap for _, cap, _ in classes]
+    m, k0, n, A, B = class_edge_pair()
+    twin = spgemm_twin(m, k0, n, A, B)
+    ub = twin[3]
+    cls = np.where(ub > 0, np.searchsorted(caps, ub, side="left") + 1, 0)  # spgemm_class_of: 0 none, 1 .. 3 the LDS classes
+    names = {0: "none", 1: "lane16", 2: "wave", 3: "block", 4: "sort"}
+    looping = {c: (names[c], int(np.sum(cls == c)), classes[c - 1][2]) for c in (2, 3)}
+    # one copy beyond the smallest count that loops: the second trip of the wavefront class then holds two whole row groups
+    copies = max(per_group * grid // rows for _, rows, per_group in looping.values()) + 2
+    where = tiled.describe_trips(cls, {c + 1: per_group for c, (_, _, per_group) in enumerate(classes)}, grid, names)
+    return dict(m=m, k=k0, n=n, A=A, B=B, twin=twin, cls=cls, caps=caps, grid=grid, copies=copies, looping=looping, where=where)

@@ -14,6 +14,7 @@ import pytest
 
 import fsai_ref as fr
 import solver_ref
+import tiled
 
 PROBLEMS = {
     "tridiagonal_8": (fr.tridiagonal_8, (1, 2, 3)),
@@ -125,6 +126,46 @@ def test_a_missing_diagonal_entry_and_a_negative_pivot_name_their_rows():
         fr.Fsai(3, [0, 1, 2, 3], [0, 1, 0], [1.0, 1.0, 1.0], 1)
     with pytest.raises(ZeroDivisionError, match="row 1 "):
         fr.Fsai(2, [0, 2, 4], [0, 1, 0, 1], [1.0, 2.0, 2.0, 1.0], 1)
+
+
+def test_block_diagonal_copies_tile_the_twin():
+    """the oracle of the GPU test's later trips over the grid (tests/tiled.py): the twin of k copies is the twin of the base, tiled -
+    pattern and bytes - at a level with two sparse products in the pattern, and on dense blocks"""
+    for copies, level, (n, rp, cc, cv) in ((4, 3, fr.laplacian_2d(8)), (3, 1, fr.dense_blocks((9, 5, 3))[:4])):
+        base = fr.Fsai(n, rp, cc, cv, level)
+        F = fr.Fsai(copies * n, *tiled.tile_csr(copies, n, rp, cc, cv), level)
+        got = (F.rp.astype(np.int32), F.cc.astype(np.int32), F.values)
+        assert tiled.tiled_mismatch(got, (base.rp, base.cc, base.values), copies, n) is None
+        assert (F.nnz, F.max_row) == (copies * base.nnz, base.max_row)
+    # ... and a value of a later copy one ulp off is named by copy, row, m and trip
+    case = fr.grid_loop_case(16)
+    ref, k = case["ref"], 3
+    want = tiled.tile_csr(k, case["n"], ref.rp, ref.cc, ref.values)
+    row = int(np.flatnonzero(case["m"] > 8)[0])
+    val = want[2].copy()
+    at = 2 * ref.nnz + int(ref.rp[row])
+    val[at] = np.nextafter(val[at], -np.inf)
+    said = tiled.tiled_mismatch((want[0], want[1], val), (ref.rp, ref.cc, ref.values), k, case["n"], case["where"])
+    assert said.startswith(f"val[{at}] ") and f"copy 2, row {row} (m = {int(case['m'][row])}, place {2 * case['rows']} of class of 16 lanes, trip 0)" in said, said
+
+
+# lanes: (rows of the class in a copy, copies): the figures the GPU test's sizes rest on
+GRID_LOOP_SIZES = {4: (9, 14564), 8: (49, 1338), 16: (45, 729), 32: (43, 382), 64: (47, 131)}
+
+
+@pytest.mark.parametrize("lanes", sorted(fr.GRID_LOOP_BASES))
+def test_the_grid_loop_cases_reach_a_second_trip(lanes):
+    """the coverage conditions of tests/test_gpu_fsai.py's later-trip test, without a GPU"""
+    case = fr.grid_loop_case(lanes)
+    k, rows, groups, grid = case["copies"], case["rows"], case["groups"], case["grid"]
+    print(f"{lanes} lanes: {k} copies x {rows} rows = {k * rows}, {groups} groups a workgroup, {grid} workgroups: "
+          f"{tiled.trips(k * rows, groups, grid)} trips; n = {k * case['n']}, nnz(A) = {k * len(case['cc'])}, nnz(G) = {k * case['ref'].nnz}")
+    assert (rows, k) == GRID_LOOP_SIZES[lanes]
+    assert k * rows > groups * grid >= (k - 1) * rows and (groups * grid) % rows != 0 and tiled.trips(k * rows, groups, grid) == 2
+    assert groups == {4: 64, 8: 32, 16: 16, 32: 8, 64: 3}[lanes]
+    m = case["m"][np.array([tiled.fsai_class_of(x) for x in case["m"]]) == tiled.fsai_lanes().index(lanes)]
+    assert lanes // 2 < m.min() <= m.max() <= lanes if lanes > 4 else m.max() <= 4
+    assert len(set(m.tolist())) > 1, "rows of different lengths follow one another in a group"
 
 
 @pytest.mark.parametrize("system", fr.SOLVER_SYSTEMS)

@@ -12,7 +12,10 @@ Problems - the smallest that reach each path (pattern sizes: tests/test_fsai_ref
   random_symmetric    1        30,000 rows, unsorted columns, the diagonal entry stored twice, stored zeros: m up to 13; level 2 has a
                                row of 81 and is the realistic refusal
   diagonal            1        diag(4^k): G = diag(2^-k) and z = r / d bit for bit
-The twin of a (problem, level) is computed once and shared.  test_every_case_ran asserts at the end that every case ran."""
+The twin of a (problem, level) is computed once and shared.  test_every_case_ran asserts at the end that every case ran.
+Section 7 takes every lane class of the row kernel on a later trip over its grid, with block-diagonal copies of bases of a few
+rows (fsai_ref.GRID_LOOP_BASES, tests/tiled.py): more rows than any problem above, and the twin runs on the base alone."""
+import functools
 import gc
 from collections import defaultdict
 
@@ -22,6 +25,7 @@ import pytest
 import fsai_ref as fr
 import oracle_lib as ol
 import solver_ref
+import tiled
 
 pytestmark = pytest.mark.gpu
 
@@ -395,7 +399,49 @@ def test_destroying_the_handle_gives_the_memory_back(ctx, pkg):
     RUNS["state"] += 1
 
 
-# ---- 7. coverage ------------------------------------------------------------------------------------------------------------------------
+# ---- 7. later trips over the grid -------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _grid_loop_case(lanes):
+    return fr.grid_loop_case(lanes)
+
+
+@pytest.mark.parametrize("lanes", sorted(fr.GRID_LOOP_BASES))
+def test_rows_on_a_later_trip_over_the_grid_repeat_the_first_trip(ctx, pkg, lanes):
+    """fsai_rows_kernel launches at most kMaxGrid workgroups and loops beyond; on a later trip a group starts from the LDS its row
+    before left behind.  Block-diagonal copies of a small base (tests/tiled.py) put more rows into the class of `lanes` lanes than
+    one trip takes: G's pattern is the base twin's tiled, the values of every copy are the bytes of copy 0, and copy 0 is held to
+    the base twin as test_factor_application_and_state_match_the_twin holds a factor."""
+    case = _grid_loop_case(lanes)
+    n0, rp0, cc0, cv0, level, ref, k = case["n"], case["rp"], case["cc"], case["cv"], case["level"], case["ref"], case["copies"]
+    rows, groups, grid = case["rows"], case["groups"], case["grid"]
+    print(f"{lanes} lanes: {k} copies x {rows} rows = {k * rows} > {groups} x {grid} = {groups * grid}: {tiled.trips(k * rows, groups, grid)} trips; "
+          f"n = {k * n0}, nnz(G) = {k * ref.nnz}, level {level}")
+    assert k * rows > groups * grid, f"the class of {lanes} lanes makes one trip over the grid: nothing of this test is left"
+    assert (groups * grid) % rows != 0, f"{rows} rows a copy divide a trip of the class of {lanes} lanes: every trip holds the same rows"
+    n = k * n0
+    A = ctx.csr(n, n, *tiled.tile_csr(k, n0, rp0, cc0, cv0))
+    ctx.fsai_setup(A, level)
+    g_rp, g_cc, g_val = ctx.fsai_factor(A)
+    # the pattern integer for integer, the values of every copy the bytes of copy 0
+    nnz0 = ref.nnz
+    bad = tiled.tiled_mismatch((g_rp, g_cc, g_val), (ref.rp.astype(np.int32), ref.cc.astype(np.int32), g_val[:nnz0]), k, n0, case["where"])
+    assert bad is None, bad
+    # copy 0 against the base twin, and the two facts that define G from the engine's first n0 rows, in np.longdouble
+    _close(g_val[:nnz0], ref.values, f"{lanes} lanes: values of copy 0")
+    diag, off = fr.residuals(n0, rp0, cc0, cv0, g_rp[:n0 + 1], g_cc[:nnz0], g_val[:nnz0])
+    print(f"{lanes} lanes: (G A G^T)_ii - 1: {diag:.2f} eps, (G A)_ij on S: {off:.2f} eps")
+    assert diag <= solver_ref.F * fr.DIAG_BOUND_EPS and off <= solver_ref.F * fr.OFF_BOUND_EPS, (diag, off)
+    assert ctx.fsai_info(A) == (level, k * nnz0, ref.max_row) and A.get_param("fsai_max_row") == ref.max_row
+    # the application against G^T (G r) formed on the host from the downloaded G
+    r_host = np.random.default_rng(23).uniform(-1, 1, n)
+    r, z = ctx.vector_from(r_host), ctx.vector(n)
+    z.fill(7.0)
+    ctx.fsai_solve(A, r, z)
+    ctx.sync()
+    _close(z.download(), fr.apply_factor(n, g_rp, g_cc, g_val, r_host), f"{lanes} lanes: application")
+
+
+# ---- 8. coverage ------------------------------------------------------------------------------------------------------------------------
 def test_every_case_ran():
     expect = {"factor": len(CASES), "bits": len(BITS_CASES), "cap": 1, "edges": 1, "cg": 3 * len(fr.SOLVER_SYSTEMS), "reuse": 1, "others": 1,
               "refusals": 1, "state": 1}

@@ -25,6 +25,9 @@ CASES = {
     "random300_one_sided": lambda: rr.one_sided_noisy(rr.shuffled(rr.random_graph(300, 200, 8), 9), 10),
     "band2000": lambda: rr.shuffled(rr.band(2000, 40, 6, 3), 4),     # the workload of tools/bench_reorder.py
 }
+# a frontier wider than one trip of the breadth-first kernels over their grid, for 4, 16 and 64 lanes a vertex; the first two also
+# hold more rows than one trip of the 16-lanes-a-row kernels (the adjacency, the permutation's keys, the bandwidth)
+CASES.update({name: build for name, (build, _) in rr.GRID_LOOP_GRAPHS.items()})
 
 
 @functools.lru_cache(maxsize=None)
@@ -41,6 +44,15 @@ def _bytes_equal(got, want, what):
 @pytest.mark.parametrize("name", list(CASES))
 def test_order_equals_the_twin_and_the_permuted_matrix_meets_the_bound(ctx, name):
     (n, rp, col, val), (order, inverse, counters, widths) = _case(name)
+    if name in rr.GRID_LOOP_GRAPHS:  # the second trip is really taken: a changed generator or setting fails here
+        lanes, widest, one_trip, one_trip_of_rows = rr.grid_loop_facts(n, rp, col, widths, counters["isolated"])
+        print(f"{name}: n = {n}, {lanes} lanes a vertex, widest frontier {widest} > {one_trip}: {-(-widest // one_trip)} trips; "
+              f"the row kernels loop beyond {one_trip_of_rows} rows: {-(-n // one_trip_of_rows)} trips")
+        assert lanes == rr.GRID_LOOP_GRAPHS[name][1], f"{name} was built for {rr.GRID_LOOP_GRAPHS[name][1]} lanes a vertex"
+        assert widest > one_trip, f"{name}: the breadth-first kernels make one trip over the grid: nothing of this case is left"
+        later = rr.later_trip_children(n, rp, col, order, widths, one_trip)
+        print(f"{name}: {later} vertices have their first parent beyond one trip: only the later trip can claim them")
+        assert later > 0 or name == "random20000_deg40", f"{name}: the later trip has nothing to find"  # (hairy8300_deg38 is why)
     A = ctx.csr(n, n, rp, col, val)
     p = ctx.perm_rcm(A)
     got_order, got_inverse = p.download()

@@ -1,6 +1,7 @@
 """spmv_spgemm and spmv_csr_transpose on the GPU against their NumPy twin (tests/spgemm_ref.py), as bytes: row_ptr, col and val of
 every result under ROWS, SORT and AUTO, the result's own validation and its "spgemm_*" parameters; the class edges and the capacity
-read from the settings header and from "spgemm_lds_products"; a hub on the sort path spliced among short rows; the transpose; the
+read from the settings header and from "spgemm_lds_products"; block-diagonal copies that take the wavefront and the workgroup class
+on later trips over the grid (tests/tiled.py); a hub on the sort path spliced among short rows; the transpose; the
 Galerkin product against spmv_amg_setup's level 1; the result as a handle; device memory around results and a refused call."""
 import functools
 import re
@@ -11,6 +12,7 @@ import pytest
 
 import exact
 import spgemm_ref as sr
+import tiled
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -133,6 +135,41 @@ def test_class_edges_and_the_capacity(ctx, one_column):
             sorted_rows = 1 if (label == "SORT" or c > caps[-1]) else 0
             assert (C.get_param("spgemm_rows_lds"), C.get_param("spgemm_rows_sorted")) == (1 - sorted_rows, sorted_rows), (c, label)
             assert C.get_param("spgemm_products") == c
+
+
+def test_rows_on_a_later_trip_over_the_grid_repeat_the_first_trip(ctx):
+    """spgemm_rows_kernel launches at most kMaxGrid workgroups and loops beyond: block-diagonal copies of sr.class_edge_pair put
+    8200 rows into the wavefront class (4 a workgroup: two trips) and into the workgroup class (1 a workgroup: five), and C must
+    be the base twin tiled (tests/tiled.py).  Five rows of a class a copy do not divide a trip's rows, so a workgroup meets rows of
+    another length - another network size - on its later trips, and rows of different network sizes side by side."""
+    case = sr.grid_loop_case()
+    m0, k0, n0, grid, k = case["m"], case["k"], case["n"], case["grid"], case["copies"]
+    rp0, cc0, cv0, ub0 = case["twin"]
+    assert tuple(int(u) for u in ub0) == sr.CLASS_EDGE_UB, "the twin counts the products the rows were built for"
+    caps = _capacities()
+    assert caps == case["caps"]
+    for c, (label, rows, per_group) in case["looping"].items():
+        lo, hi = case["caps"][c - 2], case["caps"][c - 1]
+        have = sorted(int(u) for u in ub0[case["cls"] == c])
+        assert have[0] == lo + 1 and have[-1] == hi, f"both edges of class {label}: {have}"
+        assert any(p in have and p + 1 in have for p in (1 << b for b in range(1, 12))), f"a full network and one over in class {label}: {have}"
+        print(f"class {label}: {k} copies x {rows} rows = {k * rows} > {per_group} x {grid} = {per_group * grid}: "
+              f"{tiled.trips(k * rows, per_group, grid)} trips")
+        assert k * rows > per_group * grid, f"class {label} makes one trip over the grid: nothing of this test is left"
+        assert (per_group * grid) % rows != 0, f"{rows} rows a copy divide a trip of class {label}: every trip holds the same rows"
+    A, B = tiled.tile_csr(k, k0, *case["A"]), tiled.tile_csr(k, n0, *case["B"])
+    products, nonempty = k * int(ub0.sum()), k * int(np.sum(ub0 > 0))
+    assert int(ub0.max()) <= caps[-1]
+    for label, method in METHODS:
+        C = _product(ctx, k * m0, k * k0, k * n0, A, B, method)
+        assert (C.info.nrow, C.info.ncol, C.info.nnz) == (k * m0, k * n0, k * len(cc0)), label
+        bad = tiled.tiled_mismatch(C.download(), (rp0, cc0, cv0), k, n0, case["where"])
+        assert bad is None, f"under {label}: {bad}"
+        C.validate()
+        on_sort = nonempty if label == "SORT" else 0
+        assert C.get_param("spgemm_products") == products, label
+        assert (C.get_param("spgemm_rows_lds"), C.get_param("spgemm_rows_sorted")) == (nonempty - on_sort, on_sort), label
+        del C
 
 
 @pytest.mark.parametrize("m, k, n", [(0, 3, 4), (3, 0, 4), (3, 2, 0), (0, 0, 0)])

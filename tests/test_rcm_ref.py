@@ -47,6 +47,36 @@ def test_the_random_families_are_what_their_names_say():
     assert c["components"] == 24 and c["isolated"] == 82, c
 
 
+@pytest.mark.parametrize("name", list(rr.GRID_LOOP_GRAPHS))
+def test_the_grid_loop_graphs_reach_a_second_trip(name):
+    """the coverage conditions of the wide-frontier cases of tests/test_gpu_reorder.py, without a GPU: the lanes a vertex that the
+    mean degree selects, a frontier wider than one trip of those lanes over the grid, vertices that only the later trip can claim,
+    and - all together - every lane count and more rows than one trip of the 16-lanes-a-row kernels"""
+    build, want_lanes = rr.GRID_LOOP_GRAPHS[name]
+    n, rp, col, val = build()
+    order, _, counters, widths = rr.rcm_levelwise(n, rp, col)
+    lanes, widest, one_trip, one_trip_of_rows = rr.grid_loop_facts(n, rp, col, widths, counters["isolated"])
+    print(f"{name}: n = {n}, {len(col)} entries, {counters}, widths {widths[0] if len(widths) == 1 else len(widths)}, {lanes} lanes, "
+          f"widest {widest} against {one_trip}, rows against {one_trip_of_rows}")
+    assert lanes == want_lanes and widest > one_trip and counters["components"] == 1
+    assert (n > one_trip_of_rows) == (name in ("broom131200", "random100000_deg10"))
+    assert np.array_equal(np.sort(order), np.arange(n))
+    assert sorted({l for _, l in rr.GRID_LOOP_GRAPHS.values()}) == [4, 16, 64]
+    # what only a later trip can find: the vertices whose first parent stands beyond one trip in its frontier.  random20000_deg40
+    # has none - about 29 parents a vertex, the first of them early - which is why hairy8300_deg38 stands beside it
+    later = rr.later_trip_children(n, rp, col, order, widths, one_trip)
+    print(f"{name}: {later} vertices are claimed on a later trip")
+    assert later == {"broom131200": 254, "random100000_deg10": 1019, "random20000_deg40": 0, "hairy8300_deg38": 107}[name]
+    if name == "hairy8300_deg38":  # a leaf, its parent, the root and the parent's siblings, the other children and the siblings' leaves, leaves
+        assert widths[0][:2] == [1, 1] and widths[0][3] == 8299
+    if name == "broom131200":  # a leaf, its parent, the root and the leaf's sibling, the other children, their leaves
+        assert widths[0][:4] == [1, 1, 2, 131_199] and rr.bandwidth_profile(n, rp, col)[0] > n // 2
+    if name == "random100000_deg10":
+        assert widths == [[1, 1, 11, 120, 1227, 11394, 59115, 28065, 65]] and counters["isolated"] == 1
+    if name == "random20000_deg40":
+        assert widths == [[1, 19, 714, 14626, 4640]]
+
+
 def test_a_shuffled_path_comes_back_with_bandwidth_one():
     n, rp, col, val = rr.shuffled(rr.path(1025), 11)
     assert rr.bandwidth_profile(n, rp, col)[0] > 100

@@ -7,6 +7,7 @@ import pytest
 import amg_ref
 import exact
 import spgemm_ref as sr
+import tiled
 
 
 def _dense(nrow, ncol, M):
@@ -100,6 +101,59 @@ def test_transpose_twin():
     back = sr.transpose_twin(n, m, (rp, cc, cv))
     want = sr.sorted_columns(m, A)
     assert all(np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(back, want))
+
+
+def test_block_diagonal_copies_tile_the_twin():
+    """the oracle of the GPU test's later trips over the grid (tests/tiled.py): the twin of k copies is the twin of the base, tiled"""
+    for copies, (m, k, n, A, B) in ((5, sr.order_sensitive_pair()), (3, sr.class_edge_pair()), (1, sr.cancelling_pair())):
+        base = sr.spgemm_twin(m, k, n, A, B)
+        got = sr.spgemm_twin(copies * m, copies * k, copies * n, tiled.tile_csr(copies, k, *A), tiled.tile_csr(copies, n, *B))
+        assert tiled.tiled_mismatch(got[:3], base[:3], copies, n) is None
+        assert np.array_equal(got[3], np.tile(base[3], copies))
+        want = tiled.tile_csr(copies, n, *base[:3])
+        assert all(np.asarray(g).dtype == w.dtype and np.asarray(g).tobytes() == w.tobytes() for g, w in zip(got[:3], want))
+
+
+def test_the_grid_loop_case_reaches_later_trips_and_names_what_differs():
+    """the coverage conditions of tests/test_gpu_spgemm.py's later-trip test, without a GPU, and its reporter: a tiled result with one
+    value of the last copy moved by one ulp, one column changed, one row one entry short - each named by copy, row, class and trip"""
+    case = sr.grid_loop_case()
+    k, n, grid = case["copies"], case["n"], case["grid"]
+    rp0, cc0, cv0, ub0 = case["twin"]
+    assert tuple(int(u) for u in ub0) == sr.CLASS_EDGE_UB and len(cc0) > 0
+    assert {c: v[0] for c, v in case["looping"].items()} == {2: "wave", 3: "block"}
+    for label, rows, per_group in case["looping"].values():
+        print(f"class {label}: {k * rows} rows, {per_group} a workgroup, {grid} workgroups: {tiled.trips(k * rows, per_group, grid)} trips")
+        assert k * rows > per_group * grid and (per_group * grid) % rows != 0 and tiled.trips(k * rows, per_group, grid) >= 2
+    assert any((k - 2) * rows <= per_group * grid for _, rows, per_group in case["looping"].values()), "no more copies than a second trip needs"
+    good = tiled.tile_csr(k, n, rp0, cc0, cv0)
+    assert tiled.tiled_mismatch(good, (rp0, cc0, cv0), k, n, case["where"]) is None
+    wave_rows, block_rows = np.flatnonzero(case["cls"] == 2), np.flatnonzero(case["cls"] == 3)
+    last = k - 1
+    # a value of the last workgroup-class row of the last copy, one ulp off
+    row, place = int(block_rows[-1]), last * len(block_rows) + len(block_rows) - 1
+    val = good[2].copy()
+    at = last * len(cc0) + int(rp0[row]) + 1
+    val[at] = np.nextafter(val[at], np.inf)
+    said = tiled.tiled_mismatch((good[0], good[1], val), (rp0, cc0, cv0), k, n, case["where"])
+    assert said.startswith(f"val[{at}] ") and f"copy {last}, row {row} (place {place} of class block, trip {place // grid})" in said, said
+    assert place // grid >= 1
+    # a column of the last wavefront-class row of the last copy
+    row, place = int(wave_rows[-1]), last * len(wave_rows) + len(wave_rows) - 1
+    col = good[1].copy()
+    at = last * len(cc0) + int(rp0[row + 1]) - 1
+    col[at] += 1
+    said = tiled.tiled_mismatch((good[0], col, good[2]), (rp0, cc0, cv0), k, n, case["where"])
+    per_group = case["looping"][2][2]
+    assert said.startswith(f"col[{at}] ") and f"copy {last}, row {row} (place {place} of class wave, trip {place // per_group // grid})" in said, said
+    assert place // per_group // grid == 1
+    # a row of copy 1 one entry short: the first row_ptr that differs closes that row
+    rp = good[0].copy()
+    rp[len(rp0) - 1 + row + 1:] -= 1
+    said = tiled.tiled_mismatch((rp, good[1], good[2]), (rp0, cc0, cv0), k, n, case["where"])
+    assert said.startswith("row_ptr[") and f"copy 1, row {row} (place {len(wave_rows) + len(wave_rows) - 1} of class wave, trip 0)" in said, said
+    # another shape or type is said as such
+    assert "int64" in tiled.tiled_mismatch((good[0].astype(np.int64), good[1], good[2]), (rp0, cc0, cv0), k, n)
 
 
 @pytest.mark.parametrize("mutant", sr.MUTANTS)
