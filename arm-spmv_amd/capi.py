@@ -16,11 +16,12 @@ import numpy as np
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("SPMV_HIP_SO") or _PKG / "lib" / "libspmv_hip.so")  # override: A/B against another build
 
-FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA, FMT_BSR = 0, 1, 2, 3, 4, 5
+FMT_COO, FMT_CSR, FMT_CSC, FMT_ELL, FMT_DIA, FMT_BSR, FMT_CSR_F32 = 0, 1, 2, 3, 4, 5, 6
 CSR_AUTO, CSR_VECTOR, CSR_LDSWIN, CSR_SCALAR, CSR_PANEL, CSR_TWOPHASE, CSR_SEGSCAN, CSR_SPLIT, CSR_ELL = 0, 1, 2, 3, 4, 5, 6, 7, 8
 AMG_RESTRICT_FUSED, AMG_RESTRICT_UNFUSED, AMG_PROLONG_FUSED, AMG_PROLONG_UNFUSED = 0, 1, 2, 3  # spmv_amg_transfer_timed
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0, PRECOND_CHEBYSHEV, PRECOND_AMG = 0, 1, 2, 3, 4, 5
 PRECOND_FSAI = 6
+REFINE_CG, REFINE_BICGSTAB = 0, 1  # spmv_refine's inner solver
 FSAI_MAX_ROW = 64  # SPMV_FSAI_MAX_ROW: the cap on the pattern columns of a row of G
 SPGEMM_AUTO, SPGEMM_ROWS, SPGEMM_SORT = 0, 1, 2  # spmv_spgemm's method
 FLAG_DPP_REDUCE, FLAG_XCD_REMAP = 1, 2
@@ -153,6 +154,12 @@ SIGNATURES = {
     "spmv_bsr_wrap_device": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.POINTER(_vp)]),
     "spmv_csr_to_bsr": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(_vp)]),
     "spmv_bsr_to_csr": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(_vp)]),
+    "spmv_csr_to_f32": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "spmv_csr_f32_upload": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "spmv_f32_to_csr": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "spmv_f32_info": (C.c_int, [_vp, _i64p, _i64p, _f64p]),
+    "spmv_refine": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f64p]),
     "spmv_csr_split_columns": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.POINTER(_vp), C.POINTER(_vp)]),
     "spmv_partition_rows": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, _i64p, _i64p]),
     "spmv_partition_rows_balanced": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp]),
@@ -360,6 +367,13 @@ class Context:
         rp, c, v = _host(brow_ptr, np.int32), _host(bcol, np.int32), _host(val, np.float64)
         h = _vp()
         _check(self._lib.spmv_bsr_upload(self.h, nrow, ncol, bs, _ptr(rp), _ptr(c), _ptr(v), C.byref(h)))
+        return Matrix(self, h)
+
+    def csr_f32(self, nrow, ncol, row_ptr, col, val) -> "Matrix":
+        """CSR with single-precision value storage (spmv_csr_f32_upload): val is taken as float32; packed on the device"""
+        rp, c, v = _host(row_ptr, np.int32), _host(col, np.int32), _host(val, np.float32)
+        h = _vp()
+        _check(self._lib.spmv_csr_f32_upload(self.h, nrow, ncol, _ptr(rp), _ptr(c), _ptr(v), C.byref(h)))
         return Matrix(self, h)
 
     def csc(self, nrow, ncol, col_ptr, row, val) -> "Matrix":
@@ -688,6 +702,17 @@ class Context:
         _check(self._lib.spmv_gmres(self.h, A.h, b.h, x.h, restart, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))
         return it.value, res.value
 
+    def refine(self, A: "Matrix", A_lo: "Matrix", b: "Vector", x: "Vector", solver: int = REFINE_CG, precond: int = PRECOND_NONE, max_outer: int = 20,
+               inner_max_iter: int = 1000, inner_tol: float = 1e-4, rel_tol: float = 1e-12):
+        """iterative refinement (spmv_refine) from the x passed in: r = b - A x in fp64 with A, the correction from `solver`
+        (REFINE_CG / REFINE_BICGSTAB, `precond` as that solver takes it) on A_lo - a format-6 copy of A is the intended use - to
+        inner_tol, x += d; stops at ||r|| <= rel_tol ||b||, after max_outer steps, or where a step does not reduce ||r|| (x goes
+        back to the best iterate).  Returns (outer steps, inner iterations in all, ||b - A x|| / ||b||)"""
+        outer, inner, res = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+        _check(self._lib.spmv_refine(self.h, A.h, A_lo.h, b.h, x.h, solver, precond, max_outer, inner_max_iter, inner_tol, rel_tol, C.byref(outer),
+                                     C.byref(inner), C.byref(res)))
+        return outer.value, inner.value, res.value
+
     def block_gram(self, n: int, p: int, U: "Vector", ldu: int, q: int, V: "Vector", ldv: int) -> np.ndarray:
         """G = U^T V (p, q) of two column-major blocks (column c at c * ld, ld >= n; rows n .. ld - 1 are padding that is never
         touched), synchronous; 1 <= p, q <= 96.  Deterministic, and exactly symmetric where U and V are the same block"""
@@ -787,6 +812,19 @@ class Context:
         """the BSR handle of a CSR handle (spmv_csr_to_bsr), on the device: block columns ascending, duplicates added in stored order"""
         h = _vp()
         _check(self._lib.spmv_csr_to_bsr(self.h, A.h, bs, C.byref(h)))
+        return Matrix(self, h)
+
+    def csr_to_f32(self, A: "Matrix") -> "Matrix":
+        """the format-6 handle of a CSR handle (spmv_csr_to_f32), on the device: every value rounded to float, nearest-even; what the
+        rounding did is Matrix.f32_info.  A value that is not finite or rounds to +-inf: SpmvError (SPMV_ERR_INVALID)"""
+        h = _vp()
+        _check(self._lib.spmv_csr_to_f32(self.h, A.h, C.byref(h)))
+        return Matrix(self, h)
+
+    def f32_to_csr(self, A: "Matrix") -> "Matrix":
+        """the fp64 CSR handle of a format-6 handle's widened values (spmv_f32_to_csr): exact"""
+        h = _vp()
+        _check(self._lib.spmv_f32_to_csr(self.h, A.h, C.byref(h)))
         return Matrix(self, h)
 
     def bsr_to_csr(self, A: "Matrix", drop_zeros: bool = True) -> "Matrix":
@@ -943,6 +981,13 @@ class Matrix:
         """build exactly the kernel and layout of `plan` (from get_plan of a handle of the same format), no timing launch"""
         _check(self.ctx._lib.spmv_mat_set_plan(self.h, plan, len(plan)))
 
+    def f32_info(self) -> tuple[int, int, float]:
+        """(values that changed, nonzero values that became zero or subnormal, largest relative change among the others) of the
+        rounding that made this format-6 handle (spmv_f32_info); zeros for an uploaded one"""
+        inexact, underflow, rel = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+        _check(self.ctx._lib.spmv_f32_info(self.h, C.byref(inexact), C.byref(underflow), C.byref(rel)))
+        return inexact.value, underflow.value, rel.value
+
     def set_flags(self, flags: int) -> None:
         _check(self.ctx._lib.spmv_mat_set_flags(self.h, flags))
 
@@ -956,7 +1001,7 @@ class Matrix:
         """(a, b, v) host copies; see spmv_mat_download for which array is which per format"""
         i = self.info
         fmt = i.format
-        if fmt == FMT_CSR:
+        if fmt == FMT_CSR or fmt == FMT_CSR_F32:  # (format 6: the columns and the values widened to double, out of the packed stream)
             na, nb, nv = i.nrow + 1, i.nnz, i.nnz
         elif fmt == FMT_COO:
             na = nb = nv = i.nnz

@@ -98,6 +98,7 @@ void mat_free(spmv_mat* m)
         if (m->b) (void)hipFree(const_cast<int32_t*>(m->b));
         if (m->v) (void)hipFree(const_cast<double*>(m->v));
     }
+    if (m->f32_ent) (void)hipFree(m->f32_ent);
     if (m->win_lo) (void)hipFree(m->win_lo);
     if (m->win_span) (void)hipFree(m->win_span);
     ell_layouts_free(m);
@@ -161,6 +162,7 @@ static int finish(spmv_mat* m, spmv_mat** out)
     if (rc == SPMV_OK && m->format == SPMV_FMT_CSC) rc = csc_analyse(m);
     if (rc == SPMV_OK && m->format == SPMV_FMT_ELL) rc = ell_analyse(m);
     if (rc == SPMV_OK && m->format == SPMV_FMT_BSR) rc = bsr_analyse(m);
+    if (rc == SPMV_OK && m->format == SPMV_FMT_CSR_F32) rc = csr_f32_analyse(m);
     if (rc != SPMV_OK)
     {
         mat_free(m);
@@ -711,6 +713,50 @@ int spmv_bsr_to_csr(spmv_ctx* ctx, const spmv_mat* bsr, int32_t drop_zeros, spmv
     return finish(m, out_csr);
 }
 
+// ---- CSR with single-precision value storage (format 6): the handle keeps the row pointer and one stream of packed entries ---------
+int spmv_csr_to_f32(spmv_ctx* ctx, const spmv_mat* csr, spmv_mat** out_f32)
+{
+    SPMV_REQUIRE(ctx && csr && out_f32, "spmv_csr_to_f32: null argument");
+    SPMV_TRY(csr_to_f32_check(ctx, csr, "spmv_csr_to_f32"));
+    SPMV_TRY(use_device(ctx));
+    spmv_mat* m = nullptr;
+    SPMV_TRY(csr_to_f32(ctx, csr, "spmv_csr_to_f32", &m));
+    return finish(m, out_f32);  // validates and analyses like an uploaded handle (frees on failure)
+}
+
+int spmv_csr_f32_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, const int32_t* row_ptr, const int32_t* col_ind, const float* values, spmv_mat** out)
+{
+    SPMV_REQUIRE(ctx && out && row_ptr, "spmv_csr_f32_upload: null argument");
+    SPMV_REQUIRE(nrow >= 0 && ncol >= 0, "spmv_csr_f32_upload: bad size %d x %d", nrow, ncol);
+    const int64_t nnz = (int64_t)row_ptr[nrow] - row_ptr[0];
+    SPMV_REQUIRE(row_ptr[0] == 0 && nnz >= 0 && (nnz == 0 || (col_ind && values)), "spmv_csr_f32_upload: row_ptr[0]=%d, nnz=%lld", row_ptr[0], (long long)nnz);
+    SPMV_TRY(use_device(ctx));
+    spmv_mat* m = nullptr;
+    SPMV_TRY(csr_f32_from_host(ctx, nrow, ncol, nnz, row_ptr, col_ind, values, &m));
+    return finish(m, out);
+}
+
+int spmv_f32_to_csr(spmv_ctx* ctx, const spmv_mat* f32, spmv_mat** out_csr)
+{
+    SPMV_REQUIRE(ctx && f32 && out_csr, "spmv_f32_to_csr: null argument");
+    SPMV_TRY(f32_to_csr_check(ctx, f32, "spmv_f32_to_csr"));
+    SPMV_TRY(use_device(ctx));
+    plan_arm  arm(ctx);
+    spmv_mat* m = nullptr;
+    SPMV_TRY(f32_to_csr(ctx, f32, "spmv_f32_to_csr", &m));
+    return finish(m, out_csr);
+}
+
+int spmv_f32_info(const spmv_mat* f32, int64_t* inexact, int64_t* underflow, double* max_rel_err)
+{
+    SPMV_REQUIRE(f32, "spmv_f32_info: null matrix");
+    if (f32->format != SPMV_FMT_CSR_F32) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_f32_info: the input must be a handle of format 6 (format %d)", f32->format);
+    if (inexact) *inexact = f32->f32_inexact;
+    if (underflow) *underflow = f32->f32_underflow;
+    if (max_rel_err) *max_rel_err = f32->f32_max_rel;
+    return SPMV_OK;
+}
+
 int spmv_mat_destroy(spmv_mat* m)
 {
     if (!m) return SPMV_OK;
@@ -749,6 +795,7 @@ int spmv_mat_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes_per_row)
     SPMV_REQUIRE(m, "null matrix");
     SPMV_REQUIRE(kernel >= SPMV_CSR_AUTO && kernel <= SPMV_CSR_ELL, "unknown kernel id %d", kernel);
     if (m->format == SPMV_FMT_BSR) return bsr_set_kernel(m, kernel, lanes_per_row);  // (its lanes per block row are multiples of bs * bs)
+    if (m->format == SPMV_FMT_CSR_F32) return csr_f32_set_kernel(m, kernel, lanes_per_row);  // (one kernel; anything else: UNSUPPORTED)
     SPMV_REQUIRE(lanes_per_row == 0 || (lanes_per_row >= 1 && lanes_per_row <= 64 &&
                                         (lanes_per_row & (lanes_per_row - 1)) == 0),
                  "lanes_per_row must be 0 or a power of two in 1..64, got %d", lanes_per_row);
@@ -1076,6 +1123,8 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
 int spmv_mat_set_flags(spmv_mat* m, uint32_t flags)
 {
     SPMV_REQUIRE(m, "null matrix");
+    if (m->format == SPMV_FMT_CSR_F32 && flags)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_mat_set_flags: a handle of format 6 has one kernel and takes no tuning bits (flags = 0x%x)", flags);
     m->flags = flags;
     return SPMV_OK;
 }
@@ -1093,6 +1142,30 @@ int spmv_mat_download(const spmv_mat* m, int32_t* a, int32_t* b, double* v)
         case SPMV_FMT_CSC: na = (size_t)m->ncol + 1; nb = nv = (size_t)m->nnz; break;
         case SPMV_FMT_DIA: na = (size_t)m->k; nv = (size_t)m->nrow * (size_t)m->k; break;
         case SPMV_FMT_BSR: na = (size_t)ceil_div(m->nrow, m->k) + 1; nb = (size_t)(m->nnz / (m->k * m->k)); nv = (size_t)m->nnz; break;
+        case SPMV_FMT_CSR_F32:
+        {
+            // the row pointer as it is; the columns and the values - widened to double - out of the packed stream, through set-up memory
+            const size_t nnz = (size_t)m->nnz;
+            hipStream_t  s   = m->ctx->stream;
+            if (a) SPMV_HIP(hipMemcpyAsync(a, m->a, ((size_t)m->nrow + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            void *   d_b = nullptr, *d_v = nullptr;
+            int      rc  = SPMV_OK;
+            if (nnz && b && hipMalloc(&d_b, nnz * sizeof(int32_t)) != hipSuccess) rc = SPMV_ERR_ALLOC;
+            if (rc == SPMV_OK && nnz && v && hipMalloc(&d_v, nnz * sizeof(double)) != hipSuccess) rc = SPMV_ERR_ALLOC;
+            if (rc == SPMV_ERR_ALLOC)
+            {
+                (void)hipGetLastError();
+                set_error("spmv_mat_download: out of device memory for %zu widened entries of a format 6 handle", nnz);
+            }
+            if (rc == SPMV_OK && (d_b || d_v)) rc = f32_widen_arrays(m->ctx, m, (int32_t*)d_b, (double*)d_v);
+            if (rc == SPMV_OK && d_b && hipMemcpyAsync(b, d_b, nnz * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) rc = SPMV_ERR_HIP;
+            if (rc == SPMV_OK && d_v && hipMemcpyAsync(v, d_v, nnz * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) rc = SPMV_ERR_HIP;
+            if (hipStreamSynchronize(s) != hipSuccess && rc == SPMV_OK) rc = SPMV_ERR_HIP;
+            if (rc == SPMV_ERR_HIP) set_error("spmv_mat_download: %s", hipGetErrorString(hipGetLastError()));
+            if (d_b) (void)hipFree(d_b);
+            if (d_v) (void)hipFree(d_v);
+            return rc;
+        }
         default: SPMV_FAIL(SPMV_ERR_INVALID, "unknown format %d", m->format);
     }
     SPMV_REQUIRE(!((b && nb && !m->b) || (v && nv && !m->v)), "spmv_mat_download: this handle gave up its arrays (panel_keep_csr = 0)");
@@ -1107,6 +1180,8 @@ int spmv_mat_download(const spmv_mat* m, int32_t* a, int32_t* b, double* v)
 int spmv_mat_device_ptrs(const spmv_mat* m, const int32_t** a, const int32_t** b, const double** v)
 {
     SPMV_REQUIRE(m, "null matrix");
+    if (m->format == SPMV_FMT_CSR_F32)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_mat_device_ptrs: a handle of format 6 holds one packed entry stream, no column and value arrays");
     if (a) *a = m->a;
     if (b) *b = m->b;
     if (v) *v = m->v;
@@ -1288,7 +1363,7 @@ int spmv_apply_host(spmv_ctx* ctx, const spmv_mat* A, const double* x_host, doub
         //     accumulator starts AT y_i (ELL, DIA, scalar CSR: the reference's order y0 + p0 + p1 + ...) keep y in place.
         const spmv_mat* K = A;  // the handle whose kernel runs
         while (runs_from_rowgrouped(K)) K = K->rowgrouped;
-        const bool sum_then_add = y_in_place && !kForceInPlace && K->format == SPMV_FMT_CSR && K->nnz > 0 && writes_row_sums_in_one_launch(K);
+        const bool sum_then_add = y_in_place && !kForceInPlace && (K->format == SPMV_FMT_CSR || K->format == SPMV_FMT_CSR_F32) && K->nnz > 0 && writes_row_sums_in_one_launch(K);
         if (nx && !ctx->large_bar) memcpy(hx, x_host, sizeof(double) * nx);
         if (!sum_then_add) memcpy(hy, y_host, sizeof(double) * ny);
         // x: where the CPU can store into device memory (large BAR) it writes x into the device buffer itself - 80 KB in 2 us,
@@ -1455,6 +1530,20 @@ int spmv_gmres(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x,
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
     return gmres_solve(ctx, A, b->d, x->d, restart == 0 ? 30 : restart, max_iter, rel_tol, check_every, precond, iters, rel_resid);
+}
+
+// iterative refinement: the residual with A in fp64, the correction from spmv_cg or spmv_bicgstab on A_lo (solver_refine.hip)
+int spmv_refine(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, const spmv_vec* b, spmv_vec* x, int32_t solver, int32_t precond,
+                int32_t max_outer, int32_t inner_max_iter, double inner_tol, double rel_tol, int32_t* outer, int32_t* inner_total, double* rel_resid)
+{
+    SPMV_TRY(check_refine(ctx, A, A_lo, b, x, solver, precond, max_outer, inner_max_iter, inner_tol, rel_tol, outer, inner_total, rel_resid));
+    SPMV_TRY(check_preconditioner(solver == SPMV_REFINE_CG ? kCgRules : kBicgstabRules, A_lo, precond));  // (the inner solver's own refusals)
+    *outer       = 0;
+    *inner_total = 0;
+    *rel_resid   = 0.0;
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return refine_solve(ctx, A, A_lo, b->d, x->d, solver, precond, max_outer, inner_max_iter, inner_tol, rel_tol, outer, inner_total, rel_resid);
 }
 
 // blocks: G = U^T V and Out = S C (block_ops.hip)
@@ -1879,6 +1968,8 @@ int spmv_mat_partition_rows(const spmv_mat* m, int32_t nparts, int32_t balance_e
     SPMV_REQUIRE(m && nparts > 0 && bounds, "spmv_mat_partition_rows: bad argument");
     if (m->format == SPMV_FMT_BSR && balance_entries)
         SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_mat_partition_rows: a BSR handle is not sharded: no partition by entries (balance_entries = 1)");
+    if (m->format == SPMV_FMT_CSR_F32 && balance_entries)
+        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_mat_partition_rows: a handle of format 6 is not sharded: no partition by entries (balance_entries = 1)");
     const int64_t n = m->format == SPMV_FMT_CSC ? m->ncol : m->nrow;
     // padded formats store the same number of slots for every row: equal rows ARE equal work
     if (!balance_entries || m->format == SPMV_FMT_ELL || m->format == SPMV_FMT_DIA || n == 0)

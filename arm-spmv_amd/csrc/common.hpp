@@ -194,8 +194,8 @@ struct spmv_mat
     int32_t   k         = 0;  // ELL slots / DIA ndiags / BSR block size bs
     int64_t   nnz       = 0;
     int64_t   row_begin = 0;
-    // a: row_ptr | row_ind | -       | col_ptr | offsets | block row_ptr
-    // b: col_ind | col_ind | col_ind | row_ind | -       | block col_ind   (CSR | COO | ELL | CSC | DIA | BSR)
+    // a: row_ptr | row_ind | -       | col_ptr | offsets | block row_ptr | row_ptr
+    // b: col_ind | col_ind | col_ind | row_ind | -       | block col_ind | -       (CSR | COO | ELL | CSC | DIA | BSR | CSR_F32: f32_ent below)
     const int32_t* a = nullptr;
     const int32_t* b = nullptr;
     const double*  v = nullptr;
@@ -368,8 +368,8 @@ struct spmv_mat
     int32_t                 ilu_order = 1;  // "ilu0_order": 1 multicolour (default), 0 the matrix's own row order
 
     // the transposed product (transpose.hip): a companion handle of A^T over A's arrays, or the DIA transposed kernel's set-up;
-    // built by spmv_mat_transpose_setup, no part of the forward state (kernel, copies, device_bytes, plan) - but for a BSR handle, whose
-    // companion owns its arrays and is counted in device_bytes
+    // built by spmv_mat_transpose_setup, no part of the forward state (kernel, copies, device_bytes, plan) - but for a BSR and a
+    // format-6 handle, whose companions own their arrays and are counted in device_bytes
     struct spmv::transpose_state* tr            = nullptr;
     int32_t                       tr_kernel_req = SPMV_CSR_AUTO;  // "transpose_kernel": handed to spmv_mat_set_kernel on the companion
 
@@ -394,6 +394,14 @@ struct spmv_mat
     // a handle that spmv_spgemm made (spgemm.hip): what that product did ("spgemm_*"; 0 on every other handle)
     bool    spgemm_made = false;
     int64_t spgemm_products = 0, spgemm_rows_lds = 0, spgemm_rows_sorted = 0, spgemm_transient_bytes = 0;
+
+    // single-precision value storage (SPMV_FMT_CSR_F32; kernels_csr_f32.hip, convert_f32.hip): `a` is the row pointer, b and v hold
+    // nothing; the entries are ONE stream of packed words (csr_f32_settings.hpp: column | float bits << 32), owned, counted in
+    // device_bytes.  What spmv_csr_to_f32's rounding did (zero on an uploaded handle): spmv_f32_info
+    uint64_t* f32_ent       = nullptr;  // [max(nnz, 1)]
+    int64_t   f32_inexact   = 0;        // values that changed
+    int64_t   f32_underflow = 0;        // nonzero values that became zero or subnormal
+    double    f32_max_rel   = 0.0;      // the largest relative change among the changed values that did not underflow
 };
 
 namespace spmv
@@ -583,6 +591,23 @@ int bsr_to_csr_check(const spmv_ctx* ctx, const spmv_mat* bsr, const char* who);
 int csr_to_bsr(spmv_ctx* ctx, const spmv_mat* csr, int32_t bs, spmv_mat** out);             // synchronous; analysed by the caller
 int bsr_to_csr(spmv_ctx* ctx, const spmv_mat* bsr, int32_t drop_zeros, spmv_mat** out);    // synchronous; analysed by the caller
 int bsr_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out);                       // synchronous; analysed
+// kernels_csr_f32.hip: CSR with single-precision value storage (what a product launches: csr_f32_settings.hpp)
+int csr_f32_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex = apply_extra{});
+int csr_f32_analyse(spmv_mat* m);
+int csr_f32_set_kernel(spmv_mat* m, int32_t kernel, int32_t lanes);  // spmv_mat_set_kernel on a format-6 handle
+int csr_pick_lanes(double mean_row);                                 // kernels_csr.hip: the row-parallel kernels' lanes per row from the mean row length
+// convert_f32.hip: the conversions and the handle of A^T (each check on the host, before the device is touched)
+int csr_to_f32_check(const spmv_ctx* ctx, const spmv_mat* csr, const char* who);
+int f32_to_csr_check(const spmv_ctx* ctx, const spmv_mat* f32, const char* who);
+int csr_to_f32(spmv_ctx* ctx, const spmv_mat* csr, const char* who, spmv_mat** out);  // synchronous; analysed by the caller
+int csr_f32_from_host(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int64_t nnz, const int32_t* row_ptr, const int32_t* col, const float* val,
+                      spmv_mat** out);                                                 // synchronous; analysed by the caller
+int f32_to_csr(spmv_ctx* ctx, const spmv_mat* f32, const char* who, spmv_mat** out);  // synchronous; analysed by the caller
+int f32_widen_arrays(spmv_ctx* ctx, const spmv_mat* f32, int32_t* d_col, double* d_val);  // asynchronous; either array may be null
+int f32_transpose(spmv_ctx* ctx, const spmv_mat* A, spmv_mat** out);                  // synchronous; analysed
+// solver_refine.hip: iterative refinement, the residual with A in fp64, the correction from a solver on A_lo
+int refine_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, const double* b, double* x, int solver, int precond, int max_outer,
+                 int inner_max_iter, double inner_tol, double rel_tol, int* outer, int* inner_total, double* rel_resid);
 // validate.hip
 int mat_validate(const spmv_mat* m);
 // convert.hip

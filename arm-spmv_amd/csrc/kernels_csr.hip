@@ -328,6 +328,8 @@ int launch_ldswin(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, 
 }
 }  // namespace
 
+int csr_pick_lanes(double mean_row) { return pick_lanes(mean_row); }
+
 int reduce_max_i32(spmv_ctx* ctx, const int32_t* in, int64_t n, int32_t* result)
 {
     SPMV_TRY(ensure_scratch(ctx, 64));
@@ -495,10 +497,12 @@ static bool csr_kernel_fuses_in_one_launch(int32_t kernel)
 bool writes_row_sums_in_one_launch(const spmv_mat* A)
 {
     while (runs_from_rowgrouped(A)) A = A->rowgrouped;
+    if (A->format == SPMV_FMT_CSR_F32) return true;  // (its one kernel has the row-parallel kernel's write-back: kernels_csr_f32.hip)
     return A->format == SPMV_FMT_CSR && csr_kernel_fuses_in_one_launch(A->kernel);
 }
 static bool fuses_extras(const spmv_mat* A)
 {
+    if (A->format == SPMV_FMT_CSR_F32) return A->nrow > 0;
     if (A->format != SPMV_FMT_CSR || A->nrow == 0) return false;
     if (A->kernel == SPMV_CSR_SPLIT) return A->split_short;
     // panel and two-phase build no layout for a handle without entries and launch nothing: their extras take the general path
@@ -606,6 +610,7 @@ int mat_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, c
         case SPMV_FMT_CSC: return csc_apply(ctx, A, x, y);
         case SPMV_FMT_DIA: return dia_apply(ctx, A, x, y);
         case SPMV_FMT_BSR: return bsr_apply(ctx, A, x, y);
+        case SPMV_FMT_CSR_F32: return csr_f32_apply(ctx, A, x, y, ex);
         default: SPMV_FAIL(SPMV_ERR_INVALID, "unknown format %d", A->format);
     }
 }

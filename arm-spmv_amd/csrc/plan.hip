@@ -175,6 +175,7 @@ extern "C" {
 int spmv_mat_get_plan(const spmv_mat* m, void* buf, int64_t* len)
 {
     SPMV_REQUIRE(m && len, "spmv_mat_get_plan: null argument");
+    if (m->format == SPMV_FMT_CSR_F32) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_mat_get_plan: a handle of format 6 has one kernel and no plan");
     std::vector<plan_node> nodes;
     (void)collect(m, nodes);
     const int64_t need = (int64_t)sizeof(plan_header) + (int64_t)nodes.size() * (int64_t)sizeof(plan_node);
@@ -194,6 +195,7 @@ int spmv_mat_get_plan(const spmv_mat* m, void* buf, int64_t* len)
 int spmv_mat_set_plan(spmv_mat* m, const void* buf, int64_t len)
 {
     SPMV_REQUIRE(m, "spmv_mat_set_plan: null matrix");
+    if (m->format == SPMV_FMT_CSR_F32) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_mat_set_plan: a handle of format 6 has one kernel and no plan");
     std::vector<plan_node> own;  // (a private copy: the caller's buffer may go away while copies are being built)
     SPMV_TRY(check_blob(buf, len, &own));
     SPMV_REQUIRE(own[0].format == m->format, "spmv_mat_set_plan: the plan is for format %d, the handle holds format %d", own[0].format, m->format);

@@ -79,6 +79,24 @@ int check_square_solve(const solver_rules& S, const spmv_ctx* ctx, const spmv_ma
     return check_known_preconditioner(S.who, precond);
 }
 
+int check_refine(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, const spmv_vec* b, const spmv_vec* x, int solver, int precond,
+                 int max_outer, int inner_max_iter, double inner_tol, double rel_tol, const int32_t* outer, const int32_t* inner_total,
+                 const double* rel_resid)
+{
+    const char* const who = "spmv_refine";
+    SPMV_REQUIRE(ctx && A && A_lo && b && x && outer && inner_total && rel_resid, "%s: null argument", who);
+    SPMV_REQUIRE(A->nrow == A->ncol, "%s: the matrix is %d x %d, not square", who, A->nrow, A->ncol);
+    SPMV_REQUIRE(A_lo->nrow == A->nrow && A_lo->ncol == A->ncol, "%s: A_lo is %d x %d, A is %d x %d: the shapes must match", who, A_lo->nrow, A_lo->ncol, A->nrow,
+                 A->ncol);
+    SPMV_REQUIRE(A->ctx == ctx && A_lo->ctx == ctx, "%s: %s belongs to another context", who, A->ctx != ctx ? "A" : "A_lo");
+    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "%s: b has %lld and x %lld entries, the matrix %d rows", who, (long long)b->n, (long long)x->n, A->nrow);
+    SPMV_REQUIRE(vectors_disjoint(b, x), "%s: b and x must not overlap", who);
+    SPMV_REQUIRE(max_outer >= 0 && inner_max_iter >= 0 && inner_tol >= 0.0 && rel_tol >= 0.0, "%s: max_outer=%d inner_max_iter=%d inner_tol=%g rel_tol=%g", who,
+                 max_outer, inner_max_iter, inner_tol, rel_tol);
+    SPMV_REQUIRE(solver == SPMV_REFINE_CG || solver == SPMV_REFINE_BICGSTAB, "%s: unknown solver %d (0: CG, 1: BiCGSTAB)", who, solver);
+    return check_known_preconditioner(who, precond);
+}
+
 int check_preconditioner(const solver_rules& S, const spmv_mat* A, int precond)
 {
     if (precond == SPMV_PRECOND_SYMGS && S.symgs_not_built_for)

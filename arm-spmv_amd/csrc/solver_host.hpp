@@ -34,6 +34,11 @@ int  check_known_preconditioner(const char* who, int precond);
 // the square single-vector solvers: null arguments, square, the lengths of b and x, alias / overlap, limits, a known preconditioner
 int check_square_solve(const solver_rules& S, const spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, const spmv_vec* x, int max_iter,
                        double rel_tol, int precond, const int32_t* iters, const double* rel_resid);
+// spmv_refine: null arguments, A square, A_lo of A's shape and context, the lengths of b and x, overlap, the four limits, a known inner
+// solver and preconditioner
+int check_refine(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, const spmv_vec* b, const spmv_vec* x, int solver, int precond,
+                 int max_outer, int inner_max_iter, double inner_tol, double rel_tol, const int32_t* outer, const int32_t* inner_total,
+                 const double* rel_resid);
 // a known preconditioner that this solver does not take, or not on this handle
 int check_preconditioner(const solver_rules& S, const spmv_mat* A, int precond);
 

@@ -6,7 +6,8 @@
 // (owned = false: it never frees them) and picks its own kernel like any handle of its format - a CSC companion chooses between
 // the scatter and the row-grouped copy (which is the CSR of A^T, and picks panel or another CSR kernel itself), a CSR companion
 // runs all of CSR AUTO.  A BSR handle gets a BSR handle of A^T with arrays of its own (convert_bsr.hip: blocks in stable order by
-// block column, each transposed as it is copied) and the forward kernel runs on that.  An ELL handle becomes a COO companion: its rows are ELL's col_ind (borrowed), its columns the row of every
+// block column, each transposed as it is copied) and the forward kernel runs on that; a handle of format 6 (single-precision value
+// storage) likewise gets a format-6 handle of A^T of its own (convert_f32.hip).  An ELL handle becomes a COO companion: its rows are ELL's col_ind (borrowed), its columns the row of every
 // slot (an array made here, owned by the transposed state, not by the companion), its values ELL's.  Every slot counts, padding
 // included (0.0 * x_i into y[pad column]), as the forward ELL product counts it.
 //
@@ -274,6 +275,13 @@ int transpose_build(spmv_mat* A, transpose_state* st)
             st->counted_in_owner = st->comp->device_bytes;
             A->device_bytes += st->counted_in_owner;
             return SPMV_OK;
+        case SPMV_FMT_CSR_F32:
+            // a format-6 handle of A^T with arrays of its own (convert_f32.hip: widened, transposed on the device, packed again; the two
+            // fp64 intermediates are gone when it returns), run by the forward kernel; counted in A's device_bytes like a BSR companion
+            SPMV_TRY(f32_transpose(A->ctx, A, &st->comp));
+            st->counted_in_owner = st->comp->device_bytes;
+            A->device_bytes += st->counted_in_owner;
+            return SPMV_OK;
         default: SPMV_FAIL(SPMV_ERR_INVALID, "spmv_mat_transpose_setup: unknown format %d", A->format);
     }
 }
@@ -340,6 +348,8 @@ int transpose_set_kernel(spmv_mat* A, int64_t kernel)
         SPMV_REQUIRE(kernel == SPMV_CSR_AUTO || kernel == SPMV_CSR_VECTOR, "transpose_kernel: a DIA handle has one transposed kernel: AUTO (0) or VECTOR (1)");
     else if (A->format == SPMV_FMT_BSR)
         SPMV_REQUIRE(kernel == SPMV_CSR_AUTO || kernel == SPMV_CSR_VECTOR, "transpose_kernel: the BSR handle of A^T has one kernel: AUTO (0) or VECTOR (1)");
+    else if (A->format == SPMV_FMT_CSR_F32)
+        SPMV_REQUIRE(kernel == SPMV_CSR_AUTO || kernel == SPMV_CSR_VECTOR, "transpose_kernel: the format 6 handle of A^T has one kernel: AUTO (0) or VECTOR (1)");
     else if (csr_companion)
         SPMV_REQUIRE(kernel >= SPMV_CSR_AUTO && kernel <= SPMV_CSR_ELL, "transpose_kernel: a CSR kernel id (0 .. 8) for the CSR companion of a CSC handle");
     else

@@ -4,6 +4,7 @@
 // do not either, for speed.  This is the explicit check a caller runs once on untrusted input: every index inside
 // its range, offsets non-decreasing and consistent with the entry count.  One pass over the index arrays.
 #include "common.hpp"
+#include "csr_f32_settings.hpp"
 
 namespace spmv
 {
@@ -29,6 +30,14 @@ __global__ __launch_bounds__(kBlock) void check_offsets_kernel(const int32_t* __
     if (blockIdx.x == 0 && threadIdx.x == 0 && (ptr[0] != 0 || ptr[n] != nnz)) atomicOr(flags, 4);
 }
 
+// the columns of a format-6 handle: the low halves of its packed entry words (csr_f32_settings.hpp)
+__global__ __launch_bounds__(kBlock) void check_packed_range_kernel(const uint64_t* __restrict__ ent, int64_t n, int32_t limit, int32_t* __restrict__ flags)
+{
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) bad |= (uint32_t)f32_entry_col(ent[i]) >= (uint32_t)limit;
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags, 1);
+}
+
 }  // namespace
 
 int mat_validate(const spmv_mat* m)
@@ -37,7 +46,9 @@ int mat_validate(const spmv_mat* m)
     // a handle that released its index arrays (panel_keep_csr = 0) has nothing left to check: refuse on the host, the
     // kernels below would dereference a null pointer on the GPU
     const int64_t entries = m->format == SPMV_FMT_ELL ? (int64_t)m->nrow * m->k : m->nnz;
-    if (m->format != SPMV_FMT_DIA)
+    if (m->format == SPMV_FMT_CSR_F32)
+        SPMV_REQUIRE(m->a && m->f32_ent, "spmv_mat_validate: a handle of format 6 without its row pointer or its entry stream");
+    else if (m->format != SPMV_FMT_DIA)
     {
         const bool need_a = m->format != SPMV_FMT_ELL && (m->format != SPMV_FMT_COO || entries > 0);
         SPMV_REQUIRE(!(need_a && !m->a) && !(entries > 0 && !m->b),
@@ -79,6 +90,10 @@ int mat_validate(const spmv_mat* m)
             if (nnzb) hipLaunchKernelGGL(check_range_kernel, dim3(stream_grid(nnzb)), dim3(kBlock), 0, s, m->b, nnzb, (int32_t)ceil_div(m->ncol, m->k), flags);
             break;
         }
+        case SPMV_FMT_CSR_F32:  // the CSR checks, the columns read from the packed stream
+            hipLaunchKernelGGL(check_offsets_kernel, dim3(stream_grid(m->nrow)), dim3(kBlock), 0, s, m->a, (int64_t)m->nrow, nnz, flags);
+            if (nnz) hipLaunchKernelGGL(check_packed_range_kernel, dim3(stream_grid(nnz)), dim3(kBlock), 0, s, (const uint64_t*)m->f32_ent, nnz, m->ncol, flags);
+            break;
         case SPMV_FMT_DIA: break;  // the product bounds every column by min(nrow, ncol) itself (kernels_misc.hip)
         default: SPMV_FAIL(SPMV_ERR_INVALID, "unknown format %d", m->format);
     }

@@ -55,7 +55,9 @@ typedef enum spmv_format
     SPMV_FMT_CSC = 2, /* include/matrix.h:49-68 */
     SPMV_FMT_ELL = 3, /* include/matrix.h:70-92, column-major: (row i, slot k) at i + k*nrow */
     SPMV_FMT_DIA = 4, /* include/matrix.h:117-138, row-major: (row i, diag d) at i*ndiags + d */
-    SPMV_FMT_BSR = 5  /* block CSR, square blocks of bs x bs values, 2 <= bs <= 8 (no counterpart in the reference): spmv_bsr_upload */
+    SPMV_FMT_BSR = 5, /* block CSR, square blocks of bs x bs values, 2 <= bs <= 8 (no counterpart in the reference): spmv_bsr_upload */
+    SPMV_FMT_CSR_F32 = 6 /* CSR whose values are stored as float, one packed 8-byte word per entry (no counterpart in the reference):
+                            spmv_csr_to_f32, spmv_csr_f32_upload */
 } spmv_format;
 
 /* CSR kernel selection (spmv_mat_set_kernel).  AUTO (csrc/select.hip) is decided when the handle is
@@ -647,6 +649,32 @@ int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec*
  *   the size in the message. */
 int spmv_gmres(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t restart, int32_t max_iter, double rel_tol,
                int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
+/* Iterative refinement (solver_refine.hip): fp64 answers from a solver that runs on a cheaper handle.  A (any square
+ *   handle) defines the system; A_lo (any handle of the same shape in the same context - a SPMV_FMT_CSR_F32 copy of A is the intended
+ *   use; A_lo == A is allowed) is what the inner solver multiplies by.  From the x passed in, per outer step:
+ *     r = b - A x with A's forward product and ||r||, both in fp64 (the deterministic dot of the solvers);
+ *     stop if ||r|| <= rel_tol ||b||, or after max_outer steps, or if ||r|| is not below the smallest residual seen so far - then x
+ *     goes back to the iterate of that smallest residual; else
+ *     solve A_lo d = r from d = 0 with `solver` (SPMV_REFINE_CG: spmv_cg, SPMV_REFINE_BICGSTAB: spmv_bicgstab) to inner_tol within
+ *     inner_max_iter iterations, check_every = 1, `precond` handed to that solver on A_lo exactly as it takes it (its refusals are
+ *     this call's, made before the device is touched); an inner solve that runs out of iterations is no error, its d is used; an
+ *     inner breakdown returns the inner solver's error;  x += d.
+ *   SPMV_OK in all three stopping cases.  *outer = the steps that solved and updated, *inner_total = the inner iterations of all
+ *   of them, *rel_resid = ||b - A x|| / ||b|| of the x returned - always written.  b = 0: x is untouched, the counts and the
+ *   residual are 0 (spmv_cg's rule).  nrow = 0: likewise.
+ *   Refused with SPMV_ERR_INVALID before any device use: null pointers, A not square, A_lo of another shape or another context,
+ *   b or x of the wrong length, b and x overlapping, negative max_outer / inner_max_iter / inner_tol / rel_tol, an unknown solver.
+ *   Synchronous.  Device memory for the duration of the call: three work vectors of nrow doubles (r, d, and the best iterate) on
+ *   top of the inner solver's own, released on every path.  The handles' forward state (kernel, copies, plan) is left as it was;
+ *   a preconditioner's state is built in A_lo as the inner solver builds it. */
+enum
+{
+    SPMV_REFINE_CG       = 0,
+    SPMV_REFINE_BICGSTAB = 1
+};
+int spmv_refine(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, const spmv_vec* b, spmv_vec* x, int32_t solver, int32_t precond,
+                int32_t max_outer, int32_t inner_max_iter, double inner_tol, double rel_tol, int32_t* outer, int32_t* inner_total,
+                double* rel_resid);
 /* Blocks: the dense tall-skinny arithmetic of a block method (block_ops.hip).  A BLOCK is p columns of n doubles held
  *   column-major in one spmv_vec: column c starts at entry c * ld, ld >= n, and the vector holds at least (p - 1) * ld + n entries.
  *   Rows n .. ld - 1 of a column are padding: never read, never written.  1 <= p, q <= 96 (SPMV_BLOCK_MAX_COLS) in both calls; blocks
@@ -1077,6 +1105,46 @@ int spmv_bsr_wrap_device(spmv_ctx* ctx, int32_t nrow, int32_t ncol, int32_t bs, 
  * shard, a handle of another context, a CSR handle without its arrays (SPMV_ERR_INVALID). */
 int spmv_csr_to_bsr(spmv_ctx* ctx, const spmv_mat* csr, int32_t bs, spmv_mat** out_bsr);
 int spmv_bsr_to_csr(spmv_ctx* ctx, const spmv_mat* bsr, int32_t drop_zeros, spmv_mat** out_csr);
+
+/* ---- CSR with single-precision value storage (SPMV_FMT_CSR_F32 = 6): csrc/kernels_csr_f32.hip, csrc/convert_f32.hip -----------
+ * A CSR matrix with an int32 row pointer (nnz < 2^31, as CSR) whose entries live in ONE packed stream: an 8-byte word per entry,
+ * the column in the low 32 bits, the IEEE bits of the float value in the high 32.  The handle holds the row pointer and that
+ * stream - no fp64 copy of the values, no separate column array: 8 bytes per entry against CSR's 12.  x is gathered, the sums
+ * are accumulated and y is written in fp64.  device_bytes = 4 (nrow + 1) + 8 nnz.
+ * The product y += A x (spmv_apply, _timed, _host, _dot, and every solver under SPMV_PRECOND_NONE or a Chebyshev state set up with
+ * explicit bounds) runs csr_f32_kernel<lanes>: the arrangement AND the order of operations of the row-parallel CSR kernel.  THE
+ * CONTRACT: a product of a format-6 handle returns the same bits as the product of the fp64 CSR handle that holds the widened
+ * values, forced to SPMV_CSR_VECTOR at the same lanes_per_row with default flags.  No atomics touch y.
+ * spmv_mat_get_info: format 6, kernel 1 (SPMV_CSR_VECTOR), lanes_per_row chosen from the mean row length, max_row_nnz.
+ * spmv_mat_set_kernel: AUTO (0: choose the lanes again) or VECTOR (1) with 0 or a power of two <= 64; anything else
+ * SPMV_ERR_UNSUPPORTED.  spmv_mat_validate: the CSR checks.  spmv_mat_download: a = the row pointer, b = the columns, v = the
+ * values widened to double.  spmv_apply_transpose: spmv_mat_transpose_setup builds a format-6 handle of A^T once - the values
+ * are widened into an fp64 CSR copy, the device transpose (spmv_csr_transpose) runs on it and the result is packed again; the
+ * two fp64 intermediates (12 nnz bytes each, plus the transpose's own set-up memory) are TRANSIENT and freed before it
+ * returns; the companion (4 (ncol + 1) + 8 nnz bytes) is counted in device_bytes and freed with the handle.
+ * Refused with SPMV_ERR_UNSUPPORTED, the message naming format 6: spmv_apply_multi and spmv_cg_multi, spmv_mat_device_ptrs,
+ * spmv_mat_set_flags with any bit set, spmv_mat_partition_rows(balance_entries = 1), spmv_mat_get_plan / spmv_mat_set_plan (a
+ * format-6 handle has one kernel and no plan; spmv_plan_check refuses a node of format 6), and every entry point that needs a
+ * CSR handle (ILU(0), SymGS, AMG, FSAI, SpGEMM, the reorderings, the Jacobi preconditioner).  The way there is spmv_f32_to_csr.
+ * There is NO spmv_csr_f32_wrap_device: the packed stream is the handle's own layout, not one a caller holds.
+ *
+ * spmv_csr_to_f32: from an unsharded CSR handle of this context that still has its arrays.  ONE device pass rounds every value
+ *   to nearest-even, packs the stream and gathers three statistics: the values that changed (inexact), the nonzero values that
+ *   became zero or subnormal (underflow), and the largest relative change |float(v) - v| / |v| among the changed values that did
+ *   not underflow.  Counts are integer atomics and the largest change is a maximum: the same bits after every call.  A value that
+ *   rounds to +-inf, or is not finite to begin with, refuses the conversion with SPMV_ERR_INVALID (the message gives their number
+ *   and the first row that holds one); no handle is returned.
+ * spmv_csr_f32_upload: host arrays (row_ptr of nrow + 1 entries from 0, nnz columns, nnz floats), packed on the device; a value
+ *   that is not finite is refused in the same way.
+ * spmv_f32_to_csr: the fp64 CSR handle of the widened values (exact), analysed like an uploaded one.
+ * spmv_f32_info: the three statistics of spmv_csr_to_f32; all zero for an uploaded handle (any pointer may be null).
+ * Refused on the host before the device is touched: null arguments, a handle of the wrong format (SPMV_ERR_UNSUPPORTED), a
+ * shard, a handle of another context, a CSR handle without its arrays (SPMV_ERR_INVALID). */
+int spmv_csr_to_f32(spmv_ctx* ctx, const spmv_mat* csr, spmv_mat** out_f32);
+int spmv_csr_f32_upload(spmv_ctx* ctx, int32_t nrow, int32_t ncol, const int32_t* row_ptr, const int32_t* col_ind, const float* values,
+                        spmv_mat** out);
+int spmv_f32_to_csr(spmv_ctx* ctx, const spmv_mat* f32, spmv_mat** out_csr);
+int spmv_f32_info(const spmv_mat* f32, int64_t* inexact, int64_t* underflow, double* max_rel_err);
 
 /* Split a CSR handle (a row shard) by column range, on the device: `inside` holds the entries with a column in
  * [col_begin, col_end), REBASED to 0 (it multiplies the caller's own slice of x: ncol = col_end - col_begin);
