@@ -94,6 +94,57 @@ def abs_product(nrow, ncol, bs, brow_ptr, bcol, val, x):
     return s, np.bincount(i, minlength=nrow)[:nrow] if nrow else np.zeros(0, dtype=np.int64)
 
 
+# ---- block-diagonal copies past one trip of the set-up kernels' grid (tests/tiled.py) ------------------------------------------------
+def tiled_base(bs, bits=3, e=2):
+    """(nrow0, ncol0, row_ptr, col, val) of a CSR base of 8 x 9 blocks of bs: dyadic values (tests/exact.py: sums of duplicates are
+    exact), columns unsorted, every row's first entry stored twice more (three values on one position), row 1 empty, block row 5
+    empty; the rows of a block row draw their columns from four of the nine block columns"""
+    import exact
+
+    rng = np.random.default_rng(2500 + bs)
+    nrow0, ncol0 = 8 * bs, 9 * bs
+    cols = []
+    for br in range(8):
+        pool = (rng.permutation(9)[:4, None] * bs + np.arange(bs)[None, :]).ravel()
+        for r in range(bs):
+            i = br * bs + r
+            if i == 1 or br == 5:
+                cols.append(np.zeros(0, np.int64))
+                continue
+            c = rng.permutation(pool)[:3 + (i % 3)]
+            cols.append(np.concatenate([c, c[:1], c[:1]]))
+    row_ptr = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int32)
+    col = np.concatenate(cols).astype(np.int32)
+    return nrow0, ncol0, row_ptr, col, exact.dyadic(rng, len(col), bits, e)
+
+
+def tiled_copies(bs, base, trip):
+    """(k, conditions): the least number of copies of `base` with which every grid-stride kernel of csrc/convert_bsr.hip takes a
+    later trip (one trip: `trip` items), and the conditions as {text: holds}.  The kernels run over the entries (owner_of_entry,
+    block_keys and the runs' pipeline: nnz), the blocks (block_fill, block_order_check, gather_i32, histogram, the sorts: nnzb), the
+    stored values (block_transpose: nnzb * bs^2) and the scalar rows and one (bsr_rows: nrow + 1)."""
+    nrow0, ncol0, rp, cc, cv = base
+    nnz0 = int(rp[-1])
+    nnzb0 = len(csr_to_bsr(nrow0, ncol0, rp, cc, cv, bs)[1])
+    more = lambda per: trip // per + 1  # the least k with k * per > trip
+    if bs == 2:
+        k = max(more(nnz0), more(nnzb0), -(-trip // nrow0))
+        cond = {"nnz > one trip": k * nnz0 > trip, "nnzb > one trip": k * nnzb0 > trip, "nrow + 1 > one trip": k * nrow0 + 1 > trip,
+                "blocks per copy no divisor of 256": 256 % nnzb0 != 0}
+    else:
+        k = max(more(nnz0), more(nnzb0 * bs * bs))
+        cond = {"nnz > one trip": k * nnz0 > trip, f"nnzb * {bs * bs} > one trip": k * nnzb0 * bs * bs > trip,
+                "below 100 MB of values": k * nnzb0 * bs * bs * 8 < 100e6}
+    return k, cond
+
+
+def shuffle_blocks(rng, brow_ptr, bcol, val, bs):
+    """the same BSR matrix with the blocks of every block row in random order"""
+    bp = np.asarray(brow_ptr, dtype=np.int64)
+    ids = np.concatenate([bp[r] + rng.permutation(int(bp[r + 1] - bp[r])) for r in range(len(bp) - 1)]).astype(np.int64)
+    return np.asarray(bcol)[ids], np.asarray(val, dtype=np.float64).reshape(-1, bs * bs)[ids].reshape(-1)
+
+
 def dense(nrow, ncol, bs, brow_ptr, bcol, val):
     i, j, v, _ = positions(nrow, ncol, bs, brow_ptr, bcol, val)
     A = np.zeros((nrow, ncol))

@@ -140,3 +140,44 @@ def scaled_laplacian(m: int = 24, seed: int = 7):
                     val.append(d[r] * e[1] * d[e[0]])
             rp.append(len(col))
     return n, np.array(rp, np.int32), np.array(col, np.int32), np.array(val)
+
+
+# ---- block-diagonal copies past one trip of the set-up kernels' grid (tests/tiled.py) ------------------------------------------------
+TILED_ROWS, TILED_NCOL = 128, 307
+LANES = (1, 2, 4, 8, 16, 32, 64)
+
+
+def tiled_structure():
+    """(row_ptr, col) of a 128-row base: every row length of the 300-row matrix of tests/test_gpu_csr_f32.py once (0, 1, and for every
+    lane count lpr + 1 and 4 lpr + 1, and 300), the other rows of 0, 1, 2, 3 and 5 entries - a mean near 10, so that the copies
+    pass one trip in rows before they pass 5 M entries; columns distinct inside a row and in random order"""
+    rng = np.random.default_rng(171)
+    once = sorted({n for lpr in LANES for n in (0, 1, lpr + 1, 4 * lpr + 1)} | {300})
+    short = (0, 1, 2, 3, 5)
+    counts = [once[i // 8] if i % 8 == 3 and i // 8 < len(once) else short[i % 5] for i in range(TILED_ROWS)]
+    assert set(once) <= set(counts)
+    col = np.concatenate([rng.permutation(TILED_NCOL)[:n] for n in counts]).astype(np.int32)
+    return np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), col
+
+
+def tiled_rounded():
+    """(row_ptr, col, val): values that essentially all take a rounding, three of them underflowing (to zero, to a subnormal, a
+    subnormal float as it is)"""
+    rp, col = tiled_structure()
+    rng = np.random.default_rng(172)
+    val = rng.standard_normal(len(col)) * np.ldexp(1.0, rng.integers(-30, 31, size=len(col)))
+    val[[5, len(val) // 2, len(val) - 2]] = [1e-46, -1e-40, 2.0**-149]
+    return rp, col, val
+
+
+def tiled_copies(row_ptr, trip):
+    """(k, conditions): the least number of copies with which the kernels over the entries (f32_pack, f32_widen, the packed-range
+    check) and over the rows (csr_f32_row_max) take a later trip (one trip: `trip` items)"""
+    nrow0, nnz0 = len(row_ptr) - 1, int(row_ptr[-1])
+    k = max(trip // nnz0 + 1, trip // nrow0 + 1)
+    return k, {"nnz > one trip": k * nnz0 > trip, "nrow > one trip": k * nrow0 > trip}
+
+
+# a value with a larger relative change than rounding a random value gives: just below the tie between 1 and 1 + 2^-23, it rounds to 1
+WORST_VALUE = 1.0 + 2.0**-24 - 2.0**-40
+WORST_REL = (WORST_VALUE - 1.0) / WORST_VALUE

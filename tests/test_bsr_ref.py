@@ -80,3 +80,47 @@ def test_unsorted_block_columns_come_out_ascending():
     for r in range(nrow):
         assert np.all(np.diff(c[rp[r]:rp[r + 1]]) > 0)
     assert np.array_equal(_dense_csr(nrow, ncol, rp, c, v), bsr_ref.dense(nrow, ncol, bs, bp, bc, bv))
+
+
+@pytest.mark.parametrize("bs", (2, 3, 8))
+def test_the_conversions_commute_with_block_diagonal_copies(bs):
+    """the oracle of tests/tiled.py for csrc/convert_bsr.hip: csr_to_bsr, bsr_to_csr (both drop_zeros) and transpose of k copies are
+    the base's result tiled, as bytes; and the coverage conditions of the GPU cases (tests/test_gpu_bsr.py) hold for their k"""
+    import tiled
+
+    base = bsr_ref.tiled_base(bs)
+    nrow0, ncol0, rp, cc, cv = base
+    assert (nrow0, ncol0) == (8 * bs, 9 * bs)
+    rows = np.repeat(np.arange(nrow0), np.diff(rp))
+    assert rp[2] == rp[1] and not np.any(rows // bs == 5), "an empty row and an empty block row"
+    assert any(np.any(np.diff(cc[rp[r]:rp[r + 1]]) < 0) for r in range(nrow0)), "unsorted columns"
+    assert all(np.count_nonzero(cc[rp[r]:rp[r + 1]] == cc[rp[r]]) == 3 for r in range(nrow0) if rp[r + 1] > rp[r]), "duplicates"
+    bp0, bc0, bv0 = bsr_ref.csr_to_bsr(nrow0, ncol0, rp, cc, cv, bs)
+    assert np.any(bv0 == 0.0) and np.any(np.diff(bp0) == 0)
+    for k in (1, 2, 5):
+        trp, tcc, tcv = tiled.tile_csr(k, ncol0, rp, cc, cv)
+        got = bsr_ref.csr_to_bsr(k * nrow0, k * ncol0, trp, tcc, tcv, bs)
+        want = tiled.tile_bsr(k, 9, bp0, bc0, bv0, bs)
+        for g, w in zip(got, want):
+            assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), f"bs {bs} k {k}: csr_to_bsr"
+        # from blocks in random order inside the block rows, as an uploaded handle may hold them
+        sc0, sv0 = bsr_ref.shuffle_blocks(np.random.default_rng(k), bp0, bc0, bv0, bs)
+        assert np.any(np.diff(sc0)[np.diff(np.repeat(np.arange(8), np.diff(bp0))) == 0] < 0)
+        sp, sc, sv = tiled.tile_bsr(k, 9, bp0, sc0, sv0, bs)
+        for drop in (True, False):
+            base_csr = bsr_ref.bsr_to_csr(nrow0, ncol0, bs, bp0, bc0, bv0, drop)
+            assert tiled.tiled_mismatch(bsr_ref.bsr_to_csr(k * nrow0, k * ncol0, bs, *want, drop), base_csr, k, ncol0) is None
+            assert tiled.tiled_mismatch(bsr_ref.bsr_to_csr(k * nrow0, k * ncol0, bs, sp, sc, sv, drop), base_csr, k, ncol0) is None
+        tp0, tc0, tv0 = bsr_ref.transpose(nrow0, ncol0, bs, bp0, sc0, sv0)
+        for g, w in zip(bsr_ref.transpose(k * nrow0, k * ncol0, bs, sp, sc, sv), tiled.tile_bsr(k, 8, tp0, tc0, tv0, bs)):
+            assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), f"bs {bs} k {k}: transpose"
+    # what tile_bsr is: the copy's offset on the block columns, the pointer continued, the same bytes
+    p2, c2, v2 = tiled.tile_bsr(2, 9, bp0, bc0, bv0, bs)
+    assert np.array_equal(p2, np.concatenate([bp0, bp0[1:] + bp0[-1]])) and np.array_equal(c2, np.concatenate([bc0, bc0 + 9]))
+    assert v2.tobytes() == bv0.tobytes() * 2
+    trip = tiled.max_grid() * tiled.block_lanes()
+    k, cond = bsr_ref.tiled_copies(bs, base, trip)
+    assert all(cond.values()), cond
+    per = {2: nrow0, 3: int(rp[-1]), 8: int(rp[-1])}[bs]  # what binds k here; one copy fewer misses its condition: k is the least
+    assert not ((k - 1) * per + (1 if bs == 2 else 0) > trip), (k, per)
+    print(f"bs {bs}: {k} copies, nnz {k * int(rp[-1])}, nnzb {k * len(bc0)}, rows {k * nrow0}, one trip {trip}")

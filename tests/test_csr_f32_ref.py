@@ -98,3 +98,34 @@ def test_refinement_reaches_fp64_accuracy_where_the_rounded_matrix_alone_stalls(
     assert ref.refine(A, A32, np.zeros(n), x1, 1e-4, 1e-12, 20, 1000) == (0, 0, 0.0) and np.all(x1 == 1.0)
     assert ref.refine(A, A32, b, np.zeros(n), 1e-4, 1e-12, 1, 1000)[0] == 1
     assert ref.refine(A, A, b, np.zeros(n), 1e-12, 1e-11, 20, 5000)[0] == 1
+
+
+def test_demotion_and_its_statistics_commute_with_block_diagonal_copies():
+    """the oracle of tests/tiled.py for csrc/convert_f32.hip: the rounding is entry by entry, so k copies demote and widen to the
+    base's bytes tiled; the counts are k times the base's and the largest relative change is the base's; one value of the last
+    copy can raise it.  And the coverage conditions of the GPU cases (tests/test_gpu_csr_f32.py) hold for their k."""
+    import tiled
+
+    rp, col, val = ref.tiled_rounded()
+    nrow0, nnz0 = len(rp) - 1, len(val)
+    assert (nrow0, int(rp[-1])) == (ref.TILED_ROWS, nnz0) and col.max() < ref.TILED_NCOL
+    once = {n for lpr in ref.LANES for n in (0, 1, lpr + 1, 4 * lpr + 1)} | {300}
+    assert once <= set(np.diff(rp).tolist()), "every row length of the 300-row matrix"
+    f0, inexact0, under0, rel0 = ref.demote(val)
+    assert under0 == 3 and inexact0 == nnz0 - 1 and 0.0 < rel0 < 2.0**-24
+    for k in (1, 3, 7):
+        trp, tcc, tcv = tiled.tile_csr(k, ref.TILED_NCOL, rp, col, val)
+        f, inexact, under, rel = ref.demote(tcv)
+        assert (inexact, under, rel) == (k * inexact0, k * under0, rel0)
+        assert f.tobytes() == np.tile(f0, k).tobytes() and ref.widen(f).tobytes() == np.tile(ref.widen(f0), k).tobytes()
+        assert tiled.tiled_mismatch((trp, tcc, ref.widen(f)), (rp, col, ref.widen(f0)), k, ref.TILED_NCOL) is None
+        assert np.array_equal(ref.pack(tcc, f) >> np.uint64(32), np.tile(ref.pack(col, f0) >> np.uint64(32), k))
+        # one value of the last copy with a larger change than any of the base
+        worse = tcv.copy()
+        worse[-1] = ref.WORST_VALUE
+        g, inexact_w, under_w, rel_w = ref.demote(worse)
+        assert rel_w == ref.WORST_REL > rel0 and (inexact_w, under_w) == (k * inexact0, k * under0) and g[-1] == np.float32(1.0)
+    trip = tiled.max_grid() * tiled.block_lanes()
+    k, cond = ref.tiled_copies(rp, trip)
+    assert all(cond.values()) and not ((k - 1) * nrow0 > trip and (k - 1) * nnz0 > trip), (k, cond)
+    print(f"{k} copies: {k * nrow0} rows, {k * nnz0} entries, one trip {trip}")

@@ -1,21 +1,29 @@
 """Block CSR on the GPU: the product and its transposed form bit for bit on dyadic inputs (tests/exact.py) for every block size and
 every number of lanes per block row, the conversions against the NumPy twin (tests/bsr_ref.py) array for array, the rounding gate
-for ordinary values, the plumbing (validate, download, plans, memory) and the solvers on a BSR handle.
+for ordinary values, the plumbing (validate, download, plans, memory) and the solvers on a BSR handle.  The exact cases stand at every
+block-row length where the kernel's loop changes shape, at every remainder of nrow and ncol, over more than two workgroups, through
+spmv_apply_dot and spmv_apply_host as well; the set-up runs past one trip of its grid on block-diagonal copies (tests/tiled.py); a
+closing test asserts that every instance of the kernel ran.
 
 The rounding gate is derived, not measured: a row of t stored positions is a sum of t + 1 terms (y0 and t products); any order of
 them, with or without fma, stays within (t + 1) * 2^-52 * (|A||x| + |y0|)_i of the exact sum to first order, and the reference
 is the twin's product in np.longdouble.
 """
+import collections
+
 import numpy as np
 import pytest
 
 import bsr_ref
 import exact
+import tiled
 from conftest import perf_expect
 
 pytestmark = pytest.mark.gpu
 AUTO, VECTOR, PANEL = 0, 1, 4
 GUARD = 12345.0
+INSTANCES = set()  # (bs, G, EDGE) of the bsr_vector_kernel instances that an exact test launched
+RUNS = collections.Counter()
 
 
 def _lanes(bs):
@@ -49,7 +57,7 @@ def _structure(rng, mb, nbc, counts):
 def _exact_matrices(bs):
     """(name, mb, nbc, counts): one block row of 0, 1, S, S + 1 and 1000 blocks each, and 37 block rows that hold all of them (the
     1000 behind others, so that its values cross offset 2^16 at bs = 8; the last workgroup is part-filled)"""
-    S = 64 // (bs * bs)
+    S = tiled.bsr_slots(bs)
     out = [(f"mb1-{n}", 1, 1003, [n]) for n in (0, 1, S, S + 1, 1000)]
     pattern = [1, S, 0, S + 1, 1]
     counts = [pattern[i % 5] for i in range(37)]
@@ -58,22 +66,76 @@ def _exact_matrices(bs):
     return out
 
 
+def _loop_lengths(bs):
+    """the block-row lengths at which the loop of bsr_vector_kernel<bs, G, .> changes shape (four steps of G blocks in flight, then
+    single steps), for every G that bs takes: none, one, one short of / exactly / one more than a step, the same around the four
+    steps in flight, a fifth step, and a long row whose steps are no multiple of four at any G but 1, 2, 5 (at those, 4 G + 1 is)"""
+    groups = [lanes // (bs * bs) for lanes in _lanes(bs)]
+    return sorted({n for G in groups for n in (0, 1, G - 1, G, G + 1, 4 * G - 1, 4 * G, 4 * G + 1, 5 * G, 1000)})
+
+
+MIXED_ROWS = 131
+
+
+def _mixed_counts(bs):
+    """131 block rows that hold every length of _loop_lengths, the 1000 once and behind others; every round through the lengths
+    starts one further, so that a length stands on even and on odd block rows (_structure: with and without the last block column)"""
+    short = [n for n in _loop_lengths(bs) if n != 1000]
+    counts = [short[(i + i // len(short)) % len(short)] for i in range(MIXED_ROWS)]
+    counts[70] = 1000
+    return counts
+
+
+def _edge_matrices(bs):
+    """(name, mb, nbc, counts, nrow % bs, ncol % bs): every length of _loop_lengths as a matrix of one block row, and the 131 mixed
+    block rows once for every column remainder 0 .. bs - 1 (remainder 0: the kernel without the column edge), the row remainder one
+    less (so 0 .. bs - 1 occur as well, and the instance without the column edge meets absent rows).  131 block rows are more than
+    two workgroups at every number of lanes: a third, part-filled one runs"""
+    out = [(f"row-{n}", 1, 1003, [n], (t + 1) % bs, t % bs) for t, n in enumerate(_loop_lengths(bs))]
+    for crem in range(bs):
+        out.append((f"mixed-c{crem}", MIXED_ROWS, 1003, _mixed_counts(bs), (crem - 1) % bs, crem))
+    return out
+
+
+def _shape(bs, matrix):
+    """(name, mb, nbc, counts, nrow, ncol); a matrix without remainders has nrow % bs = bs - 1 and ncol % bs = 1"""
+    name, mb, nbc, counts = matrix[:4]
+    rrem, crem = matrix[4:] if len(matrix) > 4 else (bs - 1, 1)
+    return name, mb, nbc, counts, bs * (mb - 1) + (rrem or bs), bs * (nbc - 1) + (crem or bs)
+
+
+def _poisoned_handle(ctx, rng, bs, matrix, bits, e):
+    """the BSR handle of a matrix with dyadic values and NaN at every stored position outside nrow x ncol, and its entry list"""
+    name, mb, nbc, counts, nrow, ncol = _shape(bs, matrix)
+    bp, bc = _structure(rng, mb, nbc, counts)
+    val = exact.dyadic(rng, len(bc) * bs * bs, bits, e)
+    i, j, v, at = bsr_ref.positions(nrow, ncol, bs, bp, bc, val)
+    stored = np.full(len(val), np.nan)  # NaN at every position outside nrow x ncol
+    stored[at] = val[at]
+    outside = bool((ncol % bs and np.any(bc == nbc - 1)) or (nrow % bs and counts[-1] > 0))
+    assert (len(at) < len(val)) == outside, name
+    A = ctx.bsr(nrow, ncol, bs, bp, bc, stored)
+    info = A.info
+    assert (info.format, info.nrow, info.ncol, info.ell_k, info.nnz, info.kernel) == (5, nrow, ncol, bs, len(bc) * bs * bs, VECTOR)
+    assert info.max_row_nnz == max(counts) * bs and info.lanes_per_row in _lanes(bs)
+    return A, (i, j, v)
+
+
+def _ran(A, bs):
+    """the instance of bsr_vector_kernel that a product of A launches (bsr_apply: none where there is nothing to add)"""
+    info = A.info
+    if info.nrow and info.nnz:
+        INSTANCES.add((bs, info.lanes_per_row // (bs * bs), info.ncol % bs != 0))
+
+
 def check_exact(ctx, bs, matrices, guarded):
     """the forward product under every number of lanes per block row and the transposed product, bit for bit, y with a guard"""
     rng = np.random.default_rng(500 + bs)
-    for name, mb, nbc, counts in matrices:
-        nrow, ncol = bs * mb - 1, bs * nbc - (bs - 1)
-        bp, bc = _structure(rng, mb, nbc, counts)
+    for matrix in matrices:
+        name, mb, nbc, counts, nrow, ncol = _shape(bs, matrix)
         bits, e = exact.choose_bits(max(1000 * bs, mb * bs))
-        val = exact.dyadic(rng, len(bc) * bs * bs, bits, e)
-        i, j, v, at = bsr_ref.positions(nrow, ncol, bs, bp, bc, val)
-        stored = np.full(len(val), np.nan)  # NaN at every position outside nrow x ncol
-        stored[at] = val[at]
-        assert len(at) < len(val) or len(bc) == 0
-        A = ctx.bsr(nrow, ncol, bs, bp, bc, stored)
+        A, (i, j, v) = _poisoned_handle(ctx, rng, bs, matrix, bits, e)
         info = A.info
-        assert (info.format, info.nrow, info.ncol, info.ell_k, info.nnz, info.kernel) == (5, nrow, ncol, bs, len(bc) * bs * bs, VECTOR)
-        assert info.max_row_nnz == max(counts) * bs and info.lanes_per_row in _lanes(bs)
         x = exact.poison(exact.dyadic(rng, ncol, bits, e), j)  # NaN / inf at every column no stored in-range position uses
         y0 = exact.dyadic(rng, nrow, bits, e)
         want = exact.exact_product(nrow, i, j, v, x, e, y0=y0)
@@ -87,6 +149,7 @@ def check_exact(ctx, bs, matrices, guarded):
             got = read()
             assert got[nrow] == GUARD, f"bs {bs} {name} lanes {lanes}: y written at nrow"
             assert np.array_equal(got[:nrow], want), f"bs {bs} {name} lanes {lanes}: forward"
+            _ran(A, bs)
         A.set_kernel(AUTO, 0)
         assert A.info.lanes_per_row == info.lanes_per_row
         # transposed: x has nrow entries (poisoned where no stored position reads a row), y ncol and its guard
@@ -105,6 +168,70 @@ def check_exact(ctx, bs, matrices, guarded):
 @pytest.mark.parametrize("bs", range(2, 9))
 def test_product_and_transposed_product_are_exact_on_dyadic_inputs(ctx, bs):
     check_exact(ctx, bs, _exact_matrices(bs), _guarded)
+    RUNS["exact"] += 1
+
+
+@pytest.mark.parametrize("bs", range(2, 9))
+def test_every_loop_edge_and_every_remainder_is_exact(ctx, bs):
+    """every length at which the kernel's loop changes shape, alone and mixed over three workgroups, every nrow % bs and ncol % bs,
+    under every number of lanes per block row"""
+    matrices = _edge_matrices(bs)
+    lengths = _loop_lengths(bs)
+    for lanes in _lanes(bs):
+        G = lanes // (bs * bs)
+        assert {0, 1, G - 1, G, G + 1, 4 * G - 1, 4 * G, 4 * G + 1, 5 * G, 1000} <= set(lengths), (bs, G)
+        assert MIXED_ROWS >= 2 * tiled.bsr_rows_per_workgroup(bs, lanes) + 1, (bs, lanes)
+    assert {m[3][0] for m in matrices if m[1] == 1} == set(lengths) == set(_mixed_counts(bs))
+    assert {m[5] for m in matrices} == set(range(bs)) == {m[4] for m in matrices}
+    assert {m[5] for m in matrices if m[1] == MIXED_ROWS} == set(range(bs)) == {m[4] for m in matrices if m[1] == MIXED_ROWS}
+    check_exact(ctx, bs, matrices, _guarded)
+    RUNS["edges"] += 1
+
+
+@pytest.mark.parametrize("bs", range(2, 9))
+def test_the_other_entry_points_are_exact_on_the_mixed_matrix(ctx, bs):
+    """spmv_apply_transpose, spmv_apply_dot (y = A x over NaN, y += A x, and the dot w . y held to integer arithmetic) and
+    spmv_apply_host on the 131 mixed block rows, at the lanes AUTO picks and at the widest"""
+    rng = np.random.default_rng(900 + bs)
+    for crem in sorted({0, 1, bs - 1}):  # without the column edge, the remainder of the earlier tests, the widest remainder
+        matrix = (f"mixed-c{crem}", MIXED_ROWS, 1003, _mixed_counts(bs), (crem - 1) % bs, crem)
+        name, mb, nbc, counts, nrow, ncol = _shape(bs, matrix)
+        bits, e = exact.choose_bits_dot(sum(counts) * bs * bs, max(nrow, ncol))
+        A, (i, j, v) = _poisoned_handle(ctx, rng, bs, matrix, bits, e)
+        x = exact.poison(exact.dyadic(rng, ncol, bits, e), j)
+        y0, w = exact.dyadic(rng, nrow, bits, e), exact.dyadic(rng, nrow, bits, e)
+        xt = exact.poison(exact.dyadic(rng, nrow, bits, e), i)
+        yt0 = exact.dyadic(rng, ncol, bits, e)
+        over, onto = exact.exact_product(nrow, i, j, v, x, e), exact.exact_product(nrow, i, j, v, x, e, y0=y0)
+        want_t = exact.exact_product(ncol, j, i, v, xt, e, y0=yt0)
+        dx, dw, dxt = ctx.vector_from(x), ctx.vector_from(w), ctx.vector_from(xt)
+        auto = A.info.lanes_per_row
+        for lanes in sorted({auto, _lanes(bs)[-1]}):
+            A.set_kernel(VECTOR, lanes)
+            what = f"bs {bs} {name} lanes {lanes}"
+            dy, read = _guarded(ctx, np.full(nrow, np.nan))
+            dot = ctx.apply_dot(A, dx, dy, dw, overwrite=True)
+            got = read()
+            assert got[nrow] == GUARD and np.array_equal(got[:nrow], over), f"{what}: overwrite"
+            assert dot == exact.exact_dot(w, over, e, 2 * e), f"{what}: the dot of y = A x"
+            dy, read = _guarded(ctx, y0)
+            dot = ctx.apply_dot(A, dx, dy, dw, overwrite=False)
+            got = read()
+            assert got[nrow] == GUARD and np.array_equal(got[:nrow], onto), f"{what}: y += A x with the dot"
+            assert dot == exact.exact_dot(w, onto, e, 2 * e), f"{what}: the dot of y += A x"
+            _ran(A, bs)
+            y, dy = y0.copy(), ctx.vector_from(y0)
+            ctx.apply_host(A, x, y)
+            ctx.apply(A, dx, dy)
+            ctx.sync()
+            assert np.array_equal(y.view(np.uint64), dy.download().view(np.uint64)), f"{what}: apply_host against apply on device vectors"
+            assert np.array_equal(y, onto), f"{what}: apply_host"
+            dyt, read = _guarded(ctx, yt0)
+            ctx.apply_transpose(A, dxt, dyt)
+            ctx.sync()
+            got = read()
+            assert got[ncol] == GUARD and np.array_equal(got[:ncol], want_t), f"{what}: transposed"
+    RUNS["entry points"] += 1
 
 
 def _torch_child(case):
@@ -184,7 +311,7 @@ def _csr_inputs():
     dcols = np.concatenate([cols, cols[:, 1:2], cols[:, 1:2]], axis=1)
     dval = rng.uniform(0.5, 2.0, size=7 * nrow) * rng.choice([-1.0, 1.0], size=7 * nrow)
     dup = (nrow, ncol, (7 * np.arange(nrow + 1)).astype(np.int32), dcols.reshape(-1).astype(np.int32), dval)
-    # rows 40 .. 79 empty: whole block rows without a block for bs = 2, 3, 8
+    # rows 40 .. 79 empty: whole block rows without a block for every bs
     keep = np.ones(nrow, dtype=bool)
     keep[40:80] = False
     counts = np.where(keep, 5, 0)
@@ -206,7 +333,7 @@ def _gate(nrow, ncol, bs, bp, bc, bv, x, y0, got, what):
     assert np.all(err <= bound), f"{what}: {worst:.3f} of the bound"
 
 
-@pytest.mark.parametrize("bs", (2, 3, 8))
+@pytest.mark.parametrize("bs", range(2, 9))
 @pytest.mark.parametrize("which", list(CSR_INPUTS))
 def test_conversions_equal_the_twin_and_the_products_agree(ctx, which, bs):
     nrow, ncol, rp, col, val = CSR_INPUTS[which]
@@ -282,6 +409,92 @@ def test_rounding_gate_on_non_dyadic_values(ctx):
             ctx.apply(A, ctx.vector_from(x), dy)
             ctx.sync()
             _gate(nrow, ncol, bs, bp, bc, bv, x, y0, dy.download(), f"bs {bs} lanes {lanes}")
+
+
+# ---- set-up kernels past one trip of their grid (tests/tiled.py) ---------------------------------------------------------------------------
+TRIP = tiled.max_grid() * tiled.block_lanes()  # items of one trip of a grid-stride kernel of csrc/convert_bsr.hip
+
+
+def _tiled_case(bs):
+    base = bsr_ref.tiled_base(bs)
+    k, cond = bsr_ref.tiled_copies(bs, base, TRIP)
+    assert all(cond.values()), (bs, k, cond)
+    return base, k
+
+
+def _where(nrow0):
+    return lambda copy, row: f"scalar row {copy * nrow0 + row}, trip {(copy * nrow0 + row) // TRIP} of the row kernels"
+
+
+@pytest.mark.parametrize("bs", (2, 3, 8))
+def test_conversions_and_products_of_block_diagonal_copies_past_one_trip(ctx, bs):
+    """k copies of an 8 x 9-block base: every grid-stride kernel of the set-up takes a later trip (the conditions are those of
+    bsr_ref.tiled_copies, asserted here and in tests/test_bsr_ref.py), and the results are the base twin's tiled, as bytes"""
+    (nrow0, ncol0, rp, cc, cv), k = _tiled_case(bs)
+    nrow, ncol = k * nrow0, k * ncol0
+    bp0, bc0, bv0 = bsr_ref.csr_to_bsr(nrow0, ncol0, rp, cc, cv, bs)
+    print(f"bs {bs}: {k} copies, nnz {k * int(rp[-1])}, nnzb {k * len(bc0)}, stored values {k * len(bv0)}, rows {nrow}, one trip {TRIP}")
+    C = ctx.csr(nrow, ncol, *tiled.tile_csr(k, ncol0, rp, cc, cv))
+    B = ctx.csr_to_bsr(C, bs)
+    del C
+    for part, got, want in zip(("brow_ptr", "bcol", "val"), B.download(), tiled.tile_bsr(k, 9, bp0, bc0, bv0, bs)):
+        assert got.dtype == want.dtype and got.shape == want.shape, f"bs {bs}: csr_to_bsr {part}"
+        if got.tobytes() != want.tobytes():
+            at = int(np.flatnonzero(got.view(np.uint64 if part == "val" else np.int32) != want.view(np.uint64 if part == "val" else np.int32))[0])
+            raise AssertionError(f"bs {bs}: csr_to_bsr {part}[{at}] is {got[at]!r} against {want[at]!r} (copy {at // max(len(want) // k, 1)})")
+    assert B.info.max_row_nnz == int(np.max(np.diff(bp0))) * bs
+    for drop in (True, False):
+        miss = tiled.tiled_mismatch(ctx.bsr_to_csr(B, drop_zeros=drop).download(), bsr_ref.bsr_to_csr(nrow0, ncol0, bs, bp0, bc0, bv0, drop), k, ncol0, _where(nrow0))
+        assert miss is None, f"bs {bs}: bsr_to_csr(drop_zeros={drop}): {miss}"
+    # the products: the base's exact y tiled (a stored 0.0 multiplies its x: every column of a stored block is read)
+    rng = np.random.default_rng(2600 + bs)
+    i, j, v, _ = bsr_ref.positions(nrow0, ncol0, bs, bp0, bc0, bv0)
+    bits, e = exact.choose_bits(4 * 9 * bs)  # (a row holds at most 4 blocks of bs positions, each the sum of at most three values)
+    x0, y00 = exact.poison(exact.dyadic(rng, ncol0, bits, e), j), exact.dyadic(rng, nrow0, bits, e)
+    xt0, yt00 = exact.poison(exact.dyadic(rng, nrow0, bits, e), i), exact.dyadic(rng, ncol0, bits, e)
+    dy, dyt = ctx.vector_from(np.tile(y00, k)), ctx.vector_from(np.tile(yt00, k))
+    ctx.apply(B, ctx.vector_from(np.tile(x0, k)), dy)
+    ctx.apply_transpose(B, ctx.vector_from(np.tile(xt0, k)), dyt)
+    ctx.sync()
+    for what, got, want0 in (("forward", dy.download(), exact.exact_product(nrow0, i, j, v, x0, e, y0=y00)),
+                             ("transposed", dyt.download(), exact.exact_product(ncol0, j, i, v, xt0, e, y0=yt00))):
+        bad = np.flatnonzero(got.view(np.uint64) != np.tile(want0, k).view(np.uint64))
+        assert len(bad) == 0, f"bs {bs}: {what} product: {len(bad)} outputs differ, the first is {bad[0]} (copy {bad[0] // len(want0)}, output {bad[0] % len(want0)})"
+    RUNS["tiled"] += 1
+
+
+def test_unsorted_blocks_past_one_trip_and_a_block_column_out_of_range_in_the_last_block(ctx, pkg):
+    """the sort path of bsr_to_csr (block_order_check, sort_ids_by_key twice, gather_i32) at nnzb > one trip: an uploaded handle whose
+    blocks stand in random order inside the block rows gives the base twin - which sorts them stably - tiled"""
+    bs = 2
+    (nrow0, ncol0, rp, cc, cv), k = _tiled_case(bs)
+    bp0, bc0, bv0 = bsr_ref.csr_to_bsr(nrow0, ncol0, rp, cc, cv, bs)
+    sc0, sv0 = bsr_ref.shuffle_blocks(np.random.default_rng(7), bp0, bc0, bv0, bs)
+    assert k * len(bc0) > TRIP and not np.array_equal(sc0, bc0)
+    bp, bc, bv = tiled.tile_bsr(k, 9, bp0, sc0, sv0, bs)
+    B = ctx.bsr(k * nrow0, k * ncol0, bs, bp, bc, bv)
+    for drop in (True, False):
+        want0 = bsr_ref.bsr_to_csr(nrow0, ncol0, bs, bp0, sc0, sv0, drop)
+        for a, b in zip(want0, bsr_ref.bsr_to_csr(nrow0, ncol0, bs, bp0, bc0, bv0, drop)):
+            assert a.tobytes() == b.tobytes()  # (distinct block columns: the stable order is the ascending one)
+        miss = tiled.tiled_mismatch(ctx.bsr_to_csr(B, drop_zeros=drop).download(), want0, k, ncol0, _where(nrow0))
+        assert miss is None, f"bsr_to_csr(drop_zeros={drop}) of unsorted blocks: {miss}"
+    del B
+    bad = bc.copy()
+    bad[-1] = 9 * k  # = nbc, in the last block: the validation's later trip
+    with pytest.raises(pkg.capi.SpmvError, match="index out of range"):
+        ctx.bsr(k * nrow0, k * ncol0, bs, bp, bad, bv)
+    RUNS["tiled unsorted"] += 1
+
+
+def test_the_longest_block_row_is_found_on_a_later_trip(ctx):
+    """bsr_row_max_kernel: one trip and 5 block rows of one block each, the last of three"""
+    bs, mb = 2, TRIP + 5
+    bp = np.concatenate([np.arange(mb), [mb + 2]]).astype(np.int32)
+    bc = np.concatenate([np.arange(mb - 1) % 3, [0, 1, 2]]).astype(np.int32)
+    A = ctx.bsr(bs * mb, bs * 3, bs, bp, bc, np.ones(len(bc) * bs * bs))
+    assert (A.info.nnz, A.info.max_row_nnz) == (len(bc) * bs * bs, 3 * bs)
+    RUNS["row max"] += 1
 
 
 # ---- plumbing ---------------------------------------------------------------------------------------------------------------------------
@@ -426,3 +639,17 @@ def test_band_product_against_its_csr_handle(ctx):
     m_bsr, m_csr = float(np.median(t_bsr)), float(np.median(t_csr))
     print(f"bs 4 band, 1M rows: BSR {m_bsr:.4f} ms, CSR kernel {C.info.kernel} {m_csr:.4f} ms, ratio {m_csr / m_bsr:.3f}")
     perf_expect(m_bsr <= m_csr, f"the bs = 4 band product takes {m_bsr:.4f} ms, its CSR AUTO handle (kernel {C.info.kernel}) {m_csr:.4f} ms")
+
+
+# ---- coverage -------------------------------------------------------------------------------------------------------------------------
+def test_every_instance_of_the_kernel_ran():
+    """every bsr_vector_kernel<BS, G, EDGE> that bsr_apply's switch can launch ran under exact values: the 15 cases of the switch
+    (read from csrc/kernels_bsr.hip), with and without the column edge"""
+    expect = {"exact": 7, "edges": 7, "entry points": 7, "tiled": 3, "tiled unsorted": 1, "row max": 1}
+    if any(RUNS[f] != c for f, c in expect.items()):
+        pytest.skip(f"the coverage check needs every test of this module (ran {dict(RUNS)}, expected {expect})")
+    cases = tiled.bsr_kernel_cases()
+    assert len(cases) == 15 and set(cases) == {(bs, lanes // (bs * bs)) for bs in range(2, 9) for lanes in _lanes(bs)}
+    need = {(bs, g, edge) for bs, g in cases for edge in (True, False)}
+    print(f"{len(INSTANCES)} instances of bsr_vector_kernel ran: {sorted(INSTANCES)}")
+    assert len(need) == 30 and INSTANCES == need, f"never ran: {sorted(need - INSTANCES)}; not in the switch: {sorted(INSTANCES - need)}"

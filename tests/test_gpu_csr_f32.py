@@ -6,7 +6,9 @@ Rounded: the conversion and its statistics equal the NumPy twin (tests/csr_f32_r
 CSR handle of the widened values forced to the row-parallel kernel at the same lanes (the kernel's contract), and lies in the derived
 gate of the twin's long-double product: a row of t entries is a sum of t + 1 terms, any order of them, with or without fma, stays
 within (t + 1) * 2^-52 * (|A||x| + |y0|)_i of the exact sum to first order.
-Then the plumbing, the solvers on a format-6 handle, and refinement against the twin's loop - the yardstick, never the engine.
+Then the plumbing, the solvers on a format-6 handle, and refinement against the twin's loop - the yardstick, never the engine - with
+the branches of the loop that a converging solve never takes; last, the set-up past one trip of its grid on block-diagonal copies
+(tests/tiled.py): bytes, statistics, refusals and exact products.
 """
 import gc
 
@@ -15,6 +17,7 @@ import pytest
 
 import csr_f32_ref as ref
 import exact
+import tiled
 
 pytestmark = pytest.mark.gpu
 AUTO, VECTOR, PANEL = 0, 1, 4
@@ -401,3 +404,177 @@ def test_the_edges_of_the_refinement_loop(ctx):
     dx = ctx.vector_from(np.zeros(n))
     outer, inner, res = ctx.refine(A, L, db, dx, max_outer=3, inner_max_iter=5, inner_tol=1e-4, rel_tol=1e-12)
     assert outer == 3 and inner == 15 and res < 1.0
+
+
+def test_a_step_that_grows_the_residual_gives_the_iterate_back(ctx):
+    """A_lo = 0.4 A: the correction is 2.5 times the right one, x = 0 + 2.5 A^-1 b has the residual 1.5 ||b||, and the loop takes the
+    branch "the step did not reduce ||r||": x is the iterate before the step, bit for bit, and res is its residual (the twin:
+    (1, 88, 1.0) with x back at zeros)"""
+    n, rp, col, val, f, A64, A32, b = SYSTEM
+    A = ctx.csr(n, n, rp, col, val)
+    A.set_kernel(VECTOR)  # the same bits of every residual from call to call
+    A_lo = ctx.csr(n, n, rp, col, 0.4 * val)
+    db = ctx.vector_from(b)
+    dx = ctx.vector_from(np.zeros(n))
+    outer, inner, res = ctx.refine(A, A_lo, db, dx, inner_tol=1e-4, rel_tol=1e-12)
+    assert (outer, res) == (1, 1.0) and inner > 0, (outer, inner, res)
+    assert np.array_equal(dx.download().view(np.uint64), np.zeros(n).view(np.uint64)), "x is not the iterate before the step"
+    x0 = np.random.default_rng(12).standard_normal(n)
+    dx = ctx.vector_from(x0)
+    res0 = ctx.refine(A, A_lo, db, dx, max_outer=0)
+    assert res0[:2] == (0, 0) and res0[2] > 1e-3 and np.array_equal(dx.download().view(np.uint64), x0.view(np.uint64))
+    outer, inner, res = ctx.refine(A, A_lo, db, dx, inner_tol=1e-4, rel_tol=1e-12)
+    assert outer == 1 and inner > 0 and res == res0[2], (outer, inner, res, res0)
+    assert np.array_equal(dx.download().view(np.uint64), x0.view(np.uint64)), "x is not the x0 passed in"
+
+
+def test_refinement_converges_then_stalls_and_returns_the_best_iterate(ctx):
+    """rel_tol = 0 can never be met: the residual falls to the rounding of the fp64 residual itself, a step no longer reduces it, and
+    the loop returns the iterate before that step with ITS residual (the twin stops after 6 outer steps at 6.65e-16)"""
+    n, rp, col, val, f, A64, A32, b = SYSTEM
+    A = ctx.csr(n, n, rp, col, val)
+    A.set_kernel(VECTOR)
+    L = ctx.csr_to_f32(A)
+    db = ctx.vector_from(b)
+    dx = ctx.vector_from(np.zeros(n))
+    outer, inner, res = ctx.refine(A, L, db, dx, max_outer=50, inner_tol=1e-4, rel_tol=0.0)
+    x = dx.download()
+    true = _true_residual(A64, x, b)
+    print(f"rel_tol = 0: outer {outer} inner {inner} reported {res:.3e} true {true:.3e}")
+    assert 1 < outer < 50 and inner > 0
+    again = ctx.refine(A, L, db, dx, max_outer=0)
+    assert again == (0, 0, res), (again, res)
+    assert np.array_equal(dx.download().view(np.uint64), x.view(np.uint64))
+    assert true <= 1e-14
+
+
+def test_refinement_with_a_preconditioned_inner_solver(ctx, pkg):
+    """precond reaches the inner solver: with A_lo = A from x = 0 the first residual is b itself and the inner solve is spmv_cg's
+    driver on (A, b), so its count is that of ctx.cg with the Jacobi preconditioner; a format-6 A_lo has no diagonal to read"""
+    n, rp, col, val, f, A64, A32, b = SYSTEM
+    JACOBI = pkg.capi.PRECOND_JACOBI
+    A = ctx.csr(n, n, rp, col, val)
+    A.set_kernel(VECTOR)
+    db = ctx.vector_from(b)
+    dx = ctx.vector_from(np.zeros(n))
+    iters, _ = ctx.cg(A, db, dx, max_iter=5000, rel_tol=1e-12, jacobi=True)
+    dx0 = ctx.vector_from(np.zeros(n))
+    plain, _ = ctx.cg(A, db, dx0, max_iter=5000, rel_tol=1e-12)
+    dx = ctx.vector_from(np.zeros(n))
+    outer, inner, res = ctx.refine(A, A, db, dx, precond=JACOBI, inner_max_iter=5000, inner_tol=1e-12, rel_tol=1e-10)
+    print(f"precond = JACOBI: outer {outer} inner {inner} (spmv_cg: {iters} with Jacobi, {plain} without) reported {res:.3e}")
+    assert outer == 1 and inner == iters and 0 < iters and res <= 1e-10, (outer, inner, iters, res)
+    assert _true_residual(A64, dx.download(), b) <= 1e-10
+    L = ctx.csr_to_f32(A)
+    x0 = np.arange(1.0, n + 1.0)
+    dx = ctx.vector_from(x0)
+    _refused(pkg, UNSUPPORTED, "Jacobi", lambda: ctx.refine(A, L, db, dx, precond=JACOBI))
+    assert np.array_equal(dx.download().view(np.uint64), x0.view(np.uint64))
+
+
+# ---- set-up kernels past one trip of their grid (tests/tiled.py) ---------------------------------------------------------------------------
+TRIP = tiled.max_grid() * tiled.block_lanes()  # items of one trip of a grid-stride kernel of csrc/convert_f32.hip
+TNCOL = ref.TILED_NCOL
+
+
+def _copies(rp):
+    k, cond = ref.tiled_copies(rp, TRIP)
+    assert all(cond.values()), (k, cond)
+    return k
+
+
+def _same_bytes(got, want, what):
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    if got.tobytes() != want.tobytes():
+        at = int(np.flatnonzero(got.view(np.uint64 if got.dtype == np.float64 else np.int32) != want.view(np.uint64 if got.dtype == np.float64 else np.int32))[0])
+        raise AssertionError(f"{what}[{at}] is {got[at]!r} against {want[at]!r}, trip {at // TRIP} of a kernel over this array")
+
+
+def test_conversion_and_statistics_of_block_diagonal_copies_past_one_trip(ctx):
+    """k copies of a 128-row base with the row lengths of ROUNDED: f32_pack, f32_widen and the row maximum take a later trip; the
+    words are the base's tiled, the counts k times the base's, the largest change the base's - or that of one value of the LAST copy"""
+    rp0, col0, val0 = ref.tiled_rounded()
+    nrow0, nnz0 = len(rp0) - 1, len(val0)
+    k = _copies(rp0)
+    nrow, ncol = k * nrow0, k * TNCOL
+    f0, inexact0, under0, rel0 = ref.demote(val0)
+    assert under0 == 3 and inexact0 > 0.99 * nnz0
+    rp, col, val = tiled.tile_csr(k, TNCOL, rp0, col0, val0)
+    print(f"{k} copies: {nrow} rows, {len(val)} entries, one trip {TRIP}")
+    A = ctx.csr_to_f32(ctx.csr(nrow, ncol, rp, col, val))
+    assert A.f32_info() == (k * inexact0, k * under0, rel0)
+    assert (A.info.nnz, A.info.max_row_nnz) == (k * nnz0, 300)
+    assert tiled.tiled_mismatch(A.download(), (rp0, col0, ref.widen(f0)), k, TNCOL) is None
+    assert tiled.tiled_mismatch(ctx.f32_to_csr(A).download(), (rp0, col0, ref.widen(f0)), k, TNCOL) is None
+    del A
+    # one value of the last copy raises the largest relative change: the maximum over the bits is formed across the trips
+    worse = val.copy()
+    worse[-1] = ref.WORST_VALUE
+    assert ref.WORST_REL > rel0 and ref.demote(worse[-nnz0:])[1:] == (inexact0, under0, ref.WORST_REL)
+    assert ctx.csr_to_f32(ctx.csr(nrow, ncol, rp, col, worse)).f32_info() == (k * inexact0, k * under0, ref.WORST_REL)
+    # the float stream uploaded: the same bytes, no statistics
+    U = ctx.csr_f32(nrow, ncol, rp, col, np.tile(f0, k))
+    assert U.f32_info() == (0, 0, 0.0) and U.info.max_row_nnz == 300
+    assert tiled.tiled_mismatch(U.download(), (rp0, col0, ref.widen(f0)), k, TNCOL) is None
+
+
+def test_products_of_block_diagonal_copies_are_exact_past_one_trip(ctx):
+    """dyadic values on the same pattern: the forward product, spmv_apply_dot and the transposed product - whose set-up widens,
+    transposes and packs 4.4 M entries - are the base's integer results tiled"""
+    rp0, col0 = ref.tiled_structure()
+    nrow0, nnz0 = len(rp0) - 1, len(col0)
+    k = _copies(rp0)
+    nrow, ncol = k * nrow0, k * TNCOL
+    rng = np.random.default_rng(173)
+    bits, e = exact.choose_bits_dot(k * nnz0, max(nrow, ncol))
+    val0 = exact.dyadic(rng, nnz0, bits, e)
+    i, j, _ = exact.csr_entries(rp0, col0, val0)
+    x0, y00, w0 = exact.poison(exact.dyadic(rng, TNCOL, bits, e), j), exact.dyadic(rng, nrow0, bits, e), exact.dyadic(rng, nrow0, bits, e)
+    xt0, yt00 = exact.poison(exact.dyadic(rng, nrow0, bits, e), i), exact.dyadic(rng, TNCOL, bits, e)
+    A = ctx.csr_to_f32(ctx.csr(nrow, ncol, *tiled.tile_csr(k, TNCOL, rp0, col0, val0)))
+    assert A.f32_info() == (0, 0, 0.0)
+    dx, dw = ctx.vector_from(np.tile(x0, k)), ctx.vector_from(np.tile(w0, k))
+    onto, over = exact.exact_product(nrow0, i, j, val0, x0, e, y0=y00), exact.exact_product(nrow0, i, j, val0, x0, e)
+    dy = ctx.vector_from(np.tile(y00, k))
+    ctx.apply(A, dx, dy)
+    ctx.sync()
+    _same_bytes(dy.download(), np.tile(onto, k), "forward: y")
+    dy = ctx.vector_from(np.full(nrow, np.nan))
+    dot = ctx.apply_dot(A, dx, dy, dw, overwrite=True)
+    _same_bytes(dy.download(), np.tile(over, k), "apply_dot: y")
+    assert dot == exact.exact_dot(np.tile(w0, k), np.tile(over, k), e, 2 * e), "the dot over every copy"
+    dyt = ctx.vector_from(np.tile(yt00, k))
+    ctx.apply_transpose(A, ctx.vector_from(np.tile(xt0, k)), dyt)
+    ctx.sync()
+    _same_bytes(dyt.download(), np.tile(exact.exact_product(TNCOL, j, i, val0, xt0, e, y0=yt00), k), "transposed: y")
+
+
+def test_refusals_find_values_and_columns_on_a_later_trip(ctx, pkg):
+    """a NaN in the last copy and a 1e39 in a copy beyond the first trip: both counted, and the first refused row is the EARLIER one,
+    by its global index; a packed column equal to ncol in the last entry is refused at upload"""
+    rp0, col0, val0 = ref.tiled_rounded()
+    nrow0, nnz0 = len(rp0) - 1, len(val0)
+    k = _copies(rp0)
+    nrow, ncol = k * nrow0, k * TNCOL
+    rp, col, val = tiled.tile_csr(k, TNCOL, rp0, col0, val0)
+    copy, r_big, r_nan = TRIP // nnz0 + 2, 43, 11  # (rows with entries)
+    assert rp0[r_big + 1] > rp0[r_big] and rp0[r_nan + 1] > rp0[r_nan] and copy * nnz0 > TRIP and copy < k - 1
+    val[copy * nnz0 + rp0[r_big]] = 1e39
+    val[(k - 1) * nnz0 + rp0[r_nan]] = np.nan
+    C = ctx.csr(nrow, ncol, rp, col, val)
+    _refused(pkg, INVALID, rf"spmv_csr_to_f32: 2 values .* row {copy * nrow0 + r_big}\)", lambda: ctx.csr_to_f32(C))
+    del C
+    f = np.tile(ref.demote(val0)[0], k)
+    bad = col.copy()
+    bad[-1] = ncol
+    with pytest.raises(pkg.capi.SpmvError, match="index out of range"):
+        ctx.csr_f32(nrow, ncol, rp, bad, f)
+
+
+def test_the_longest_row_is_found_on_a_later_trip(ctx):
+    """csr_f32_row_max_kernel: one trip and 5 rows of one entry each, the last of three"""
+    nrow = TRIP + 5
+    rp = np.concatenate([np.arange(nrow), [nrow + 2]]).astype(np.int32)
+    col = np.concatenate([np.arange(nrow - 1) % 3, [0, 1, 2]]).astype(np.int32)
+    A = ctx.csr_f32(nrow, 3, rp, col, np.ones(len(col), np.float32))
+    assert (A.info.nnz, A.info.max_row_nnz) == (len(col), 3)

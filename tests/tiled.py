@@ -104,6 +104,30 @@ def rcm_row_lanes():
     return _constant(code, "kRowLanes")
 
 
+def bsr_slots(bs):
+    """whole blocks of bs x bs values a wavefront holds at a time (bsr_slots): S of the BSR tests"""
+    code = _code("bsr_settings.hpp")
+    assert "constexpr int bsr_slots(int bs) { return kBsrWave / (bs * bs); }" in code, "bsr_settings.hpp no longer says bsr_slots = kBsrWave / bs^2"
+    return _constant(code, "kBsrWave") // (bs * bs)
+
+
+def bsr_rows_per_workgroup(bs, lanes):
+    """block rows a workgroup of the BSR product holds at `lanes` lanes a block row: the header's text, recomputed"""
+    code = _code("bsr_settings.hpp")
+    for text in ("constexpr int bsr_rows_per_wave(int bs, int lanes) { return bsr_slots(bs) / (lanes / (bs * bs)); }",
+                 "constexpr int bsr_rows_per_workgroup(int bs, int lanes) { return (kBsrWorkgroup / kBsrWave) * bsr_rows_per_wave(bs, lanes); }"):
+        assert text in code, f"bsr_settings.hpp no longer says: {text}"
+    assert lanes % (bs * bs) == 0 and bsr_slots(bs) % (lanes // (bs * bs)) == 0, "lanes: bs^2 times a divisor of the slots"
+    return (_constant(code, "kBsrWorkgroup") // _constant(code, "kBsrWave")) * (bsr_slots(bs) // (lanes // (bs * bs)))
+
+
+def bsr_kernel_cases():
+    """[(bs, G)] of the instances bsr_apply's switch launches (csrc/kernels_bsr.hip): G blocks of bs x bs values a step"""
+    found = re.findall(r"case (\d+): return launch_bsr<(\d+), (\d+)>\(ctx, A, x, y\);", _code("kernels_bsr.hip"))
+    assert found and all(int(label) == int(bs) * 100 + int(g) for label, bs, g in found), "bsr_apply's switch is keyed bs * 100 + g"
+    return [(int(bs), int(g)) for _, bs, g in found]
+
+
 # ---- the tiling --------------------------------------------------------------------------------------------------------------------
 def tile_csr(k, ncol0, rp, cc, cv=None):
     """(row_ptr, col[, val]) of the block-diagonal matrix of k copies of the CSR matrix (rp, cc, cv) with ncol0 columns: copy c holds
@@ -115,6 +139,15 @@ def tile_csr(k, ncol0, rp, cc, cv=None):
     out_rp = np.concatenate([[0], (rp[None, 1:] + nnz0 * at).ravel()]).astype(np.int32)
     out_cc = (cc[None, :] + ncol0 * at).ravel().astype(np.int32)
     return (out_rp, out_cc) if cv is None else (out_rp, out_cc, np.tile(np.asarray(cv, dtype=np.float64), k))
+
+
+def tile_bsr(k, nbc0, bp, bc, bv, bs):
+    """(brow_ptr, bcol, val) of the block-diagonal matrix of k copies of the BSR matrix (bp, bc, bv) with nbc0 block columns of
+    bs x bs values: tile_csr on the block arrays, every copy's blocks the same bytes"""
+    bv = np.asarray(bv, dtype=np.float64)
+    assert len(bv) == len(bc) * bs * bs
+    out_bp, out_bc = tile_csr(k, nbc0, bp, bc)
+    return out_bp, out_bc, np.tile(bv, k)
 
 
 def trips(rows, per_workgroup, grid):
