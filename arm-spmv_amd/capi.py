@@ -684,8 +684,8 @@ class Context:
     def bicgstab(self, A: "Matrix", b: "Vector", x: "Vector", max_iter: int = 1000, rel_tol: float = 1e-8, check_every: int = 1,
                  precond: int = 0):
         """A x = b for a square, not necessarily symmetric A by right-preconditioned BiCGSTAB on the device, from the x passed in: any
-        format, two forward products per iteration, no transposed state.  precond: PRECOND_NONE, or PRECOND_JACOBI or PRECOND_ILU0 (the
-        ILU(0) factors, set up on first use; two applications per iteration) on a CSR handle.
+        format, two forward products per iteration, no transposed state.  precond: any PRECOND_* that the library's table of preconditioners
+        (csrc/precond.hip) does not refuse for this solver, on the handles its row takes; two applications per iteration.
         Stops at ||r|| <= rel_tol * ||b||; returns (iterations, ||r|| / ||b||)"""
         it, res = C.c_int32(0), C.c_double(0.0)
         _check(self._lib.spmv_bicgstab(self.h, A.h, b.h, x.h, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))
@@ -695,8 +695,8 @@ class Context:
               precond: int = 0):
         """A x = b for a square, not necessarily symmetric A by right-preconditioned restarted GMRES(restart) on the device, from the x
         passed in: any format, one forward product and one preconditioner application per iteration, classical Gram-Schmidt twice
-        against a basis of restart + 1 work vectors (restart: 1 .. 64; 0: 30).  precond: PRECOND_NONE, or PRECOND_JACOBI or
-        PRECOND_ILU0 (the ILU(0) factors, set up on first use) on a CSR handle.  Does not break down where BiCGSTAB does; stagnation
+        against a basis of restart + 1 work vectors (restart: 1 .. 64; 0: 30).  precond: any PRECOND_* that the library's table of
+        preconditioners (csrc/precond.hip) does not refuse for this solver, on the handles its row takes.  Does not break down where BiCGSTAB does; stagnation
         (GMRES(1) on a rotation) is no error.  Stops at ||r|| <= rel_tol * ||b||; returns (iterations, ||r|| / ||b||)"""
         it, res = C.c_int32(0), C.c_double(0.0)
         _check(self._lib.spmv_gmres(self.h, A.h, b.h, x.h, restart, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))
@@ -733,7 +733,7 @@ class Context:
                precond: int | None = None):
         """the nev (default k) smallest - largest: largest - eigenvalues of a symmetric A and their vectors by LOBPCG with a block of
         k <= 16 vectors, synchronous.  X: nrow * k entries, column-major; holds the start block (gen_vector(nrow * k)) and receives
-        the unit vectors.  precond: gmres's set (None: PRECOND_NONE), applied column by column; it must be positive definite.
+        the unit vectors.  precond: as for gmres, by the same table (None: PRECOND_NONE), applied column by column; it must be positive definite.
         Stops when resid_j = ||A x_j - theta_j x_j|| <= tol for the first nev columns, or after max_iter iterations (no error).
         Returns (theta[k], resid[k], iterations)"""
         theta, resid, it = np.zeros(max(int(k), 1)), np.zeros(max(int(k), 1)), C.c_int32(0)

@@ -103,11 +103,8 @@ void mat_free(spmv_mat* m)
     if (m->win_span) (void)hipFree(m->win_span);
     ell_layouts_free(m);
     csr_layouts_free(m, kCsrAllLayouts);
-    symgs_free(m);
-    ilu0_free(m);
-    cheby_free(m);
-    amg_free(m);
-    fsai_free(m);
+    for (const precond_row& P : kPreconds)  // (in id order)
+        if (P.free) P.free(m);
     if (m->rowgrouped) mat_free(m->rowgrouped);
     coo_free_bins(m);
     delete m;
@@ -837,6 +834,8 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
 {
     SPMV_REQUIRE(m && name, "null argument");
     if (int rc = SPMV_OK; ell_set_param(m, name, value, &rc)) return rc;  // "ell_tiled_values", "ell_dia_order"
+    for (const precond_row& P : kPreconds)  // the preconditioners' own, each by its unit's hook; they take effect at the next set-up
+        if (int rc = SPMV_OK; P.set_param && P.set_param(m, name, value, &rc)) return rc;
     if (!strcmp(name, "panel_rows"))
         m->pb_group_rows = (int32_t)value;
     else if (!strcmp(name, "panel_width"))
@@ -918,26 +917,6 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
         m->tp_offer_csr = value < 0 || value > 2 ? 1 : (int32_t)value;  // (2: tests - a carved piece is taken whatever the timings say)
     else if (!strcmp(name, "panel_trial"))
         m->pb_trial = (int32_t)value;
-    else if (!strcmp(name, "symgs_order"))  // 1 multicolour, 0 the matrix's own row order; takes effect at the next set-up / sweep
-    {
-        SPMV_REQUIRE(value == 0 || value == 1, "symgs_order: 0 (row order) or 1 (multicolour), got %lld", (long long)value);
-        m->gs_order = (int32_t)value;
-    }
-    else if (!strcmp(name, "ilu0_order"))  // 1 multicolour, 0 the matrix's own row order; takes effect at the next set-up / application
-    {
-        SPMV_REQUIRE(value == 0 || value == 1, "ilu0_order: 0 (row order) or 1 (multicolour), got %lld", (long long)value);
-        m->ilu_order = (int32_t)value;
-    }
-    else if (int arc = SPMV_OK; amg_set_param(m, name, value, &arc))  // "amg_level_kernel": at the next set-up
-    {
-        if (arc != SPMV_OK) return arc;
-    }
-    else if (int frc = SPMV_OK; fsai_set_param(m, name, value, &frc))  // "fsai_level": at the next set-up of a solver's own
-    {
-        if (frc != SPMV_OK) return frc;
-    }
-    else if (int crc = SPMV_OK; cheby_set_param(m, name, value, &crc))  // "cheby_degree", "cheby_ratio", "cheby_lanczos_steps": at the next set-up
-        return crc;
     else if (!strcmp(name, "twophase_panel_cols"))  // takes effect at the next spmv_mat_set_kernel(TWOPHASE)
         m->tp_pcols_req = (int32_t)value;
     else if (!strcmp(name, "twophase_placement_budget_mb"))
@@ -1022,20 +1001,9 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value)
 int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
 {
     SPMV_REQUIRE(m && name && value, "null argument");
-    if (!strncmp(name, "symgs_", 6))
-    {
-        SPMV_REQUIRE(symgs_info(m, name, value) == SPMV_OK, "unknown parameter '%s'", name);
-        return SPMV_OK;
-    }
-    if (!strncmp(name, "ilu0_", 5))
-    {
-        SPMV_REQUIRE(ilu0_info(m, name, value) == SPMV_OK, "unknown parameter '%s'", name);
-        return SPMV_OK;
-    }
-    if (amg_get_param(m, name, value)) return SPMV_OK;  // "amg_ready", "amg_levels", "amg_bytes", "amg_launches", "amg_mis_rounds", "amg_level_kernel"
-    if (fsai_get_param(m, name, value)) return SPMV_OK;  // "fsai_level", "fsai_ready", "fsai_bytes", "fsai_max_row"
+    for (const precond_row& P : kPreconds)  // the preconditioners' own: what each unit's hook lists
+        if (P.get_param && P.get_param(m, name, value)) return SPMV_OK;
     if (spgemm_get_param(m, name, value)) return SPMV_OK;  // "spgemm_products", "spgemm_rows_lds", "spgemm_rows_sorted", "spgemm_lds_products", ...
-    if (cheby_get_param(m, name, value)) return SPMV_OK;  // "cheby_ready", "cheby_degree", "cheby_bytes", "cheby_launches", ...
     if (transpose_get_param(m, name, value)) return SPMV_OK;  // "transpose_ready", "transpose_bytes", "transpose_kernel", ...
     if (!strcmp(name, "panel_keep_csr"))
         *value = (m->b && m->v) || m->nnz == 0 ? 1 : 0;
@@ -1451,12 +1419,8 @@ int spmv_apply_dot(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec
 }
 
 // The five solves.  Every check is made before the device is touched, so that they hold (and are tested) on a machine without one;
-// the checks they share and what each solver's refusals depend on (solver_rules) are solver_host.hpp's.
-static const solver_rules kCgRules       = {"spmv_cg", "the matrix", true, nullptr, nullptr, solver_rules::jacobi_arrays_unsupported, nullptr, nullptr, nullptr};
-static const solver_rules kCgMultiRules  = {"spmv_cg_multi", "the matrix", false, "k columns", "k columns", solver_rules::jacobi_arrays_elsewhere, "k columns", "k columns", "k columns"};
-static const solver_rules kBicgstabRules = {"spmv_bicgstab", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr, nullptr};
-static const solver_rules kGmresRules    = {"spmv_gmres", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr, nullptr};
-
+// the checks they share are solver_host.hpp's, and what each solver's refusals depend on (k*Rules) stands beside the preconditioners'
+// table (precond.hip).
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
             int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
 {
@@ -1563,8 +1527,6 @@ int spmv_block_combine(spmv_ctx* ctx, int64_t n, int32_t p, const spmv_vec* S, i
 }
 
 // extreme eigenpairs of a symmetric matrix by LOBPCG (solver_lobpcg.hip)
-static const solver_rules kLobpcgRules = {"spmv_lobpcg", "the matrix (shard)", false, "this solver", nullptr, solver_rules::jacobi_arrays_invalid, nullptr, nullptr, nullptr};
-
 int spmv_lobpcg(spmv_ctx* ctx, const spmv_mat* A, int32_t k, int32_t nev, int32_t largest, spmv_vec* X, int32_t max_iter, double tol, int32_t precond,
                 double* theta, double* resid, int32_t* iters)
 {
@@ -1604,8 +1566,7 @@ int spmv_symgs(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32
 {
     SPMV_REQUIRE(ctx && A && b && x, "spmv_symgs: null argument");
     SPMV_REQUIRE(A->ctx == ctx, "spmv_symgs: the matrix belongs to another context");
-    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "spmv_symgs: b has %lld and x %lld entries, the matrix %d rows", (long long)b->n,
-                 (long long)x->n, A->nrow);
+    SPMV_TRY(check_vector_lengths("spmv_symgs", A, "b", b, "x", x));
     SPMV_REQUIRE(b->d != x->d || x->n == 0, "spmv_symgs: b and x must not alias");
     SPMV_REQUIRE(sweeps >= 0, "spmv_symgs: sweeps = %d", sweeps);
     SPMV_TRY(use_device(ctx));
@@ -1630,9 +1591,7 @@ int spmv_ilu0_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_ve
     SPMV_REQUIRE(ctx && A && r && z, "spmv_ilu0_solve: null argument");
     SPMV_REQUIRE(A->ctx == ctx, "spmv_ilu0_solve: the matrix belongs to another context");
     SPMV_TRY(ilu0_check_handle(A, "spmv_ilu0_solve"));
-    SPMV_REQUIRE(r->n == A->nrow && z->n == A->nrow, "spmv_ilu0_solve: r has %lld and z %lld entries, the matrix %d rows", (long long)r->n,
-                 (long long)z->n, A->nrow);
-    SPMV_REQUIRE(r->n == 0 || r->d + r->n <= z->d || z->d + z->n <= r->d, "spmv_ilu0_solve: r and z must not overlap");
+    SPMV_TRY(check_vector_pair("spmv_ilu0_solve", A, "r", r, "z", z));
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
     SPMV_TRY(ilu0_setup(const_cast<spmv_mat*>(A)));  // first call: order, symbolic, numeric (synchronous); later calls: nothing
@@ -1702,9 +1661,7 @@ int spmv_chebyshev_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, sp
 {
     SPMV_REQUIRE(ctx && A && r && z, "spmv_chebyshev_solve: null argument");
     SPMV_TRY(cheby_check_handle(A, "spmv_chebyshev_solve"));
-    SPMV_REQUIRE(r->n == A->nrow && z->n == A->nrow, "spmv_chebyshev_solve: r has %lld and z %lld entries, the matrix %d rows", (long long)r->n,
-                 (long long)z->n, A->nrow);
-    SPMV_REQUIRE(vectors_disjoint(r, z), "spmv_chebyshev_solve: r and z must not overlap");
+    SPMV_TRY(check_vector_pair("spmv_chebyshev_solve", A, "r", r, "z", z));
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
     return cheby_apply(ctx, A, r->d, z->d);
@@ -1783,9 +1740,7 @@ int spmv_amg_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec
 {
     SPMV_REQUIRE(ctx && A && r && z, "spmv_amg_solve: null argument");
     SPMV_TRY(amg_check_handle(A, "spmv_amg_solve"));
-    SPMV_REQUIRE(r->n == A->nrow && z->n == A->nrow, "spmv_amg_solve: r has %lld and z %lld entries, the matrix %d rows", (long long)r->n,
-                 (long long)z->n, A->nrow);
-    SPMV_REQUIRE(vectors_disjoint(r, z), "spmv_amg_solve: r and z must not overlap");
+    SPMV_TRY(check_vector_pair("spmv_amg_solve", A, "r", r, "z", z));
     if (!A->amg) SPMV_FAIL(SPMV_ERR_INVALID, "spmv_amg_solve: the handle was not set up (spmv_amg_setup)");
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
@@ -1810,9 +1765,7 @@ int spmv_fsai_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_ve
     SPMV_REQUIRE(ctx && A && r && z, "%s: null argument", who);
     SPMV_TRY(fsai_check_handle(A, who));
     SPMV_REQUIRE(A->ctx == ctx, "%s: the matrix belongs to another context", who);
-    SPMV_REQUIRE(r->n == A->nrow && z->n == A->nrow, "%s: r has %lld and z %lld entries, the matrix %d rows", who, (long long)r->n, (long long)z->n,
-                 A->nrow);
-    SPMV_REQUIRE(vectors_disjoint(r, z), "%s: r and z must not overlap", who);
+    SPMV_TRY(check_vector_pair(who, A, "r", r, "z", z));
     if (!A->fsai) SPMV_FAIL(SPMV_ERR_INVALID, "%s: the handle was not set up (spmv_fsai_setup)", who);
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
@@ -1840,9 +1793,7 @@ int spmv_chebyshev(spmv_ctx* ctx, spmv_mat* A, const spmv_vec* b, spmv_vec* x)
 {
     SPMV_REQUIRE(ctx && A && b && x, "spmv_chebyshev: null argument");
     SPMV_TRY(cheby_check_handle(A, "spmv_chebyshev"));
-    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "spmv_chebyshev: b has %lld and x %lld entries, the matrix %d rows", (long long)b->n,
-                 (long long)x->n, A->nrow);
-    SPMV_REQUIRE(vectors_disjoint(b, x), "spmv_chebyshev: b and x must not overlap");
+    SPMV_TRY(check_vector_pair("spmv_chebyshev", A, "b", b, "x", x));
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
     return cheby_smooth(ctx, A, b->d, x->d);

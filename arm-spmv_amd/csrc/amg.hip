@@ -854,14 +854,7 @@ int dense_inverse(spmv_ctx* ctx, const spmv_mat* A, double** inv_out)
 }  // namespace
 
 // ---- checks on the host: the leading fields of the handle alone ------------------------------------------------------------------
-int amg_check_handle(const spmv_mat* m, const char* who)
-{
-    if (m->format != SPMV_FMT_CSR) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: AMG needs a CSR handle (format %d)", who, m->format);
-    SPMV_REQUIRE(m->nrow == m->ncol && m->row_begin == 0, "%s: AMG needs the whole square matrix (%d x %d, first row %lld)", who, m->nrow, m->ncol,
-                 (long long)m->row_begin);
-    SPMV_REQUIRE(m->nnz == 0 || (m->b && m->v), "%s: the CSR arrays are gone (panel_keep_csr = 0 released them)", who);
-    return SPMV_OK;
-}
+int amg_check_handle(const spmv_mat* m, const char* who) { return check_whole_square_csr(m, who, "AMG"); }
 
 int amg_check_setup(const spmv_mat* m, int max_levels, int coarse_max, int smooth_degree, double strength, double overcorrection, const char* who)
 {

@@ -444,18 +444,12 @@ int cheby_coefficients(int degree, double lmin, double lmax, double* c0, double*
 }
 
 // ---- checks on the host: the leading fields of the handle alone ------------------------------------------------------------------
-int cheby_check_handle(const spmv_mat* m, const char* who)
-{
-    SPMV_REQUIRE(m->nrow == m->ncol && m->row_begin == 0, "%s: Chebyshev needs the whole square matrix (%d x %d, first row %lld)", who, m->nrow,
-                 m->ncol, (long long)m->row_begin);
-    return SPMV_OK;
-}
+int cheby_check_handle(const spmv_mat* m, const char* who) { return check_whole_square(m, who, "Chebyshev"); }
 
 int cheby_check_scaled(const spmv_mat* m, const char* who)
 {
     SPMV_REQUIRE(m->format == SPMV_FMT_CSR, "%s: the Jacobi scaling reads the diagonal of a CSR handle (format %d)", who, m->format);
-    SPMV_REQUIRE(m->nnz == 0 || (m->b && m->v), "%s: the CSR arrays are gone (panel_keep_csr = 0 released them): no diagonal for the Jacobi scaling", who);
-    return SPMV_OK;
+    return check_csr_arrays(m, who, ": no diagonal for the Jacobi scaling");
 }
 
 int cheby_check_setup(const spmv_mat* m, int degree, int scaled, double lmin, double lmax, const char* who)

@@ -499,7 +499,8 @@ bool adds_into_y_with_atomics(const spmv_mat* A);       // global_atomic_add_f64
 // The five solves' drivers.  Each is entered from its ABI entry (abi.hip) behind the argument checks and use_device, zeroes its
 // outputs, returns at an empty system, and shares its host side - the workspace that owns its device memory, the preconditioner's
 // set-up and application, the looks at its scalars - with the others through solver_host.hpp.
-// solver.hip: conjugate gradients for a symmetric positive definite A (precond: NONE, JACOBI, SYMGS, ILU0, CHEBYSHEV, AMG)
+// Which driver takes which preconditioner is written down once, beside the preconditioners' table (precond.hip: kPreconds, k*Rules).
+// solver.hip: conjugate gradients for a symmetric positive definite A
 int cg_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
              int precond, int* iters, double* rel_resid);
 int vec_dot_accumulate(spmv_ctx* ctx, const double* x, const double* y, int64_t n, double* device_out);
@@ -509,15 +510,15 @@ int cg_multi_solve(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* B,
 // solver_cgls.hip: CGLS for min ||b - A x||^2 + damp^2 ||x||^2 over the forward and the transposed product of any handle
 int cgls_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                double damp, int* iters, double* rel_normal_resid, double* rel_resid);
-// solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle (precond: NONE, JACOBI, ILU0, CHEBYSHEV, AMG)
+// solver_bicgstab.hip: right-preconditioned BiCGSTAB for square A over two forward products of any handle
 int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int max_iter, double rel_tol, int check_every,
                    int precond, int* iters, double* rel_resid);
 // solver_gmres.hip: right-preconditioned restarted GMRES(restart) for square A over one forward product of any handle per iteration
-// (restart: 1 .. 64; precond: NONE, JACOBI, ILU0, CHEBYSHEV, AMG)
+// (restart: 1 .. 64)
 int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int restart, int max_iter, double rel_tol, int check_every,
                 int precond, int* iters, double* rel_resid);
 // solver_lobpcg.hip: LOBPCG for the k smallest (largest) eigenpairs of a symmetric A over one forward product per active column and
-// iteration (k: 1 .. 16; precond: NONE, JACOBI, ILU0, CHEBYSHEV, AMG); X: n x k, column-major, ld = n
+// iteration (k: 1 .. 16); X: n x k, column-major, ld = n
 int lobpcg_solve(spmv_ctx* ctx, const spmv_mat* A, int k, int nev, bool largest, double* X, int max_iter, double tol, int precond, double* theta,
                  double* resid, int* iters);
 // block_ops.hip: G = U^T V and Out = S C for column-major blocks of up to kBlockMaxCols columns (the layout and the contracts: there)
@@ -614,11 +615,17 @@ int mat_validate(const spmv_mat* m);
 int exclusive_scan_i32(spmv_ctx* ctx, const int32_t* in, int32_t* out, int64_t n);
 constexpr int32_t kCsrAutoNoSegscan = -1;  // coo_to_csr's force_kernel: AUTO among the kernels a COO handle does not have itself
 int coo_to_csr(spmv_ctx* ctx, const spmv_mat* coo, spmv_mat** out, int32_t force_kernel = 0 /* SPMV_CSR_AUTO: select */);
+// The preconditioners.  Their host side is reached through one table, a row per SPMV_PRECOND_* id (precond.hpp); the pieces their
+// handle checks are built from are precond.hip's (`noun`: the unit's name in the message):
+int  check_whole_square(const spmv_mat* m, const char* who, const char* noun);      // INVALID: not square, or a shard that starts behind row 0
+int  check_csr_arrays(const spmv_mat* m, const char* who, const char* what_for);    // INVALID: arrays released; what_for: "" or ": no ... for ..."
+int  check_whole_square_csr(const spmv_mat* m, const char* who, const char* noun);  // UNSUPPORTED: not CSR; then the two above
 // symgs.hip
 int  symgs_setup(spmv_mat* m);
 void symgs_free(spmv_mat* m);
 int  symgs_sweep(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, bool zero_guess);
-int  symgs_info(const spmv_mat* m, const char* what, int64_t* value);
+bool symgs_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "symgs_*"; false: not one of them
+bool symgs_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "symgs_order"; false: not that
 int  symgs_sequence(const spmv_mat* m, int32_t* out);
 // ilu0.hip: ILU(0) of a CSR handle in sweep order and its application z = U^-1 L^-1 r (SPMV_PRECOND_ILU0)
 int  ilu0_check_handle(const spmv_mat* m, const char* who);  // on the host: UNSUPPORTED (not CSR) / INVALID (a shard, not square, arrays released)
@@ -627,7 +634,8 @@ void ilu0_free(spmv_mat* m);
 int  ilu0_apply(spmv_ctx* ctx, const spmv_mat* A, const double* r, double* z);  // asynchronous; r and z must not overlap
 int  ilu0_factor_values(const spmv_mat* m, double* out);      // aligned to the handle's own entries, to the host
 int  ilu0_sequence(const spmv_mat* m, int32_t* out);
-int  ilu0_info(const spmv_mat* m, const char* what, int64_t* value);
+bool ilu0_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "ilu0_*"; false: not one of them
+bool ilu0_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "ilu0_order"; false: not that
 // chebyshev.hip: the Chebyshev polynomial preconditioner z = p_d(diag(s) A) diag(s) r (SPMV_PRECOND_CHEBYSHEV), and the Lanczos estimate
 int  cheby_coefficients(int degree, double lmin, double lmax, double* c0, double* c1, double* c2);  // host only; c1, c2: degree entries
 int  cheby_check_handle(const spmv_mat* m, const char* who);  // on the host: INVALID (not square, a shard that starts behind row 0)

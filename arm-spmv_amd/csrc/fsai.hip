@@ -235,14 +235,7 @@ void state_free(fsai_state* st)
 }  // namespace
 
 // the handles FSAI takes, checked on the host: a CSR handle that holds the whole square matrix and still has its arrays
-int fsai_check_handle(const spmv_mat* m, const char* who)
-{
-    if (m->format != SPMV_FMT_CSR) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: FSAI needs a CSR handle (format %d)", who, m->format);
-    SPMV_REQUIRE(m->nrow == m->ncol && m->row_begin == 0, "%s: FSAI needs the whole square matrix (%d x %d, first row %lld)", who, m->nrow, m->ncol,
-                 (long long)m->row_begin);
-    SPMV_REQUIRE(m->nnz == 0 || (m->b && m->v), "%s: the CSR arrays are gone (panel_keep_csr = 0 released them)", who);
-    return SPMV_OK;
-}
+int fsai_check_handle(const spmv_mat* m, const char* who) { return check_whole_square_csr(m, who, "FSAI"); }
 
 int fsai_check_level(int32_t level, const char* who)
 {

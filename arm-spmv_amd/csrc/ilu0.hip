@@ -250,14 +250,7 @@ size_t launches_of(const tri_part& p)
 }  // namespace
 
 // the handles ILU(0) takes, checked on the host: a CSR handle that holds the whole square matrix and still has its arrays
-int ilu0_check_handle(const spmv_mat* m, const char* who)
-{
-    if (m->format != SPMV_FMT_CSR) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: ILU(0) needs a CSR handle (format %d)", who, m->format);
-    SPMV_REQUIRE(m->nrow == m->ncol && m->row_begin == 0, "%s: ILU(0) needs the whole square matrix (%d x %d, first row %lld)", who, m->nrow,
-                 m->ncol, (long long)m->row_begin);
-    SPMV_REQUIRE(m->nnz == 0 || (m->b && m->v), "%s: the CSR arrays are gone (panel_keep_csr = 0 released them)", who);
-    return SPMV_OK;
-}
+int ilu0_check_handle(const spmv_mat* m, const char* who) { return check_whole_square_csr(m, who, "ILU(0)"); }
 
 void ilu0_free(spmv_mat* m)
 {
@@ -466,7 +459,7 @@ int ilu0_sequence(const spmv_mat* m, int32_t* out)
     return SPMV_OK;
 }
 
-int ilu0_info(const spmv_mat* m, const char* what, int64_t* value)
+bool ilu0_get_param(const spmv_mat* m, const char* what, int64_t* value)
 {
     const ilu0_plan* g = m->ilu;
     if (!strcmp(what, "ilu0_order"))
@@ -484,7 +477,19 @@ int ilu0_info(const spmv_mat* m, const char* what, int64_t* value)
     else if (!strcmp(what, "ilu0_bytes"))
         *value = g ? g->bytes : 0;
     else
-        return SPMV_ERR_INVALID;
-    return SPMV_OK;
+        return false;
+    return true;
+}
+
+// "ilu0_order": 1 multicolour, 0 the matrix's own row order; takes effect at the next set-up / application
+bool ilu0_set_param(spmv_mat* m, const char* name, int64_t value, int* rc)
+{
+    if (strcmp(name, "ilu0_order")) return false;
+    *rc = value == 0 || value == 1 ? SPMV_OK : SPMV_ERR_INVALID;
+    if (*rc == SPMV_OK)
+        m->ilu_order = (int32_t)value;
+    else
+        set_error("ilu0_order: 0 (row order) or 1 (multicolour), got %lld", (long long)value);
+    return true;
 }
 }  // namespace spmv

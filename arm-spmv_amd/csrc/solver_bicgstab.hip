@@ -335,15 +335,15 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
     *rel_resid            = 0.0;
     if (n == 0) return SPMV_OK;
     hipStream_t st  = ctx->stream;
-    const bool  pre = precond == SPMV_PRECOND_JACOBI, ilu = applied_by_launches(precond);  // ilu: ILU(0) or the Chebyshev polynomial
+    const bool  jacobi = precond == SPMV_PRECOND_JACOBI, by_launches = applied_by_launches(precond);  // (by_launches: the column of precond.hpp's table)
     // r, rhat, p, v, s, t (Jacobi: dinv, phat, shat; ILU(0): phat, shat) and the partial sums of two quantities
     double *r, *rhat, *p, *v, *sv, *t, *dinv = nullptr, *phat = nullptr, *shat = nullptr, *part;
     BicgScalars*   s = nullptr;
     SolveWorkspace ws(ctx, who);
     for (double** piece : {&r, &rhat, &p, &v, &sv, &t}) ws.piece(*piece, n);
-    if (pre) ws.piece(dinv, n);
-    if (pre || ilu) ws.piece(phat, n);
-    if (pre || ilu) ws.piece(shat, n);
+    if (jacobi) ws.piece(dinv, n);
+    if (jacobi || by_launches) ws.piece(phat, n);
+    if (jacobi || by_launches) ws.piece(shat, n);
     ws.piece(part, 2 * (size_t)kMaxGrid);
     SPMV_TRY(ws.allocate((void**)&s, sizeof(BicgScalars)));
     SPMV_TRY(setup_preconditioner(ctx, A, precond, dinv, who));
@@ -356,14 +356,14 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
     // the seven launches of an iteration (ILU(0): and the two applications phat = M^-1 p, shat = M^-1 s; in a quiet iteration they
     // run on the p and s that stand, which the update kernel then does not read)
     auto iteration = [&]() -> int {
-        if (ilu) SPMV_TRY(apply_preconditioner(ctx, A, precond, p, phat));
+        if (by_launches) SPMV_TRY(apply_preconditioner(ctx, A, precond, p, phat));
         SPMV_TRY(mat_apply_ex(ctx, A, phat, v, over));
         hipLaunchKernelGGL(bicg_dot_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)rhat, (const double*)v, &s->rhv, part, s);
-        if (pre)
+        if (jacobi)
             hipLaunchKernelGGL(bicg_half_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)r, (const double*)v, (const double*)dinv, sv, shat, s);
         else
             hipLaunchKernelGGL(bicg_half_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)r, (const double*)v, (const double*)dinv, sv, shat, s);
-        if (ilu) SPMV_TRY(apply_preconditioner(ctx, A, precond, sv, shat));
+        if (by_launches) SPMV_TRY(apply_preconditioner(ctx, A, precond, sv, shat));
         SPMV_TRY(mat_apply_ex(ctx, A, shat, t, over));
         hipLaunchKernelGGL(bicg_dot_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)t, (const double*)sv, &s->ts, part, s);
         if (wide_x)
@@ -372,7 +372,7 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
         else
             hipLaunchKernelGGL(bicg_update_kernel<false>, dim3(grid_x), dim3(kBlock), 0, st, n, (const double*)phat, (const double*)shat, (const double*)sv,
                                (const double*)t, (const double*)rhat, x, r, part, s);
-        if (pre)
+        if (jacobi)
             hipLaunchKernelGGL(bicg_direction_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, (const double*)r, (const double*)v, (const double*)dinv, p, phat,
                                (const BicgScalars*)s);
         else
@@ -384,18 +384,18 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
     auto        fetch = [&]() { return read_scalars(ctx, &h, s, sizeof(BicgScalars), who); };
     // s (and shat) are read by the second product of a quiet iteration that never wrote them
     SPMV_TRY(hip_step(hipMemsetAsync(sv, 0, sizeof(double) * (size_t)n, st), who, "clearing s"));
-    if (pre) SPMV_TRY(hip_step(hipMemsetAsync(shat, 0, sizeof(double) * (size_t)n, st), who, "clearing shat"));
+    if (jacobi) SPMV_TRY(hip_step(hipMemsetAsync(shat, 0, sizeof(double) * (size_t)n, st), who, "clearing shat"));
     SPMV_TRY(mat_apply_ex(ctx, A, x, v, over));  // v = A x0
 #define SPMV_BICG_INIT(WIDE, PRE)                                                                                                                  \
     hipLaunchKernelGGL((bicg_init_kernel<WIDE, PRE>), dim3(grid_b), dim3(kBlock), 0, st, n, b, (const double*)v, (const double*)dinv, r, rhat, p, phat, \
                        part, s)
     if (wide_b)
     {
-        if (pre) SPMV_BICG_INIT(true, true); else SPMV_BICG_INIT(true, false);
+        if (jacobi) SPMV_BICG_INIT(true, true); else SPMV_BICG_INIT(true, false);
     }
     else
     {
-        if (pre) SPMV_BICG_INIT(false, true); else SPMV_BICG_INIT(false, false);
+        if (jacobi) SPMV_BICG_INIT(false, true); else SPMV_BICG_INIT(false, false);
     }
 #undef SPMV_BICG_INIT
     SPMV_TRY(fetch());

@@ -438,7 +438,7 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
     if (n == 0) return SPMV_OK;
     const int   m  = restart;
     hipStream_t st = ctx->stream;
-    const bool  pre = precond == SPMV_PRECOND_JACOBI, ilu = applied_by_launches(precond);  // ilu: ILU(0) or the Chebyshev polynomial
+    const bool  jacobi = precond == SPMV_PRECOND_JACOBI, by_launches = applied_by_launches(precond);  // (by_launches: the column of precond.hpp's table)
     // the basis (m + 1 vectors, a padded vector apart), w, z (Jacobi, ILU(0)), dinv (Jacobi) and the partial sums of m + 2 quantities
     const size_t   sn = SolveWorkspace::padded((size_t)n);
     double *       V, *w, *z = nullptr, *dinv = nullptr, *part;
@@ -446,8 +446,8 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
     SolveWorkspace ws(ctx, who);
     ws.piece(V, (size_t)(m + 1) * sn);
     ws.piece(w, n);
-    if (pre || ilu) ws.piece(z, n);
-    if (pre) ws.piece(dinv, n);
+    if (jacobi || by_launches) ws.piece(z, n);
+    if (jacobi) ws.piece(dinv, n);
     ws.piece(part, (size_t)(m + 2) * (size_t)kMaxGrid);
     SPMV_TRY(ws.allocate((void**)&s, sizeof(GmresState)));
     SPMV_TRY(setup_preconditioner(ctx, A, precond, dinv, who));
@@ -458,7 +458,7 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
     apply_extra over;
     over.overwrite = true;
     auto normalise = [&]() {
-        if (pre)
+        if (jacobi)
             hipLaunchKernelGGL(gmres_normalise_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n, vs, V, (const double*)w, (const double*)dinv, z,
                                (const GmresState*)s);
         else
@@ -485,8 +485,8 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
     // quiet too).  last: no later column of this cycle reads v_{j+1}
     auto iteration = [&](int j, bool last) -> int {
         const double* vj = V + (size_t)j * sn;
-        if (ilu) SPMV_TRY(apply_preconditioner(ctx, A, precond, vj, z));
-        SPMV_TRY(mat_apply_ex(ctx, A, (pre || ilu) ? (const double*)z : vj, w, over));
+        if (by_launches) SPMV_TRY(apply_preconditioner(ctx, A, precond, vj, z));
+        SPMV_TRY(mat_apply_ex(ctx, A, (jacobi || by_launches) ? (const double*)z : vj, w, over));
         hipLaunchKernelGGL(gmres_dots_kernel, dim3(grid), dim3(kBlock), 0, st, n, vs, (const double*)V, (const double*)w, 1, part, s);
         hipLaunchKernelGGL(gmres_update_kernel<false>, dim3(grid), dim3(kBlock), 0, st, n, vs, (const double*)V, w, part, s);
         hipLaunchKernelGGL(gmres_dots_kernel, dim3(grid), dim3(kBlock), 0, st, n, vs, (const double*)V, (const double*)w, 0, part, s);
@@ -499,7 +499,7 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
         hipLaunchKernelGGL(gmres_backsolve_kernel, dim3(1), dim3(kWave), 0, st, s);
 #define SPMV_GMRES_XUPDATE(WIDE, MODE, GRID, OUT) \
     hipLaunchKernelGGL((gmres_xupdate_kernel<WIDE, MODE>), dim3(GRID), dim3(kBlock), 0, st, n, vs, (const double*)V, (const double*)dinv, OUT, (const GmresState*)s)
-        if (ilu)
+        if (by_launches)
         {
             SPMV_GMRES_XUPDATE(true, 2, grid, w);
             SPMV_TRY(apply_preconditioner(ctx, A, precond, w, z));
@@ -508,7 +508,7 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
             else
                 hipLaunchKernelGGL(gmres_xadd_kernel<false>, dim3(grid_x), dim3(kBlock), 0, st, n, (const double*)z, x);
         }
-        else if (pre)
+        else if (jacobi)
         {
             if (wide_x) SPMV_GMRES_XUPDATE(true, 1, grid_x, x); else SPMV_GMRES_XUPDATE(false, 1, grid_x, x);
         }
@@ -525,7 +525,7 @@ int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, in
     auto fetch = [&]() { return read_scalars(ctx, h_bytes, s, kGmresHeadBytes, who); };
     // the basis, w and z lie behind one another from V on; the product of a quiet iteration reads a basis vector or z that no launch
     // of the cycle wrote
-    SPMV_TRY(hip_step(hipMemsetAsync(V, 0, sizeof(double) * (size_t)(m + 2 + (pre || ilu ? 1 : 0)) * sn, st), who, "clearing the basis"));
+    SPMV_TRY(hip_step(hipMemsetAsync(V, 0, sizeof(double) * (size_t)(m + 2 + (jacobi || by_launches ? 1 : 0)) * sn, st), who, "clearing the basis"));
     SPMV_TRY(start_cycle(true));
     SPMV_TRY(fetch());
     const double bb = h->bb;

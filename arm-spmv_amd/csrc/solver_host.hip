@@ -1,5 +1,6 @@
 // solver_host.hip — the host side that the five solves share (solver_host.hpp): argument checks, the workspace, the preconditioner's
-// set-up and application.  One kernel: the inverse diagonal of a CSR handle, for Jacobi and for Chebyshev's scaling.
+// set-up and application through its row of the table (precond.hpp).  One kernel: the inverse diagonal of a CSR handle, for Jacobi
+// and for Chebyshev's scaling.
 #include "solver_host.hpp"
 
 namespace spmv
@@ -56,11 +57,23 @@ int check_limits(const char* who, int max_iter, double rel_tol)
     return SPMV_OK;
 }
 
+int check_vector_lengths(const char* who, const spmv_mat* A, const char* name_b, const spmv_vec* b, const char* name_x, const spmv_vec* x)
+{
+    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "%s: %s has %lld and %s %lld entries, the matrix %d rows", who, name_b, (long long)b->n, name_x,
+                 (long long)x->n, A->nrow);
+    return SPMV_OK;
+}
+
+int check_vector_pair(const char* who, const spmv_mat* A, const char* name_b, const spmv_vec* b, const char* name_x, const spmv_vec* x)
+{
+    SPMV_TRY(check_vector_lengths(who, A, name_b, b, name_x, x));
+    SPMV_REQUIRE(vectors_disjoint(b, x), "%s: %s and %s must not overlap", who, name_b, name_x);
+    return SPMV_OK;
+}
+
 int check_known_preconditioner(const char* who, int precond)
 {
-    SPMV_REQUIRE(precond == SPMV_PRECOND_NONE || precond == SPMV_PRECOND_JACOBI || precond == SPMV_PRECOND_SYMGS || precond == SPMV_PRECOND_ILU0 ||
-                     precond == SPMV_PRECOND_CHEBYSHEV || precond == SPMV_PRECOND_AMG || precond == SPMV_PRECOND_FSAI,
-                 "%s: unknown preconditioner %d", who, precond);
+    SPMV_REQUIRE(precond_row_of(precond), "%s: unknown preconditioner %d", who, precond);
     return SPMV_OK;
 }
 
@@ -69,12 +82,13 @@ int check_square_solve(const solver_rules& S, const spmv_ctx* ctx, const spmv_ma
 {
     SPMV_REQUIRE(ctx && A && b && x && iters && rel_resid, "%s: null argument", S.who);
     SPMV_REQUIRE(A->nrow == A->ncol, "%s: %s is %d x %d, not square", S.who, S.matrix, A->nrow, A->ncol);
-    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "%s: b has %lld and x %lld entries, the matrix %d rows", S.who, (long long)b->n,
-                 (long long)x->n, A->nrow);
     if (S.alias_only)
+    {
+        SPMV_TRY(check_vector_lengths(S.who, A, "b", b, "x", x));
         SPMV_REQUIRE(b->d != x->d || x->n == 0, "%s: b and x must not alias", S.who);
+    }
     else
-        SPMV_REQUIRE(vectors_disjoint(b, x), "%s: b and x must not overlap", S.who);
+        SPMV_TRY(check_vector_pair(S.who, A, "b", b, "x", x));
     SPMV_TRY(check_limits(S.who, max_iter, rel_tol));
     return check_known_preconditioner(S.who, precond);
 }
@@ -89,8 +103,7 @@ int check_refine(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, c
     SPMV_REQUIRE(A_lo->nrow == A->nrow && A_lo->ncol == A->ncol, "%s: A_lo is %d x %d, A is %d x %d: the shapes must match", who, A_lo->nrow, A_lo->ncol, A->nrow,
                  A->ncol);
     SPMV_REQUIRE(A->ctx == ctx && A_lo->ctx == ctx, "%s: %s belongs to another context", who, A->ctx != ctx ? "A" : "A_lo");
-    SPMV_REQUIRE(b->n == A->nrow && x->n == A->nrow, "%s: b has %lld and x %lld entries, the matrix %d rows", who, (long long)b->n, (long long)x->n, A->nrow);
-    SPMV_REQUIRE(vectors_disjoint(b, x), "%s: b and x must not overlap", who);
+    SPMV_TRY(check_vector_pair(who, A, "b", b, "x", x));
     SPMV_REQUIRE(max_outer >= 0 && inner_max_iter >= 0 && inner_tol >= 0.0 && rel_tol >= 0.0, "%s: max_outer=%d inner_max_iter=%d inner_tol=%g rel_tol=%g", who,
                  max_outer, inner_max_iter, inner_tol, rel_tol);
     SPMV_REQUIRE(solver == SPMV_REFINE_CG || solver == SPMV_REFINE_BICGSTAB, "%s: unknown solver %d (0: CG, 1: BiCGSTAB)", who, solver);
@@ -99,28 +112,10 @@ int check_refine(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, c
 
 int check_preconditioner(const solver_rules& S, const spmv_mat* A, int precond)
 {
-    if (precond == SPMV_PRECOND_SYMGS && S.symgs_not_built_for)
-        SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the symmetric Gauss-Seidel preconditioner is not built for %s", S.who, S.symgs_not_built_for);
-    if (precond == SPMV_PRECOND_ILU0)
-    {
-        if (S.ilu0_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the ILU(0) preconditioner is not built for %s", S.who, S.ilu0_not_built_for);
-        return ilu0_check_handle(A, S.who);
-    }
-    if (precond == SPMV_PRECOND_CHEBYSHEV)
-    {
-        if (S.cheby_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the Chebyshev preconditioner is not built for %s", S.who, S.cheby_not_built_for);
-        return cheby_check_handle(A, S.who);  // (whether the handle is set up, and what its own set-up needs, is looked at on the device's side)
-    }
-    if (precond == SPMV_PRECOND_AMG)
-    {
-        if (S.amg_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the AMG preconditioner is not built for %s", S.who, S.amg_not_built_for);
-        return amg_check_handle(A, S.who);
-    }
-    if (precond == SPMV_PRECOND_FSAI)
-    {
-        if (S.fsai_not_built_for) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the FSAI preconditioner is not built for %s", S.who, S.fsai_not_built_for);
-        return fsai_check_handle(A, S.who);
-    }
+    SPMV_TRY(check_known_preconditioner(S.who, precond));
+    const precond_row& P = kPreconds[precond];
+    if (S.refused & (1u << precond)) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "%s: the %s preconditioner is not built for %s", S.who, P.name, S.not_built_for);
+    if (P.check_handle) return P.check_handle(A, S.who);
     if (precond != SPMV_PRECOND_JACOBI) return SPMV_OK;
     // Jacobi reads the diagonal from the handle's own CSR arrays (the plain solve needs the product alone and takes a handle that
     // released them)
@@ -189,30 +184,15 @@ SolveWorkspace::~SolveWorkspace()
 // ---- the preconditioner --------------------------------------------------------------------------------------------------------
 int setup_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, double* dinv, const char* who)
 {
-    switch (precond)
-    {
-        case SPMV_PRECOND_JACOBI: return jacobi_inverse_diagonal(ctx, A, dinv, who);
-        case SPMV_PRECOND_SYMGS: return symgs_setup(const_cast<spmv_mat*>(A));
-        case SPMV_PRECOND_ILU0: return ilu0_setup(const_cast<spmv_mat*>(A));
-        case SPMV_PRECOND_CHEBYSHEV:  // a handle that was set up explicitly is used as it stands
-            return A->cheby ? SPMV_OK : cheby_setup(ctx, const_cast<spmv_mat*>(A), A->cheby_degree, /*scaled=*/1, 0.0, 0.0);
-        case SPMV_PRECOND_AMG:  // likewise; 0: every default
-            return A->amg ? SPMV_OK : amg_setup(ctx, const_cast<spmv_mat*>(A), 0, 0, 0, 0.0, 0.0);
-        case SPMV_PRECOND_FSAI:  // likewise; 0: the handle's "fsai_level"
-            return A->fsai ? SPMV_OK : fsai_setup(ctx, const_cast<spmv_mat*>(A), 0);
-        default: return SPMV_OK;
-    }
+    if (precond == SPMV_PRECOND_JACOBI) return jacobi_inverse_diagonal(ctx, A, dinv, who);
+    const precond_row* P = precond_row_of(precond);
+    return P && P->ensure ? P->ensure(ctx, const_cast<spmv_mat*>(A)) : SPMV_OK;
 }
 
 int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const double* r, double* z)
 {
-    switch (precond)
-    {
-        case SPMV_PRECOND_ILU0: return ilu0_apply(ctx, A, r, z);
-        case SPMV_PRECOND_CHEBYSHEV: return cheby_apply(ctx, A, r, z);
-        case SPMV_PRECOND_AMG: return amg_apply(ctx, A, r, z);
-        case SPMV_PRECOND_FSAI: return fsai_apply(ctx, A, r, z);
-        default: return symgs_sweep(ctx, A, r, z, true);
-    }
+    const precond_row* P = precond_row_of(precond);
+    if (!P || !P->apply) SPMV_FAIL(SPMV_ERR_INVALID, "apply_preconditioner: preconditioner %d is not applied by launches", precond);
+    return P->apply(ctx, A, r, z);
 }
 }  // namespace spmv

@@ -1,34 +1,21 @@
 // solver_host.hpp — the host side that the five solves share (spmv_cg, spmv_cg_multi, spmv_cgls, spmv_bicgstab, spmv_gmres): the
-// argument checks of their ABI entries, the owner of a solve's device memory, the preconditioner's set-up and application, and the
-// small questions every driver asks about a vector (may it go in 16-byte accesses, how many workgroups).  Defined in
-// solver_host.hip; the device side of what the solvers share is solver_common.hpp.
+// argument checks of their ABI entries, the owner of a solve's device memory, the preconditioner's set-up and application (a
+// look-up in precond.hpp's table and a call), and the small questions every driver asks about a vector (may it go in 16-byte
+// accesses, how many workgroups).  Defined in solver_host.hip; the device side of what the solvers share is solver_common.hpp.
 #pragma once
 
 #include "common.hpp"
+#include "precond.hpp"
 
 namespace spmv
 {
 // ---- argument checks: on the host, before the device is touched (abi.hip) ------------------------------------------------------
-// What a solver's refusals depend on.  Every message starts with `who`.
-struct solver_rules
-{
-    const char* who;
-    const char* matrix;               // the noun of "is %d x %d, not square": "the matrix" or "the matrix (shard)"
-    bool        alias_only;           // b and x are refused where they start at the same address (spmv_cg), not where their ranges overlap
-    const char* symgs_not_built_for;  // nullptr: symmetric Gauss-Seidel is built; else the end of the refusal
-    const char* ilu0_not_built_for;   // nullptr: ILU(0) is built (ilu0_check_handle decides on the handle); else the end of the refusal
-    enum
-    {
-        jacobi_arrays_elsewhere,    // the entry checks the handle's arrays itself, for its product
-        jacobi_arrays_unsupported,  // arrays gone: UNSUPPORTED, as a handle that is not CSR (spmv_cg)
-        jacobi_arrays_invalid       // arrays gone: INVALID, "gave up its CSR arrays"
-    } jacobi_arrays;
-    const char* cheby_not_built_for;  // nullptr: the Chebyshev polynomial is built (cheby_check_handle decides on the handle); else the end of the refusal
-    const char* amg_not_built_for;    // nullptr: AMG is built (amg_check_handle decides on the handle); else the end of the refusal
-    const char* fsai_not_built_for;   // nullptr: FSAI is built (fsai_check_handle decides on the handle); else the end of the refusal
-};
-
+// (what a solver's refusals depend on: solver_rules, precond.hpp)
 bool vectors_disjoint(const spmv_vec* b, const spmv_vec* x);  // an empty vector overlaps nothing
+// two vectors of as many entries as A has rows: "<who>: <name_b> has %lld and <name_x> %lld entries, the matrix %d rows" ...
+int check_vector_lengths(const char* who, const spmv_mat* A, const char* name_b, const spmv_vec* b, const char* name_x, const spmv_vec* x);
+// ... whose ranges are apart: "<who>: <name_b> and <name_x> must not overlap"
+int check_vector_pair(const char* who, const spmv_mat* A, const char* name_b, const spmv_vec* b, const char* name_x, const spmv_vec* x);
 int  check_limits(const char* who, int max_iter, double rel_tol);
 int  check_known_preconditioner(const char* who, int precond);
 // the square single-vector solvers: null arguments, square, the lengths of b and x, alias / overlap, limits, a known preconditioner
@@ -39,7 +26,7 @@ int check_square_solve(const solver_rules& S, const spmv_ctx* ctx, const spmv_ma
 int check_refine(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, const spmv_vec* b, const spmv_vec* x, int solver, int precond,
                  int max_outer, int inner_max_iter, double inner_tol, double rel_tol, const int32_t* outer, const int32_t* inner_total,
                  const double* rel_resid);
-// a known preconditioner that this solver does not take, or not on this handle
+// a known preconditioner that this solver does not take (S.refused), or not on this handle (the row's check_handle; Jacobi: S.jacobi_arrays)
 int check_preconditioner(const solver_rules& S, const spmv_mat* A, int precond);
 
 // ---- errors carry text ---------------------------------------------------------------------------------------------------------
@@ -79,20 +66,19 @@ private:
 };
 
 // ---- the preconditioner --------------------------------------------------------------------------------------------------------
-// Before a solve's first launch: the state that stays in the handle (symgs_setup, ilu0_setup: built once; cheby_setup and amg_setup
-// and fsai_setup with the defaults unless the handle was set up before), or dinv[i] = 1 / a_ii of
-// a CSR handle for Jacobi (synchronous; a zero or missing diagonal entry is `who`'s error).  SPMV_PRECOND_NONE: nothing.
+// Before a solve's first launch: the state that stays in the handle (the row's ensure), or dinv[i] = 1 / a_ii of a CSR handle for
+// Jacobi (synchronous; a zero or missing diagonal entry is `who`'s error).  SPMV_PRECOND_NONE: nothing.
 int setup_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, double* dinv, const char* who);
 // dinv[i] = 1 / a_ii of a CSR handle (duplicates summed; synchronous); a zero or missing entry: INVALID, "<who>: ... (<what>)"
 int jacobi_inverse_diagonal(spmv_ctx* ctx, const spmv_mat* A, double* dinv, const char* who, const char* what = "Jacobi preconditioner");
-// a preconditioner that is a launch sequence of its own (a work vector z between the product and the updates), not a diagonal
+// a preconditioner that is a launch sequence of its own (a work vector z between the product and the updates), not a diagonal: the
+// table's by_launches column
 inline bool applied_by_launches(int precond)
 {
-    return precond == SPMV_PRECOND_ILU0 || precond == SPMV_PRECOND_CHEBYSHEV || precond == SPMV_PRECOND_AMG || precond == SPMV_PRECOND_FSAI;
+    const precond_row* P = precond_row_of(precond);
+    return P && P->by_launches;
 }
-// z = M^-1 r for the preconditioners that are launch sequences of their own: the two triangular solves of ILU(0) (ilu0.hip), one
-// symmetric Gauss-Seidel sweep from z = 0 (symgs.hip), the Chebyshev polynomial in the handle (chebyshev.hip), one AMG cycle (amg.hip), or
-// the two products of FSAI (fsai.hip)
+// z = M^-1 r: the row's apply (symmetric Gauss-Seidel: one sweep from z = 0).  A preconditioner without one: INVALID
 int apply_preconditioner(spmv_ctx* ctx, const spmv_mat* A, int precond, const double* r, double* z);
 
 // ---- width and grids -----------------------------------------------------------------------------------------------------------

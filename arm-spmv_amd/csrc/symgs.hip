@@ -367,7 +367,7 @@ int symgs_sequence(const spmv_mat* m, int32_t* out)
     return SPMV_OK;
 }
 
-int symgs_info(const spmv_mat* m, const char* what, int64_t* value)
+bool symgs_get_param(const spmv_mat* m, const char* what, int64_t* value)
 {
     const symgs_plan* g = m->gs;
     if (!strcmp(what, "symgs_levels_forward"))
@@ -385,7 +385,19 @@ int symgs_info(const spmv_mat* m, const char* what, int64_t* value)
     else if (!strcmp(what, "symgs_order"))
         *value = m->gs_order != 0 ? 1 : 0;
     else
-        return SPMV_ERR_INVALID;
-    return SPMV_OK;
+        return false;
+    return true;
+}
+
+// "symgs_order": 1 multicolour, 0 the matrix's own row order; takes effect at the next set-up / sweep
+bool symgs_set_param(spmv_mat* m, const char* name, int64_t value, int* rc)
+{
+    if (strcmp(name, "symgs_order")) return false;
+    *rc = value == 0 || value == 1 ? SPMV_OK : SPMV_ERR_INVALID;
+    if (*rc == SPMV_OK)
+        m->gs_order = (int32_t)value;
+    else
+        set_error("symgs_order: 0 (row order) or 1 (multicolour), got %lld", (long long)value);
+    return true;
 }
 }  // namespace spmv
