@@ -110,6 +110,7 @@ SIGNATURES = {
     "spmv_cgls": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_double, C.POINTER(C.c_int32), _f64p, _f64p]),
     "spmv_bicgstab": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_gmres": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
+    "spmv_minres": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
     "spmv_block_gram": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.c_int32, _vp, C.c_int64, _f64p]),
     "spmv_block_combine": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.c_int32, _f64p, _vp, C.c_int64]),
     "spmv_lobpcg": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_double, C.c_int32, _f64p, _f64p, C.POINTER(C.c_int32)]),
@@ -700,6 +701,19 @@ class Context:
         (GMRES(1) on a rotation) is no error.  Stops at ||r|| <= rel_tol * ||b||; returns (iterations, ||r|| / ||b||)"""
         it, res = C.c_int32(0), C.c_double(0.0)
         _check(self._lib.spmv_gmres(self.h, A.h, b.h, x.h, restart, max_iter, rel_tol, check_every, precond, C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def minres(self, A: "Matrix", b: "Vector", x: "Vector", shift: float = 0.0, P: "Matrix | None" = None, max_iter: int = 1000,
+               rel_tol: float = 1e-8, check_every: int = 1, precond: int = 0):
+        """(A - shift I) x = b for a square symmetric A that need not be positive definite, by preconditioned MINRES on the device, from
+        the x passed in: any format, one forward product and one preconditioner application per iteration, no breakdown, a residual that
+        never grows.  P: the handle the preconditioner is built from and kept in (None: A) - it must be symmetric positive definite, which
+        one built from an indefinite A is not.  precond: PRECOND_NONE, PRECOND_JACOBI, PRECOND_CHEBYSHEV, PRECOND_AMG or PRECOND_FSAI.
+        Stops at phibar <= rel_tol * sqrt(b.M^-1 b), phibar the residual's M^-1 norm (the 2-norm without a preconditioner); returns
+        (iterations, phibar / sqrt(b.M^-1 b))"""
+        it, res = C.c_int32(0), C.c_double(0.0)
+        _check(self._lib.spmv_minres(self.h, A.h, P.h if P is not None else None, b.h, x.h, shift, max_iter, rel_tol, check_every, precond,
+                                     C.byref(it), C.byref(res)))
         return it.value, res.value
 
     def refine(self, A: "Matrix", A_lo: "Matrix", b: "Vector", x: "Vector", solver: int = REFINE_CG, precond: int = PRECOND_NONE, max_outer: int = 20,

@@ -1418,7 +1418,7 @@ int spmv_apply_dot(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* x, spmv_vec
     return SPMV_OK;
 }
 
-// The five solves.  Every check is made before the device is touched, so that they hold (and are tested) on a machine without one;
+// The solves.  Every check is made before the device is touched, so that they hold (and are tested) on a machine without one;
 // the checks they share are solver_host.hpp's, and what each solver's refusals depend on (k*Rules) stands beside the preconditioners'
 // table (precond.hip).
 int spmv_cg(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t max_iter, double rel_tol,
@@ -1494,6 +1494,20 @@ int spmv_gmres(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x,
     if (A->nrow == 0) return SPMV_OK;
     SPMV_TRY(use_device(ctx));
     return gmres_solve(ctx, A, b->d, x->d, restart == 0 ? 30 : restart, max_iter, rel_tol, check_every, precond, iters, rel_resid);
+}
+
+// symmetric indefinite systems with a shift over one forward product per iteration (solver_minres.hip)
+int spmv_minres(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* P, const spmv_vec* b, spmv_vec* x, double shift, int32_t max_iter, double rel_tol,
+                int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid)
+{
+    SPMV_TRY(check_square_solve(kMinresRules, ctx, A, b, x, max_iter, rel_tol, precond, iters, rel_resid));
+    SPMV_TRY(check_shift_and_precond_handle(kMinresRules, ctx, A, P, shift, precond));
+    SPMV_TRY(check_preconditioner(kMinresRules, P ? P : A, precond));
+    *iters     = 0;
+    *rel_resid = 0.0;
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return minres_solve(ctx, A, P, b->d, x->d, shift, max_iter, rel_tol, check_every, precond, iters, rel_resid);
 }
 
 // iterative refinement: the residual with A in fp64, the correction from spmv_cg or spmv_bicgstab on A_lo (solver_refine.hip)

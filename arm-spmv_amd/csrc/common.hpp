@@ -496,7 +496,7 @@ int  mat_apply_ex(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, 
 int  csr_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y, const apply_extra& ex = apply_extra{});
 bool writes_row_sums_in_one_launch(const spmv_mat* A);  // the product can store sum_i instead of y_i + sum_i at no extra launch
 bool adds_into_y_with_atomics(const spmv_mat* A);       // global_atomic_add_f64 on y, by the kernel (of the handle or its copies) that runs
-// The five solves' drivers.  Each is entered from its ABI entry (abi.hip) behind the argument checks and use_device, zeroes its
+// The solves' drivers.  Each is entered from its ABI entry (abi.hip) behind the argument checks and use_device, zeroes its
 // outputs, returns at an empty system, and shares its host side - the workspace that owns its device memory, the preconditioner's
 // set-up and application, the looks at its scalars - with the others through solver_host.hpp.
 // Which driver takes which preconditioner is written down once, beside the preconditioners' table (precond.hip: kPreconds, k*Rules).
@@ -517,6 +517,10 @@ int bicgstab_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x,
 // (restart: 1 .. 64)
 int gmres_solve(spmv_ctx* ctx, const spmv_mat* A, const double* b, double* x, int restart, int max_iter, double rel_tol, int check_every,
                 int precond, int* iters, double* rel_resid);
+// solver_minres.hip: preconditioned MINRES for (A - shift I) x = b, A square and symmetric, over one forward product of any handle per
+// iteration; the preconditioner is P's (null: A's)
+int minres_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* P, const double* b, double* x, double shift, int max_iter, double rel_tol,
+                 int check_every, int precond, int* iters, double* rel_resid);
 // solver_lobpcg.hip: LOBPCG for the k smallest (largest) eigenpairs of a symmetric A over one forward product per active column and
 // iteration (k: 1 .. 16); X: n x k, column-major, ld = n
 int lobpcg_solve(spmv_ctx* ctx, const spmv_mat* A, int k, int nev, bool largest, double* X, int max_iter, double tol, int precond, double* theta,

@@ -44,6 +44,8 @@ const solver_rules kCgMultiRules  = {"spmv_cg_multi", "the matrix",         fals
 const solver_rules kBicgstabRules = {"spmv_bicgstab", "the matrix (shard)", false,      bit(SPMV_PRECOND_SYMGS), "this solver", solver_rules::jacobi_arrays_invalid};
 const solver_rules kGmresRules    = {"spmv_gmres",    "the matrix (shard)", false,      bit(SPMV_PRECOND_SYMGS), "this solver", solver_rules::jacobi_arrays_invalid};
 const solver_rules kLobpcgRules   = {"spmv_lobpcg",   "the matrix (shard)", false,      bit(SPMV_PRECOND_SYMGS), "this solver", solver_rules::jacobi_arrays_invalid};
+// (spmv_minres needs a symmetric positive definite M: the sweep and the incomplete factors are neither symmetric nor sure to be definite)
+const solver_rules kMinresRules   = {"spmv_minres",   "the matrix (shard)", false,      bit(SPMV_PRECOND_SYMGS) | bit(SPMV_PRECOND_ILU0), "this solver", solver_rules::jacobi_arrays_invalid};
 
 // ---- the pieces of the units' handle checks (on the host; `noun` is the unit's name in its messages) -----------------------------
 int check_whole_square(const spmv_mat* m, const char* who, const char* noun)

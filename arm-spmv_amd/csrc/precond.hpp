@@ -28,7 +28,7 @@ extern const precond_row kPreconds[kPrecondCount];  // in id order
 
 inline const precond_row* precond_row_of(int id) { return id >= 0 && id < kPrecondCount ? &kPreconds[id] : nullptr; }
 
-// What a solver's refusals depend on.  Every message starts with `who`.  The rows of the five solvers stand under the table.
+// What a solver's refusals depend on.  Every message starts with `who`.  The rows of the solvers stand under the table.
 struct solver_rules
 {
     const char* who;
@@ -43,5 +43,5 @@ struct solver_rules
         jacobi_arrays_invalid       // arrays gone: INVALID, "gave up its CSR arrays"
     } jacobi_arrays;
 };
-extern const solver_rules kCgRules, kCgMultiRules, kBicgstabRules, kGmresRules, kLobpcgRules;
+extern const solver_rules kCgRules, kCgMultiRules, kBicgstabRules, kGmresRules, kLobpcgRules, kMinresRules;
 }  // namespace spmv

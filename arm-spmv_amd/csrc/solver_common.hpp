@@ -1,5 +1,6 @@
-// solver_common.hpp — the device side of what the five solvers share (spmv_cg in solver.hip, spmv_cg_multi in solver_multi.hip,
-// spmv_cgls in solver_cgls.hip, spmv_bicgstab in solver_bicgstab.hip, spmv_gmres in solver_gmres.hip): the sums over a workgroup
+// solver_common.hpp — the device side of what the solvers share (spmv_cg in solver.hip, spmv_cg_multi in solver_multi.hip,
+// spmv_cgls in solver_cgls.hip, spmv_bicgstab in solver_bicgstab.hip, spmv_gmres in solver_gmres.hip, spmv_minres in
+// solver_minres.hip): the sums over a workgroup
 // and the deterministic sum over a grid (the last-ticket pattern).  The host side they share is solver_host.hpp.
 #pragma once
 

@@ -1,4 +1,4 @@
-// solver_host.hip — the host side that the five solves share (solver_host.hpp): argument checks, the workspace, the preconditioner's
+// solver_host.hip — the host side that the solves share (solver_host.hpp): argument checks, the workspace, the preconditioner's
 // set-up and application through its row of the table (precond.hpp).  One kernel: the inverse diagonal of a CSR handle, for Jacobi
 // and for Chebyshev's scaling.
 #include "solver_host.hpp"
@@ -91,6 +91,17 @@ int check_square_solve(const solver_rules& S, const spmv_ctx* ctx, const spmv_ma
         SPMV_TRY(check_vector_pair(S.who, A, "b", b, "x", x));
     SPMV_TRY(check_limits(S.who, max_iter, rel_tol));
     return check_known_preconditioner(S.who, precond);
+}
+
+int check_shift_and_precond_handle(const solver_rules& S, const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* P, double shift, int precond)
+{
+    SPMV_REQUIRE(std::isfinite(shift), "%s: shift=%g, must be finite", S.who, shift);
+    if (!P) return SPMV_OK;
+    SPMV_REQUIRE(precond != SPMV_PRECOND_NONE, "%s: a preconditioner's handle P was given with SPMV_PRECOND_NONE: name the preconditioner, or pass P = NULL", S.who);
+    SPMV_REQUIRE(P->nrow == A->nrow && P->ncol == A->nrow, "%s: P is %d x %d, A is %d x %d: the preconditioner's handle must be square and of A's size", S.who,
+                 P->nrow, P->ncol, A->nrow, A->ncol);
+    SPMV_REQUIRE(P->ctx == ctx, "%s: P belongs to another context", S.who);
+    return SPMV_OK;
 }
 
 int check_refine(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, const spmv_vec* b, const spmv_vec* x, int solver, int precond,

@@ -1,4 +1,4 @@
-// solver_host.hpp — the host side that the five solves share (spmv_cg, spmv_cg_multi, spmv_cgls, spmv_bicgstab, spmv_gmres): the
+// solver_host.hpp — the host side that the solves share (spmv_cg, spmv_cg_multi, spmv_cgls, spmv_bicgstab, spmv_gmres, spmv_minres): the
 // argument checks of their ABI entries, the owner of a solve's device memory, the preconditioner's set-up and application (a
 // look-up in precond.hpp's table and a call), and the small questions every driver asks about a vector (may it go in 16-byte
 // accesses, how many workgroups).  Defined in solver_host.hip; the device side of what the solvers share is solver_common.hpp.
@@ -21,6 +21,9 @@ int  check_known_preconditioner(const char* who, int precond);
 // the square single-vector solvers: null arguments, square, the lengths of b and x, alias / overlap, limits, a known preconditioner
 int check_square_solve(const solver_rules& S, const spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, const spmv_vec* x, int max_iter,
                        double rel_tol, int precond, const int32_t* iters, const double* rel_resid);
+// beside it for spmv_minres: a finite shift, and a preconditioner's own handle P (null: A) - square, of A's size, in A's context, and
+// not given where precond is SPMV_PRECOND_NONE
+int check_shift_and_precond_handle(const solver_rules& S, const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* P, double shift, int precond);
 // spmv_refine: null arguments, A square, A_lo of A's shape and context, the lengths of b and x, overlap, the four limits, a known inner
 // solver and preconditioner
 int check_refine(const spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* A_lo, const spmv_vec* b, const spmv_vec* x, int solver, int precond,

@@ -88,6 +88,22 @@ class SparseOperator:
         self.last_solve = run(self.A, self.ctx.wrap_vector(b.detach()), self.ctx.wrap_vector(x), **kw)
         return x
 
+    def solve_symmetric(self, b: torch.Tensor, x0: torch.Tensor | None = None, shift: float = 0.0, M: "capi.Matrix | None" = None, **kw) -> torch.Tensor:
+        """x with (A - shift I) x = b for a square symmetric A that need not be positive definite, from x0 (default 0), into a fresh
+        tensor, by capi.Context.minres; M: the handle the preconditioner is built from (None: A); kw: max_iter, rel_tol, check_every,
+        precond.  (iterations, residual) of the solve are left in self.last_solve.  No autograd through the solve"""
+        nrow, ncol = self.shape
+        if nrow != ncol:
+            raise ValueError(f"solve_symmetric: the operator is {nrow} x {ncol}, not square (lstsq takes any shape)")
+        self._check(b, nrow, "solve_symmetric")
+        if x0 is None:
+            x = torch.zeros(ncol, dtype=torch.float64, device=self.device)
+        else:
+            self._check(x0, ncol, "solve_symmetric x0")
+            x = x0.detach().clone()
+        self.last_solve = self.ctx.minres(self.A, self.ctx.wrap_vector(b.detach()), self.ctx.wrap_vector(x), shift=shift, P=M, **kw)
+        return x
+
 class _SpMV(torch.autograd.Function):
     @staticmethod
     def forward(fctx, op: SparseOperator, x: torch.Tensor) -> torch.Tensor:

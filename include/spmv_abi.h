@@ -649,6 +649,49 @@ int spmv_bicgstab(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec*
  *   the size in the message. */
 int spmv_gmres(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* b, spmv_vec* x, int32_t restart, int32_t max_iter, double rel_tol,
                int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
+/* spmv_minres: (A - shift I) x = b for a square SYMMETRIC A that need not be positive definite, by Paige and Saunders' preconditioned
+ *   MINRES, starting from the x passed in (solver_minres.hip).  b and x have nrow entries.  A is any handle
+ *   spmv_bicgstab takes: every format, uploaded, wrapped, or a shard that holds a square matrix; it is meant to be symmetric and nothing
+ *   checks that.  Synchronous.  One forward product through the handle's own kernel and one preconditioner application per iteration,
+ *   a three-term recurrence, no breakdown on a symmetric A, and a residual norm that never grows.  No transposed state is built, and the
+ *   handle's kernel, copies, device_bytes and plan stay as they were.  The shift is applied behind the product, for every format: there
+ *   is no handle of A - shift I.  Use: saddle-point systems, A - sigma I with sigma inside the spectrum, singular consistent systems.
+ *   P: the handle the preconditioner `precond` is built from and kept in; NULL means A.  M must be symmetric positive definite, and one
+ *   built from an indefinite A is not: pass blockdiag(K, I) for a saddle point, the unshifted operator for A - sigma I.  P is square, of
+ *   A's size and in A's context; P given with SPMV_PRECOND_NONE is SPMV_ERR_INVALID.
+ *   Recurrence:  r1 = b - (A - shift I) x;  y = M^-1 r1;  beta1 = sqrt(r1.y);  r2 = r1;  beta = beta1;  oldb = 0;  dbar = epsln = 0;
+ *   phibar = beta1;  cs = -1;  sn = 0;  w = w2 = 0;  then per iteration  v = y / beta;  y = A v - shift v;  from the second one on
+ *   y -= (beta / oldb) r1;  alfa = v.y;  y -= (alfa / beta) r2;  r1 = r2;  r2 = y;  y = M^-1 r2;  oldb = beta;  beta = sqrt(r2.y);
+ *   oldeps = epsln;  delta = cs dbar + sn alfa;  gbar = sn dbar - cs alfa;  epsln = sn beta;  dbar = -cs beta;
+ *   gamma = sqrt(gbar^2 + beta^2);  cs = gbar / gamma;  sn = beta / gamma;  phi = cs phibar;  phibar = sn phibar;  w1 = w2;  w2 = w;
+ *   w = (v - oldeps w1 - delta w2) / gamma;  x += phi w.  phibar is ||r_k|| in the M^-1 norm (the 2-norm without a preconditioner).
+ *   precond: SPMV_PRECOND_NONE, SPMV_PRECOND_JACOBI (the diagonal of P, a CSR handle with its arrays; a zero or missing entry:
+ *   SPMV_ERR_INVALID, and so is a negative one, "the Jacobi preconditioner is not positive definite", at the set-up),
+ *   SPMV_PRECOND_CHEBYSHEV, SPMV_PRECOND_AMG and SPMV_PRECOND_FSAI on the handles those take.  SPMV_PRECOND_SYMGS and SPMV_PRECOND_ILU0:
+ *   SPMV_ERR_UNSUPPORTED (neither is a symmetric positive definite M).
+ *   Four launches per iteration without a preconditioner and with Jacobi (the product; y and alfa; r2, r2.y and the rotation; w, x and
+ *   the next v); a preconditioner applied by launches adds its own sequence and one dot kernel.  Every scalar stays on the device; the
+ *   host reads phibar, the iteration count and a status word every check_every iterations (>= 1) and after the last one.
+ *   Stopping: phibar <= rel_tol * beta_b at a look, beta_b = sqrt(b.M^-1 b) (||b|| without a preconditioner; one more application at
+ *   the set-up, and no dependence on x0), or max_iter iterations.  *iters = iterations run, *rel_resid = phibar / beta_b at the last
+ *   look.  max_iter = k with rel_tol = 0 runs exactly k iterations.  b = 0: *iters = 0, *rel_resid = 0, x untouched.  A start within the
+ *   tolerance, or max_iter = 0: no iteration, *rel_resid is that of x0.  An iteration that starts with phibar at or below the floor
+ *   1e-14 beta_b passes quietly (its kernels write nothing), and the host ends the solve at its next look; beta = 0 - the Krylov space
+ *   is exhausted and the iterate exact - gives phibar = 0 and ends the solve with SPMV_OK.
+ *   SPMV_ERR_INVALID through the status word, naming the quantity and "at or before iteration k": r.M^-1 r below zero beyond rounding,
+ *   that is below -(4 * 1e-14 beta_b)^2, in the start or in an iteration - "preconditioner is not positive definite (r.M^-1 r = ...)"
+ *   (between that and zero it counts as 0); a non-finite b.b, b.M^-1 b, beta1, alfa, beta or phibar.  The kernel that sees it leaves
+ *   x alone, so x holds an iterate of the recurrence.
+ *   Refused before any device use with SPMV_ERR_INVALID: null ctx, A, b, x, iters or rel_resid, nrow != ncol, b or x with other than
+ *   nrow entries, b and x overlapping, max_iter < 0, rel_tol < 0, a shift that is not finite, an unknown precond, a P of another size
+ *   or context, P with SPMV_PRECOND_NONE, Jacobi on a CSR handle without its arrays.  nrow = 0: SPMV_OK, *iters = 0, nothing launched.
+ *   Deterministic dot products (per-workgroup partial sums added in a fixed order by the workgroup that finishes last): a solve is
+ *   exactly as reproducible as the product its handle runs.  x and b need only be 8-byte aligned; where they are 16-byte aligned the
+ *   vector kernels use 16-byte accesses on them.
+ *   Device memory: six work vectors of nrow doubles (a preconditioner: seven, Jacobi: eight), the partial sums of three quantities
+ *   and a small scalar block for the duration of the call, released on every path. */
+int spmv_minres(spmv_ctx* ctx, const spmv_mat* A, const spmv_mat* P, const spmv_vec* b, spmv_vec* x, double shift, int32_t max_iter,
+                double rel_tol, int32_t check_every, int32_t precond, int32_t* iters, double* rel_resid);
 /* Iterative refinement (solver_refine.hip): fp64 answers from a solver that runs on a cheaper handle.  A (any square
  *   handle) defines the system; A_lo (any handle of the same shape in the same context - a SPMV_FMT_CSR_F32 copy of A is the intended
  *   use; A_lo == A is allowed) is what the inner solver multiplies by.  From the x passed in, per outer step:
