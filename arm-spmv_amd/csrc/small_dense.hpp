@@ -138,6 +138,29 @@ inline bool cholesky_lower(int n, double* G, double* min_pivot)
     return true;
 }
 
+// The first j whose pivot - cholesky_lower's, by the same sums - is below `threshold` or not positive and finite; -1: there is none
+// (or n is out of range).  G is not written.  On a Gram matrix with unit diagonal: the first column that depends on those before it.
+inline int cholesky_first_pivot_below(int n, const double* G, double threshold)
+{
+    if (n < 1 || n > kMaxOrder) return -1;
+    std::vector<double> L(G, G + (size_t)n * n);
+    for (int j = 0; j < n; ++j)
+    {
+        double d = L[(size_t)j * n + j];
+        for (int k = 0; k < j; ++k) d = std::fma(-L[(size_t)j * n + k], L[(size_t)j * n + k], d);
+        if (!(d > 0.0) || !std::isfinite(d) || d < threshold) return j;
+        const double ljj    = std::sqrt(d);
+        L[(size_t)j * n + j] = ljj;
+        for (int i = j + 1; i < n; ++i)
+        {
+            double t = L[(size_t)i * n + j];
+            for (int k = 0; k < j; ++k) t = std::fma(-L[(size_t)i * n + k], L[(size_t)j * n + k], t);
+            L[(size_t)i * n + j] = t / ljj;
+        }
+    }
+    return -1;
+}
+
 // Li = L^-1 of a lower triangle with a non-zero diagonal (column by column, forward substitution)
 inline void tri_inverse_lower(int n, const double* L, double* Li)
 {

@@ -23,7 +23,8 @@
 //   iteration  1  R = AX - X diag(theta), ||R_j||^2: lobpcg_resid_kernel, one launch, last-ticket sums
 //              2  the host looks: active = {j: resid_j > tol}; none among the first nev, or max_iter reached: stop
 //              3  W_c = M^-1 R_j for the active j;  twice: H = X^T W, W <- W - X H (a combine of [X P W] with the rows (-H; 0; I));
-//                 orthonormalise W (kLobpcgRankPivot; rank loss: INVALID, the last iterate is returned);  AW = A W
+//                 orthonormalise W (kLobpcgRankPivot; rank loss: the first column that depends on those before it is left out of this
+//                 iteration - no W, no P from it -, and so on; none left: INVALID, the last iterate is returned);  AW = A W
 //              4  P (if any): orthonormalise P, AP alike; rank loss drops P for this iteration
 //              5  GB = S^T S, GA = S^T AS (symmetrised on the host), read together
 //              6  GA c = theta GB c on the host (generalised_eigh); the smallest pivot of GB in unit-diagonal scaling below
@@ -150,27 +151,46 @@ int lobpcg_solve(spmv_ctx* ctx, const spmv_mat* A, int k, int nev, bool largest,
         return block_combine_launch(ctx, n, p, B, ld, q, Cdev + kCoef, Out, ld);
     };
     double* const cm = coef.data() + kCoef;
-    // 0: B (and AB) orthonormalised in place;  1: rank loss, nothing written;  < 0: an error code
-    auto orthonormalise = [&](double* B, double* AB, int c) -> int {
+    // 0: B (and AB) orthonormalised in place;  1: rank loss, nothing written;  < 0: an error code.  With `kept`: a column that depends on
+    // those before it (a pivot below kLobpcgRankPivot in unit-diagonal scaling) is left out, and so on; the columns that stay are
+    // orthonormalised into the first kept->size() columns of B and named in *kept; 1 only when none stays
+    auto orthonormalise = [&](double* B, double* AB, int c, std::vector<int>* kept = nullptr) -> int {
         int rc = gram(c, B, c, B, 0);
         if (rc == SPMV_OK) rc = fetch((size_t)c * c);
         if (rc != SPMV_OK) return rc;
+        std::vector<int>    keep(c);
         std::vector<double> d(c), L((size_t)c * c), Li((size_t)c * c);
-        for (int i = 0; i < c; ++i)
+        for (int i = 0; i < c; ++i) keep[i] = i;
+        int r = c;
+        for (;;)
         {
-            const double g = G[(size_t)i * c + i];
-            if (!(g > 0.0) || !std::isfinite(g)) return 1;
-            d[i] = 1.0 / std::sqrt(g);
+            int bad = -1;
+            for (int i = 0; i < r && bad < 0; ++i)
+            {
+                const double g = G[(size_t)keep[i] * c + keep[i]];
+                if (!(g > 0.0) || !std::isfinite(g)) bad = i;
+                else d[i] = 1.0 / std::sqrt(g);
+            }
+            if (bad < 0)
+            {
+                for (int i = 0; i < r; ++i)
+                    for (int j = 0; j < r; ++j) L[(size_t)i * r + j] = i == j ? 1.0 : d[i] * G[(size_t)keep[i] * c + keep[j]] * d[j];
+                bad = dense::cholesky_first_pivot_below(r, L.data(), kLobpcgRankPivot);
+            }
+            if (bad < 0) break;
+            if (!kept) return 1;
+            keep.erase(keep.begin() + bad);
+            if (--r == 0) return 1;
         }
-        for (int i = 0; i < c; ++i)
-            for (int j = 0; j < c; ++j) L[(size_t)i * c + j] = i == j ? 1.0 : d[i] * G[(size_t)i * c + j] * d[j];
         double pivot = 0.0;
-        if (!dense::cholesky_lower(c, L.data(), &pivot) || pivot < kLobpcgRankPivot) return 1;
-        dense::tri_inverse_lower(c, L.data(), Li.data());
-        for (int i = 0; i < c; ++i)
-            for (int j = 0; j < c; ++j) cm[(size_t)i * c + j] = j >= i ? d[i] * Li[(size_t)j * c + i] : 0.0;
-        rc = combine(c, B, c, B, true);
-        if (rc == SPMV_OK && AB) rc = combine(c, AB, c, AB, false);
+        if (!dense::cholesky_lower(r, L.data(), &pivot)) return 1;
+        dense::tri_inverse_lower(r, L.data(), Li.data());
+        for (size_t e = 0; e < (size_t)c * r; ++e) cm[e] = 0.0;
+        for (int i = 0; i < r; ++i)
+            for (int j = i; j < r; ++j) cm[(size_t)keep[i] * r + j] = d[i] * Li[(size_t)j * r + i];
+        rc = combine(c, B, r, B, true);
+        if (rc == SPMV_OK && AB) rc = combine(c, AB, r, AB, false);
+        if (kept) kept->swap(keep);
         return rc;
     };
     double* const Xd  = S;
@@ -241,7 +261,7 @@ int lobpcg_solve(spmv_ctx* ctx, const spmv_mat* A, int k, int nev, bool largest,
                 wanted = wanted || j < nev;
             }
         if (!wanted || it >= max_iter) break;
-        const int na = (int)active.size(), m = k + np + na;
+        int           na = (int)active.size(), m = k + np + na;
         double* const Pd = S + (size_t)k * sn, * const APd = AS + (size_t)k * sn;
         double* const Wd = S + (size_t)(k + np) * sn, * const AWd = AS + (size_t)(k + np) * sn;
         // 3: W = M^-1 R_active, projected against X twice, orthonormalised; AW
@@ -266,7 +286,10 @@ int lobpcg_solve(spmv_ctx* ctx, const spmv_mat* A, int k, int nev, bool largest,
         }
         if (rc != SPMV_OK) break;
         {
-            const int o = orthonormalise(Wd, nullptr, na);
+            // rank loss among the residuals: the first column that depends on those before it is left out of this iteration, and so on;
+            // none left: INVALID
+            std::vector<int> kept;
+            const int        o = orthonormalise(Wd, nullptr, na, &kept);
             if (o < 0)
             {
                 rc = o;
@@ -274,11 +297,15 @@ int lobpcg_solve(spmv_ctx* ctx, const spmv_mat* A, int k, int nev, bool largest,
             }
             if (o == 1)
             {
-                set_error("%s: the preconditioned residuals have lost rank at iteration %d (a pivot below %g): X, theta and resid hold the last iterate", who,
-                          it, kLobpcgRankPivot);
+                set_error("%s: the preconditioned residuals have lost rank at iteration %d (no column with a pivot of %g or more): X, theta and resid hold the last iterate",
+                          who, it, kLobpcgRankPivot);
                 rc = SPMV_ERR_INVALID;
                 break;
             }
+            for (size_t i = 0; i < kept.size(); ++i) active[i] = active[(size_t)kept[i]];
+            active.resize(kept.size());
+            na = (int)kept.size();
+            m  = k + np + na;
         }
         for (int c = 0; c < na && rc == SPMV_OK; ++c) rc = mat_apply_ex(ctx, A, Wd + (size_t)c * sn, AWd + (size_t)c * sn, over);
         if (rc != SPMV_OK) break;

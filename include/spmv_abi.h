@@ -752,8 +752,9 @@ int spmv_block_combine(spmv_ctx* ctx, int64_t n, int32_t p, const spmv_vec* S, i
  *   through the handle's own kernel; Rayleigh-Ritz on X^T A X; X and AX rotated by its vectors.
  *   Iteration: (1) R = AX - X diag(theta) and resid_j = ||R_j||, one fused deterministic launch; (2) the host looks: active = the
  *   columns with resid_j > tol, every iteration anew; no active column among the first nev, or max_iter iterations run: stop;
- *   (3) W = M^-1 R_active; W -= X (X^T W), twice; orthonormalise W (rank loss: SPMV_ERR_INVALID, and X, theta, resid hold the last
- *   iterate); AW by one product per active column; (4) P, where it exists, is orthonormalised and AP transformed alike; rank loss
+ *   (3) W = M^-1 R_active; W -= X (X^T W), twice; orthonormalise W (rank loss: the first column that depends on those before it is
+ *   left out of this iteration, and so on; no column left: SPMV_ERR_INVALID, and X, theta, resid hold the last iterate); AW by one
+ *   product per column of W; (4) P, where it exists, is orthonormalised and AP transformed alike; rank loss
  *   drops P for this iteration; (5) S = [X P W], AS = [AX AP AW]; GB = S^T S and GA = S^T AS (symmetrised); GB's smallest pivot below
  *   1e-4 (kLobpcgBasisPivot) with P in use: the step is redone without P; (6) the host solves GA c = theta GB c and takes the k
  *   lowest (largest: highest) values and their vectors C; (7) X <- S C, AX <- AS C, P <- S C0[:, active], AP <- AS C0[:, active],

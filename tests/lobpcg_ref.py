@@ -1,17 +1,28 @@
 """NumPy twin of spmv_lobpcg (csrc/solver_lobpcg.hip) - TEST INFRASTRUCTURE ONLY (no GPU needed): the same algorithm in float64 with the
 same thresholds, the small problems through numpy.linalg instead of the engine's Jacobi rotations; the outcome checks (a)-(d) that
-every solve is held to; and the problems of tests/test_gpu_lobpcg.py with their exact eigenvalues.
+every solve is held to; and the problems of tests/test_gpu_lobpcg.py with their exact eigenvalues.  The last section is the pairs
+family (k = 16 at sizes past 256 workgroups and past one and two trips of the grid) and the record of the twin's runs on it:
+
+    python tests/lobpcg_ref.py --record     writes tests/golden/lobpcg_pairs_twin.json (some minutes: one BLAS thread)
+    python tests/lobpcg_ref.py --one-ulp    how far theta of the early iterates moves when the start block moves by one ulp
 
     start      orthonormalise X (rank loss: ValueError "start block");  AX = A X;  Rayleigh-Ritz on X^T AX
     iteration  R = AX - X diag(theta), resid_j = ||R_j||;  active = resid > tol;  none among the first nev, or max_iter: stop
-               W = M^-1 R_active;  W -= X (X^T W) twice;  orthonormalise W;  AW = A W
+               W = M^-1 R_active;  W -= X (X^T W) twice;  orthonormalise W (rank loss: without the first dependent column, and so on);  AW = A W
                P: orthonormalised with AP alike; rank loss drops it for this iteration
                S = [X P W];  GB = S^T S, GA = S^T AS symmetrised;  GB's smallest pivot (unit-diagonal scaling) < BASIS_PIVOT with P: without P
                the k lowest (largest: highest) pairs of GA c = theta GB c;  X = S C, AX = AS C, P = S C0[:, active], AP likewise
 """
 from __future__ import annotations
 
+import contextlib
+import json
 import math
+import os
+import re
+import sys
+import time
+from pathlib import Path
 
 import numpy as np
 
@@ -35,9 +46,31 @@ def _unit_diagonal_factor(G):
     return s, L, float(np.min(np.diag(L) ** 2))
 
 
-def orthonormalise(B, AB=None):
-    """(B T, AB T) with T = diag(s) L^-T, or None at rank loss (a pivot below RANK_PIVOT)"""
+def first_dependent_column(G):
+    """the first column of a block with Gram matrix G whose pivot in the unit-diagonal factorisation is below RANK_PIVOT (or whose
+    diagonal entry is not positive and finite); None: the block has full rank"""
+    d = np.diag(G)
+    for i in range(len(d)):
+        if not (d[i] > 0 and np.isfinite(d[i])):
+            return i
+    s = 1.0 / np.sqrt(d)
+    Gs = s[:, None] * G * s[None, :]
+    np.fill_diagonal(Gs, 1.0)
+    L = np.zeros_like(Gs)
+    for j in range(len(d)):
+        p = Gs[j, j] - L[j, :j] @ L[j, :j]
+        if not p >= RANK_PIVOT:
+            return j
+        L[j, j] = np.sqrt(p)
+        L[j + 1:, j] = (Gs[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    return None
+
+
+def orthonormalise(B, AB=None, seen=None):
+    """(B T, AB T) with T = diag(s) L^-T, or None at rank loss (a pivot below RANK_PIVOT); the smallest pivot is appended to `seen`"""
     f = _unit_diagonal_factor(B.T @ B)
+    if seen is not None:
+        seen.append(0.0 if f is None else f[2])
     if f is None or f[2] < RANK_PIVOT:
         return None
     s, L, _ = f
@@ -58,13 +91,17 @@ def generalised(GA, GB):
 
 
 # ---- the solver ------------------------------------------------------------------------------------------------------------------
-def lobpcg(matvec, X0, nev=None, largest=False, max_iter=500, tol=1e-8, precond=None):
-    """matvec(v) = A v and precond(r) = M^-1 r (None: the identity) on vectors.  Returns (theta[k], resid[k], iterations, X)"""
+def lobpcg(matvec, X0, nev=None, largest=False, max_iter=500, tol=1e-8, precond=None, stats=None):
+    """matvec(v) = A v and precond(r) = M^-1 r (None: the identity) on vectors.  Returns (theta[k], resid[k], iterations, X).
+    stats (a dict, optional) receives three lists indexed by the iteration count t: "theta" (theta after t iterations), "rank_pivot" and
+    "basis_pivot" (the smallest orthonormalisation pivot - the start block's counts for t = 0 - and the smallest pivot of the scaled GB
+    that iteration t + 1 saw on its way, whatever it decided on them)"""
     X = np.array(X0, dtype=np.float64, order="F")
     n, k = X.shape
     nev = k if nev is None else nev
     mv = lambda B: np.column_stack([matvec(np.ascontiguousarray(B[:, j])) for j in range(B.shape[1])])  # noqa: E731
-    o = orthonormalise(X)
+    rank_seen, basis_seen = [], []
+    o = orthonormalise(X, seen=rank_seen)
     if o is None:
         raise ValueError("start block")
     X = o[0]
@@ -81,20 +118,37 @@ def lobpcg(matvec, X0, nev=None, largest=False, max_iter=500, tol=1e-8, precond=
         resid = np.sqrt(np.sum(R * R, axis=0))
         if not (np.all(np.isfinite(theta)) and np.all(np.isfinite(resid))):
             raise ValueError("theta or a residual is not finite")
+        if stats is not None:
+            stats.setdefault("theta", []).append(theta.copy())
+            if it > 0:
+                stats.setdefault("rank_pivot", []).append(min(rank_seen))
+                stats.setdefault("basis_pivot", []).append(min(basis_seen))
+                rank_seen, basis_seen = [], []
         active = np.flatnonzero(resid > tol)
         if not np.any(active < nev) or it >= max_iter:
             return theta, resid, it, X
         W = R[:, active] if precond is None else np.column_stack([precond(np.ascontiguousarray(R[:, j])) for j in active])
         for _ in range(2):
             W = W - X @ (X.T @ W)
-        o = orthonormalise(W)
+        o = orthonormalise(W, seen=rank_seen)
         if o is None:
-            raise ValueError(f"the preconditioned residuals lost rank at iteration {it}")
+            # rank loss among the residuals: the first column that depends on those before it is left out of this iteration, and so on
+            G = W.T @ W
+            keep = list(range(len(active)))
+            while keep:
+                bad = first_dependent_column(G[np.ix_(keep, keep)])
+                if bad is None:
+                    break
+                del keep[bad]
+            o = orthonormalise(W[:, keep]) if keep else None
+            if o is None:
+                raise ValueError(f"the preconditioned residuals lost rank at iteration {it}")
+            active = active[keep]
         W = o[0]
         AW = mv(W)
         use_p = P is not None
         if use_p:
-            o = orthonormalise(P, AP)
+            o = orthonormalise(P, AP, seen=rank_seen)
             if o is None:
                 use_p = False
             else:
@@ -104,6 +158,7 @@ def lobpcg(matvec, X0, nev=None, largest=False, max_iter=500, tol=1e-8, precond=
             AS = np.column_stack([AX, AP, AW] if use_p else [AX, AW])
             GA = S.T @ AS
             g = generalised(0.5 * (GA + GA.T), S.T @ S)
+            basis_seen.append(0.0 if g is None else g[2])
             if (g is None or g[2] < BASIS_PIVOT) and use_p:
                 use_p = False
                 continue
@@ -142,8 +197,7 @@ def outcome_failures(apply_ld, anorm, X, theta, resid, nev, tol, lam, largest=Fa
         if not abs(true - resid[j]) <= 1e-12 * anorm:
             fails.append("b")
             break
-    Xl = X.astype(np.longdouble)
-    if not float(np.max(np.abs(Xl.T @ Xl - np.eye(k, dtype=np.longdouble)))) <= 1e-12:
+    if not float(np.max(np.abs(gram_ld(X, X) - np.eye(k, dtype=np.longdouble)))) <= 1e-12:
         fails.append("c")
     d = np.diff(theta)
     in_order = np.all(d <= 0) if largest else np.all(d >= 0)
@@ -292,3 +346,215 @@ def twin(name, vec_uniform, precond=None):
             precond = lambda r: dinv * r  # noqa: E731
         _twin[name] = lobpcg(E.matvec, start_block(name, vec_uniform), nev=nev, largest=largest, max_iter=max_iter, tol=tol, precond=precond)
     return _twin[name]
+
+
+# ---- the pairs family: an exact spectrum at any size, wanted vectors on chosen rows ---------------------------------------------------
+# Kept out of PROBLEMS: at these sizes the twin takes from seconds to a minute, so the GPU tests read what they need from it out of
+# tests/golden/lobpcg_pairs_twin.json (`python tests/lobpcg_ref.py --record` writes it; tests/test_lobpcg_ref.py holds it to the twin).
+ROOT = Path(__file__).resolve().parent.parent
+RECORD_PATH = ROOT / "tests" / "golden" / "lobpcg_pairs_twin.json"
+PAIRS_K = 16
+PAIRS_TOL = 1e-8
+PAIRS_MAX_ITER = 200
+EARLY = (0, 1, 2, 3)  # the max_iter values whose theta the record holds
+
+
+def grid_constants():
+    """kBlock and kMaxGrid as csrc/common.hpp defines them"""
+    text = (ROOT / "arm-spmv_amd" / "csrc" / "common.hpp").read_text()
+    vals = {}
+    for name, expr in re.findall(r"constexpr int (k\w+)\s*=\s*([^;]+);", text):
+        try:
+            vals[name] = int(eval(expr, {"__builtins__": {}}, dict(vals)))
+        except Exception:
+            pass
+    return vals["kBlock"], vals["kMaxGrid"]
+
+
+def pairs_sizes():
+    """n1: 257 workgroups (the last-ticket sum's second step);  n2: 258;  n3: a full grid and one row on the second trip;  n4: a third
+    trip and an odd tail"""
+    B, G = grid_constants()
+    return {"n1": 256 * B + 1, "n2": 257 * B + 1, "n3": G * B + 1, "n4": 2 * G * B + 2051}
+
+
+class PairsEntries(Entries):
+    """Entries of a pairs() matrix with products that use its structure (the same sums in the same order as Entries', see
+    tests/test_lobpcg_ref.py); matvec_ld also takes a block of columns"""
+
+    def matvec(self, x):
+        return self._apply(self.diagonal_values, x)
+
+    def matvec_ld(self, x):
+        return self._apply(self.diagonal_values.astype(np.longdouble), x)
+
+    def _apply(self, d, x):
+        y = (d * x.T).T
+        m = self.n - 1
+        y[0:m:2] -= x[1:m:2]
+        y[1:m:2] -= x[0:m:2]
+        return y
+
+
+def pairs_low(n, k):
+    """the pairs whose eigenvalues are wanted, sorted: on the first and last rows, on both sides of workgroup 256's edge, on both sides
+    of each trip edge, and spread evenly where the size has no such rows"""
+    B, G = grid_constants()
+    npairs = (n - 1) // 2
+    low = []
+    for r in (0, n - 3, G * B - 2, G * B, 2 * G * B - 2, 2 * G * B, 256 * B - 2, 256 * B, 254, G * B + 2, 2 * G * B + 2, 256 * B + 254):
+        if 0 <= r // 2 < npairs and r // 2 not in low:
+            low.append(r // 2)
+    for p in np.linspace(0, npairs - 1, 2 * k + 1).astype(np.int64)[1::2]:
+        if int(p) not in low:
+            low.append(int(p))
+    return np.array(sorted(low[:k]), dtype=np.int64)
+
+
+def pairs(n, k, largest=False):
+    """Rows 2p and 2p+1 form the block [[a_p, -1], [-1, a_p]] (p < (n-1)/2), row n-1 stands alone with 20: the eigenvalues are exactly
+    a_p - 1, a_p + 1 and 20, and ||A||_inf = max(a) + 1.  a is 10 + 10 u (u uniform: a continuous unwanted spectrum; a constant one makes
+    the residuals lose rank within three iterations) except on the k pairs of pairs_low, where it is 3.0 .. 3 + 0.1 (k-1) shuffled
+    (largest: 40 - that).  Returns (PairsEntries, every eigenvalue ascending)"""
+    assert n % 2 == 1 and (n - 1) // 2 >= k
+    npairs = (n - 1) // 2
+    a = 10.0 + 10.0 * np.random.default_rng(7).random(npairs)
+    shuffled = 0.1 * np.random.default_rng(0).permutation(k)
+    a[pairs_low(n, k)] = 40.0 - shuffled if largest else 3.0 + shuffled
+    d = np.r_[np.repeat(a, 2), 20.0]
+    i, p = np.arange(n), 2 * np.arange(npairs)
+    E = PairsEntries(n, np.r_[i, p, p + 1], np.r_[i, p + 1, p], np.r_[d, np.full(2 * npairs, -1.0)])
+    E.diagonal_values = d
+    return E, np.sort(np.r_[a - 1.0, a + 1.0, 20.0])
+
+
+# name -> (size, nev, largest, preconditioner); k = PAIRS_K, tol = PAIRS_TOL, max_iter = PAIRS_MAX_ITER
+PAIRS_CASES = {
+    "pairs_n1_nev16_jacobi": ("n1", 16, False, "jacobi"),
+    "pairs_n1_nev12": ("n1", 12, False, None),
+    "pairs_n2_nev12_jacobi": ("n2", 12, False, "jacobi"),
+    "pairs_n2_nev12_largest": ("n2", 12, True, None),
+    "pairs_n3_nev12_jacobi": ("n3", 12, False, "jacobi"),
+    "pairs_n4_nev12_jacobi": ("n4", 12, False, "jacobi"),
+    "pairs_n4_nev16_jacobi": ("n4", 16, False, "jacobi"),
+}
+PAIRS_QUICK = ("pairs_n1_nev16_jacobi", "pairs_n2_nev12_jacobi")  # the records that tests/test_lobpcg_ref.py recomputes every time
+# the cases whose early iterates are compared.  n1's is there for its last workgroup: it holds the row that stands alone and nothing else, a
+# row whose residual vanishes at convergence, so only an iterate on the way shows whether that workgroup's partial sum is added
+PAIRS_EARLY = ("pairs_n1_nev16_jacobi", "pairs_n2_nev12_jacobi", "pairs_n3_nev12_jacobi", "pairs_n4_nev12_jacobi")
+
+_pairs_made = {}
+
+
+def pairs_problem(name):
+    """(PairsEntries, eigenvalues in the order asked for, k, nev, largest, tol, max_iter, preconditioner); a matrix is made once"""
+    size, nev, largest, pre = PAIRS_CASES[name]
+    n = pairs_sizes()[size]
+    if (n, largest) not in _pairs_made:
+        E, lam = pairs(n, PAIRS_K, largest)
+        _pairs_made[(n, largest)] = (E, lam[::-1].copy() if largest else lam)
+    E, lam = _pairs_made[(n, largest)]
+    return E, lam, PAIRS_K, nev, largest, PAIRS_TOL, PAIRS_MAX_ITER, pre
+
+
+def pairs_start(n, vec_uniform):
+    """the start block (n, PAIRS_K): spmv_gen_vec_uniform's twin over n * k entries with seed 1, column-major"""
+    return np.asfortranarray(vec_uniform(n * PAIRS_K, seed=1).reshape(PAIRS_K, n).T)
+
+
+def pairs_twin(name, vec_uniform, max_iter=None, X0=None, stats=None):
+    """the twin on a pairs case: (theta, resid, iterations, X)"""
+    E, _, k, nev, largest, tol, limit, pre = pairs_problem(name)
+    dinv = 1.0 / E.diagonal_values
+    return lobpcg(E.matvec, pairs_start(E.n, vec_uniform) if X0 is None else X0, nev=nev, largest=largest, max_iter=limit if max_iter is None else max_iter,
+                  tol=tol, precond=(lambda r: dinv * r) if pre == "jacobi" else None, stats=stats)
+
+
+def _one_blas_thread():
+    """a record is compared bit for bit, and the order in which a threaded BLAS adds up B^T B depends on its thread count: threadpoolctl
+    holds it to one, or, where that is not installed, the process was started with OMP_NUM_THREADS=1 (tests/conftest.py sets it); with
+    neither no record is made"""
+    try:
+        from threadpoolctl import threadpool_limits
+    except ImportError:
+        if os.environ.get("OMP_NUM_THREADS") != "1":
+            raise RuntimeError("a twin record needs a one-thread BLAS: install threadpoolctl or start python with OMP_NUM_THREADS=1")
+        return contextlib.nullcontext()
+    return threadpool_limits(limits=1, user_api="blas")
+
+
+def pairs_record(name, vec_uniform):
+    """what the GPU tests need from the twin on one case: its iteration count, theta (all k, float.hex) after 0 .. 3 iterations and the
+    smallest pivots those three iterations saw.  From the twin alone, never from the GPU; a twin that refuses the case raises"""
+    E, _, k, nev, largest, tol, limit, pre = pairs_problem(name)
+    stats = {}
+    with _one_blas_thread():
+        _, resid, it, _ = pairs_twin(name, vec_uniform, stats=stats)
+    t = len(EARLY)
+    assert it < limit and np.all(resid[:nev] <= tol) and len(stats["basis_pivot"]) >= t - 1, (name, it, resid)
+    return {"n": E.n, "k": k, "nev": nev, "largest": largest, "precond": pre or "none", "iterations": int(it),
+            "theta": [[float(v).hex() for v in stats["theta"][i]] for i in EARLY],
+            "rank_pivot": float(min(stats["rank_pivot"][:t - 1])).hex(), "basis_pivot": float(min(stats["basis_pivot"][:t - 1])).hex()}
+
+
+def load_records():
+    with open(RECORD_PATH) as f:
+        return json.load(f)
+
+
+def recorded_theta(rec):
+    """theta of a record as an array (len(EARLY), k)"""
+    return np.array([[float.fromhex(v) for v in row] for row in rec["theta"]])
+
+
+def gram_ld(U, V, rows=2048):
+    """U^T V in long double, added up over chunks of rows (NumPy has no fast long-double product: a chunk stays in the cache)"""
+    G = np.zeros((U.shape[1], V.shape[1]), dtype=np.longdouble)
+    for lo in range(0, U.shape[0], rows):
+        G += np.ascontiguousarray(U[lo:lo + rows].T, dtype=np.longdouble) @ np.asarray(V[lo:lo + rows], dtype=np.longdouble)
+    return G
+
+
+def ritz_failure(E, X, theta):
+    """check (e), over all k columns in long double: max |X^T A X - diag(theta)| <= 1e-12 ||A||_inf.  Returns the excess as text, or None"""
+    Xl = np.asarray(X, dtype=np.longdouble)
+    err = float(np.max(np.abs(gram_ld(Xl, E.matvec_ld(Xl)) - np.diag(np.asarray(theta, dtype=np.longdouble)))))
+    return None if err <= 1e-12 * E.norm_inf() else f"e: max |X^T A X - diag(theta)| = {err:.3e} > 1e-12 ||A||_inf = {1e-12 * E.norm_inf():.3e}"
+
+
+def _vec_uniform():
+    sys.path.insert(0, str(ROOT))
+    from __graft_entry__ import load_package
+
+    return load_package().synth.vec_uniform
+
+
+def main(argv):
+    vec_uniform = _vec_uniform()
+    if argv == ["--record"]:
+        records = {}
+        for name in PAIRS_CASES:
+            t0 = time.perf_counter()
+            records[name] = pairs_record(name, vec_uniform)
+            print(f"{name}: {records[name]['iterations']} iterations, {time.perf_counter() - t0:.1f} s", flush=True)
+        with open(RECORD_PATH, "w") as f:
+            json.dump(records, f, indent=1)
+            f.write("\n")
+    elif argv == ["--one-ulp"]:
+        # how far theta after 0 .. 3 iterations moves when every entry of the start block moves by one ulp: the yardstick of the
+        # early-iterate gate of tests/test_gpu_lobpcg.py
+        for name in PAIRS_EARLY:
+            E = pairs_problem(name)[0]
+            X0 = pairs_start(E.n, vec_uniform)
+            a, b = {}, {}
+            pairs_twin(name, vec_uniform, max_iter=EARLY[-1], X0=X0, stats=a)
+            pairs_twin(name, vec_uniform, max_iter=EARLY[-1], X0=np.nextafter(X0, np.inf), stats=b)
+            a, b = a["theta"], b["theta"]
+            moved = [float(np.max(np.abs(u - v))) for u, v in zip(a, b)]
+            print(f"{name}: ||A||_inf = {E.norm_inf()}, theta moved by " + ", ".join(f"{m:.2e}" for m in moved), flush=True)
+    else:
+        raise SystemExit("usage: python tests/lobpcg_ref.py --record | --one-ulp")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -4,6 +4,8 @@
 // (1 .. 1e12, bare and under small couplings), and for the generalised problem a GB that is nearly singular.  With eps = 2^-52,
 // ||.|| the largest absolute row sum and B(A) = 64 order eps ||A||:
 //   * jacobi_eigh:       ||A V - V W||_max <= B(A), ||V^T V - I||_max <= B(I), the values ascending;
+//   * cholesky_first_pivot_below: the first pivot below a threshold, by cholesky_lower's own sums (the threshold at the smallest pivot
+//                        and one ulp above it), G left alone
 //   * cholesky_lower:    L L^T = G to B(G), the upper triangle cleared, the reported pivot EQUAL to the smallest one of a second
 //                        factorisation written out here (the same sums in the same order), and the factor's own diagonal squared agrees;
 //   * tri_inverse_lower: L Li = I to B(I) cond(L);
@@ -278,6 +280,17 @@ int main()
         double              piv = 1.0;
         expect(!cholesky_lower(2, L.data(), &piv) && piv == -3.0, "an indefinite matrix is refused with its pivot", 2, piv + 3.0, 0);
         expect(!generalised_eigh(2, G.data(), G.data(), th.data(), C.data(), &piv), "an indefinite GB is refused", 2, 0, 0);
+        expect(cholesky_first_pivot_below(2, G.data(), 0.0) == 1 && G[1] == 2.0, "the first pivot that is not positive, G left alone", 2, 0, 0);
+        // three unit columns, the third at an angle of 1e-4 to the second: pivots 1, 1, about 1e-8
+        const double        s = 1e-4, c = std::sqrt(1.0 - s * s);
+        std::vector<double> D = {1.0, 0.0, 0.0, 0.0, 1.0, c, 0.0, c, 1.0};
+        expect(cholesky_first_pivot_below(3, D.data(), 1e-6) == 2 && cholesky_first_pivot_below(3, D.data(), 1e-9) == -1, "the first pivot below a threshold", 3,
+               0, 0);
+        std::vector<double> Dl = D;
+        expect(cholesky_lower(3, Dl.data(), &piv) && cholesky_first_pivot_below(3, D.data(), piv) == -1 &&
+                   cholesky_first_pivot_below(3, D.data(), std::nextafter(piv, 1.0)) == 2,
+               "the pivots are cholesky_lower's own", 3, 0, 0);
+        expect(cholesky_first_pivot_below(0, D.data(), 1.0) == -1 && cholesky_first_pivot_below(kMaxOrder + 1, D.data(), 1.0) == -1, "orders out of range", 0, 0, 0);
         expect(!jacobi_eigh(2, N.data(), V.data(), th.data()), "a NaN is refused", 2, 0, 0);
         expect(!jacobi_eigh(0, N.data(), V.data(), th.data()) && !jacobi_eigh(kMaxOrder + 1, N.data(), V.data(), th.data()), "orders out of range", 0, 0, 0);
     }
