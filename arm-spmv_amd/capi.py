@@ -21,6 +21,7 @@ CSR_AUTO, CSR_VECTOR, CSR_LDSWIN, CSR_SCALAR, CSR_PANEL, CSR_TWOPHASE, CSR_SEGSC
 AMG_RESTRICT_FUSED, AMG_RESTRICT_UNFUSED, AMG_PROLONG_FUSED, AMG_PROLONG_UNFUSED = 0, 1, 2, 3  # spmv_amg_transfer_timed
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_SYMGS, PRECOND_ILU0, PRECOND_CHEBYSHEV, PRECOND_AMG = 0, 1, 2, 3, 4, 5
 PRECOND_FSAI = 6
+TRSV_LOWER, TRSV_UPPER, TRSV_UNIT, TRSV_TRANSPOSE = 0, 1, 2, 4  # spmv_trsv_*'s flags
 REFINE_CG, REFINE_BICGSTAB = 0, 1  # spmv_refine's inner solver
 FSAI_MAX_ROW = 64  # SPMV_FSAI_MAX_ROW: the cap on the pattern columns of a row of G
 SPGEMM_AUTO, SPGEMM_ROWS, SPGEMM_SORT = 0, 1, 2  # spmv_spgemm's method
@@ -121,6 +122,10 @@ SIGNATURES = {
     "spmv_ilu0_solve": (C.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_ilu0_factors": (C.c_int, [_vp, _vp, _f64p]),
     "spmv_ilu0_order": (C.c_int, [_vp, _vp, _i32p]),
+    "spmv_trsv_setup": (C.c_int, [_vp, _vp, C.c_uint32]),
+    "spmv_trsv_solve": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
+    "spmv_trsv_solve_multi": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int32, _vp, _vp]),
+    "spmv_trsv_info": (C.c_int, [_vp, C.c_uint32, _i32p, _i32p, _i32p, _i64p]),
     "spmv_chebyshev_coefficients": (C.c_int, [C.c_int32, C.c_double, C.c_double, _f64p, _f64p, _f64p]),
     "spmv_lanczos": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_uint64, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "spmv_chebyshev_setup": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_double]),
@@ -538,6 +543,29 @@ class Context:
         out = np.zeros(A.info.nrow, dtype=np.int32)
         _check(self._lib.spmv_ilu0_order(self.h, A.h, out.ctypes.data_as(_i32p)))
         return out
+
+    def trsv_setup(self, A: "Matrix", flags: int = TRSV_LOWER) -> None:
+        """analyses the triangle of a square CSR handle that `flags` selects (TRSV_LOWER | TRSV_UPPER, + TRSV_TRANSPOSE): a working
+        copy, its levels and launch schedule (synchronous, idempotent; one analysis per uplo and transpose, shared by UNIT and
+        non-UNIT solves).  Without TRSV_UNIT a missing, zero or non-finite diagonal entry raises, naming the row"""
+        _check(self._lib.spmv_trsv_setup(self.h, A.h, flags))
+
+    def trsv_solve(self, A: "Matrix", b: "Vector", x: "Vector", flags: int = TRSV_LOWER) -> None:
+        """x = op(T)^-1 b with the selected triangle of A plus the diagonal (TRSV_UNIT: a unit diagonal), set up on first use,
+        asynchronous; entries of the other triangle are ignored.  b and x may be the same vector, else they must not overlap"""
+        _check(self._lib.spmv_trsv_solve(self.h, A.h, flags, b.h, x.h))
+
+    def trsv_solve_multi(self, A: "Matrix", B: "Vector", X: "Vector", k: int, flags: int = TRSV_LOWER) -> None:
+        """the same for k right-hand sides (1 .. 64) in the launches of one solve; B and X row-major (nrow, k) as apply_multi's.
+        Column c has the bits of a k = 1 solve of that column; B and X may be the same vector"""
+        _check(self._lib.spmv_trsv_solve_multi(self.h, A.h, flags, k, B.h, X.h))
+
+    def trsv_info(self, A: "Matrix", flags: int = TRSV_LOWER) -> dict:
+        """{levels, lanes, launches, bytes} of the analysis `flags` selects: dependency levels, lanes per row and launches of one
+        trsv_solve, device bytes; raises where the handle has no such analysis"""
+        lv, ln, la, by = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        _check(self._lib.spmv_trsv_info(A.h, flags, C.byref(lv), C.byref(ln), C.byref(la), C.byref(by)))
+        return dict(levels=lv.value, lanes=ln.value, launches=la.value, bytes=by.value)
 
     def lanczos(self, A: "Matrix", steps: int, scaled: bool = False, seed: int = 1):
         """`steps` (1 .. 64) Lanczos steps without reorthogonalisation on a symmetric handle (scaled: on diag(sqrt s) A diag(sqrt s),

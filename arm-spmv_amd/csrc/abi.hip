@@ -92,6 +92,7 @@ void mat_free(spmv_mat* m)
 {
     if (!m) return;
     transpose_free(m);  // (the companion borrows the arrays freed below)
+    trsv_free(m);
     if (m->owned)
     {
         if (m->a) (void)hipFree(const_cast<int32_t*>(m->a));
@@ -1004,6 +1005,7 @@ int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value)
     for (const precond_row& P : kPreconds)  // the preconditioners' own: what each unit's hook lists
         if (P.get_param && P.get_param(m, name, value)) return SPMV_OK;
     if (spgemm_get_param(m, name, value)) return SPMV_OK;  // "spgemm_products", "spgemm_rows_lds", "spgemm_rows_sorted", "spgemm_lds_products", ...
+    if (trsv_get_param(m, name, value)) return SPMV_OK;  // "trsv_ready", "trsv_bytes", "trsv_multi_launches", "trsv_multi_level_launches"
     if (transpose_get_param(m, name, value)) return SPMV_OK;  // "transpose_ready", "transpose_bytes", "transpose_kernel", ...
     if (!strcmp(name, "panel_keep_csr"))
         *value = (m->b && m->v) || m->nnz == 0 ? 1 : 0;
@@ -1632,6 +1634,61 @@ int spmv_ilu0_order(spmv_ctx* ctx, const spmv_mat* A, int32_t* order_host)
     SPMV_TRY(use_device(ctx));
     SPMV_TRY(ilu0_setup(const_cast<spmv_mat*>(A)));
     return ilu0_sequence(A, order_host);
+}
+
+// Triangular solves with the handle's own triangles (sptrsv.hip).  Every check is made before the device is touched.
+int spmv_trsv_setup(spmv_ctx* ctx, spmv_mat* A, uint32_t flags)
+{
+    SPMV_REQUIRE(ctx && A, "spmv_trsv_setup: null argument");
+    SPMV_TRY(trsv_check_flags(flags, "spmv_trsv_setup"));
+    SPMV_REQUIRE(A->ctx == ctx, "spmv_trsv_setup: the matrix belongs to another context");
+    SPMV_TRY(trsv_check_handle(A, "spmv_trsv_setup"));
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    return trsv_setup(A, flags);
+}
+
+// b and x: the same vector, or apart
+static int check_trsv_vectors(const char* who, int64_t want, const char* name_b, const spmv_vec* b, const char* name_x, const spmv_vec* x)
+{
+    SPMV_REQUIRE(b->n == want && x->n == want, "%s: %s has %lld and %s %lld entries, %lld expected", who, name_b, (long long)b->n, name_x,
+                 (long long)x->n, (long long)want);
+    SPMV_REQUIRE(b->d == x->d || vectors_disjoint(b, x), "%s: %s and %s overlap in part: they may be the same vector or lie apart", who, name_b,
+                 name_x);
+    return SPMV_OK;
+}
+
+int spmv_trsv_solve(spmv_ctx* ctx, const spmv_mat* A, uint32_t flags, const spmv_vec* b, spmv_vec* x)
+{
+    SPMV_REQUIRE(ctx && A && b && x, "spmv_trsv_solve: null argument");
+    SPMV_TRY(trsv_check_flags(flags, "spmv_trsv_solve"));
+    SPMV_REQUIRE(A->ctx == ctx, "spmv_trsv_solve: the matrix belongs to another context");
+    SPMV_TRY(trsv_check_handle(A, "spmv_trsv_solve"));
+    SPMV_TRY(check_trsv_vectors("spmv_trsv_solve", A->nrow, "b", b, "x", x));
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    SPMV_TRY(trsv_setup(const_cast<spmv_mat*>(A), flags));  // first call: the working copy and its analysis (synchronous); later calls: nothing
+    return trsv_apply(ctx, A, flags, b->d, x->d);
+}
+
+int spmv_trsv_solve_multi(spmv_ctx* ctx, const spmv_mat* A, uint32_t flags, int32_t k, const spmv_vec* B, spmv_vec* X)
+{
+    SPMV_REQUIRE(ctx && A && B && X, "spmv_trsv_solve_multi: null argument");
+    SPMV_TRY(trsv_check_flags(flags, "spmv_trsv_solve_multi"));
+    SPMV_REQUIRE(k >= 1 && k <= 64, "spmv_trsv_solve_multi: k = %d, must be in [1, 64]", k);
+    SPMV_REQUIRE(A->ctx == ctx, "spmv_trsv_solve_multi: the matrix belongs to another context");
+    SPMV_TRY(trsv_check_handle(A, "spmv_trsv_solve_multi"));
+    SPMV_TRY(check_trsv_vectors("spmv_trsv_solve_multi", (int64_t)A->nrow * k, "B", B, "X", X));
+    if (A->nrow == 0) return SPMV_OK;
+    SPMV_TRY(use_device(ctx));
+    SPMV_TRY(trsv_setup(const_cast<spmv_mat*>(A), flags));
+    return trsv_apply_multi(ctx, A, flags, k, B->d, X->d);
+}
+
+int spmv_trsv_info(const spmv_mat* A, uint32_t flags, int32_t* levels, int32_t* lanes, int32_t* launches, int64_t* bytes)
+{
+    SPMV_REQUIRE(A, "spmv_trsv_info: null argument");
+    return trsv_info(A, flags, levels, lanes, launches, bytes);
 }
 
 // The Chebyshev polynomial preconditioner and the Lanczos spectrum estimate (chebyshev.hip).  Every check is made before the device is

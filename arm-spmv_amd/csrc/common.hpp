@@ -152,6 +152,7 @@ struct cheby_state;
 struct amg_state;
 struct fsai_state;
 struct transpose_state;
+struct trsv_state;
 // ---- plans (plan.hip): the decisions a handle's set-up made - by model or by timing - as plain data ------------------------------
 // One node per handle, children by index (the row-grouped copy of a COO / CSC / ELL handle or the short-row copy of a split,
 // the long rows' matrix of a split in virtual-row mode, the ELL copy of a CSR handle).  32 four-byte fields, no pointers:
@@ -366,6 +367,11 @@ struct spmv_mat
     // forward state (kernel, copies, plan) or of the transposed state
     struct spmv::ilu0_plan* ilu = nullptr;
     int32_t                 ilu_order = 1;  // "ilu0_order": 1 multicolour (default), 0 the matrix's own row order
+
+    // triangular solves with the handle's own triangles (sptrsv.hip): a working copy, levels and schedules per (uplo, transpose) pair;
+    // built by spmv_trsv_setup (or by the first solve), counted in device_bytes, no part of the forward state, of plans or of the
+    // symgs, ILU(0) and transposed states
+    struct spmv::trsv_state* trsv = nullptr;
 
     // the transposed product (transpose.hip): a companion handle of A^T over A's arrays, or the DIA transposed kernel's set-up;
     // built by spmv_mat_transpose_setup, no part of the forward state (kernel, copies, device_bytes, plan) - but for a BSR and a
@@ -640,6 +646,15 @@ int  ilu0_factor_values(const spmv_mat* m, double* out);      // aligned to the 
 int  ilu0_sequence(const spmv_mat* m, int32_t* out);
 bool ilu0_get_param(const spmv_mat* m, const char* name, int64_t* value);      // "ilu0_*"; false: not one of them
 bool ilu0_set_param(spmv_mat* m, const char* name, int64_t value, int* rc);  // "ilu0_order"; false: not that
+// sptrsv.hip: x = op(T)^-1 b with the strictly lower / upper part of a CSR handle plus the diagonal (flags: SPMV_TRSV_*)
+int  trsv_check_flags(uint32_t flags, const char* who);      // on the host: INVALID (unknown bits)
+int  trsv_check_handle(const spmv_mat* m, const char* who);  // on the host: UNSUPPORTED (not CSR) / INVALID (a shard, not square, arrays released)
+int  trsv_setup(spmv_mat* m, uint32_t flags);                // the working copy and its analysis (synchronous; once per handle, uplo and transpose)
+void trsv_free(spmv_mat* m);
+int  trsv_apply(spmv_ctx* ctx, const spmv_mat* A, uint32_t flags, const double* b, double* x);  // asynchronous; b may be x
+int  trsv_apply_multi(spmv_ctx* ctx, const spmv_mat* A, uint32_t flags, int32_t k, const double* B, double* X);  // row-major n x k; B may be X
+int  trsv_info(const spmv_mat* m, uint32_t flags, int32_t* levels, int32_t* lanes, int32_t* launches, int64_t* bytes);
+bool trsv_get_param(const spmv_mat* m, const char* name, int64_t* value);  // "trsv_*"; false: not one of them
 // chebyshev.hip: the Chebyshev polynomial preconditioner z = p_d(diag(s) A) diag(s) r (SPMV_PRECOND_CHEBYSHEV), and the Lanczos estimate
 int  cheby_coefficients(int degree, double lmin, double lmax, double* c0, double* c1, double* c2);  // host only; c1, c2: degree entries
 int  cheby_check_handle(const spmv_mat* m, const char* who);  // on the host: INVALID (not square, a shard that starts behind row 0)

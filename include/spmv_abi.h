@@ -371,7 +371,7 @@ int spmv_mat_set_param(spmv_mat* m, const char* name, int64_t value);
  * handle were found to be diagonals and conforming rows read no column index), "symgs_order", "symgs_colours",
  * "symgs_levels_forward", "symgs_levels_backward", "symgs_launches", "symgs_bytes", "symgs_fused" (1: the colouring is proper and
  * the sweep takes one launch per colour), "ilu0_order", "ilu0_ready", "ilu0_colours", "ilu0_levels_forward", "ilu0_levels_backward",
- * "ilu0_launches" (per application), "ilu0_bytes", the "cheby_*" names listed at spmv_chebyshev_setup, the "amg_*" names listed
+ * "ilu0_launches" (per application), "ilu0_bytes", the "trsv_*" names listed at spmv_trsv_setup, the "cheby_*" names listed at spmv_chebyshev_setup, the "amg_*" names listed
  * at spmv_amg_setup, the "fsai_*" names listed at spmv_fsai_setup and the "spgemm_*" names listed at spmv_spgemm. */
 int spmv_mat_get_param(const spmv_mat* m, const char* name, int64_t* value);
 /* ---- plans: a handle's set-up decisions as plain data (plan.hip) ------------------------------------------------------------
@@ -830,6 +830,48 @@ int spmv_ilu0_setup(spmv_ctx* ctx, spmv_mat* A);
 int spmv_ilu0_solve(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* r, spmv_vec* z);
 int spmv_ilu0_factors(spmv_ctx* ctx, const spmv_mat* A, double* values_host /* nnz entries */);
 int spmv_ilu0_order(spmv_ctx* ctx, const spmv_mat* A, int32_t* order_host /* nrow entries */);
+
+/* Sparse triangular solves with a matrix the caller supplies: x = op(T)^-1 b for one right-hand side or k of them, by level
+ *   scheduling (sptrsv.hip).  A: a CSR handle that holds the whole square matrix and still has its arrays - a Cholesky,
+ *   IC, ILUT or ILU(k) factor computed elsewhere, a triangular operator, or the combined LU array of spmv_ilu0_factors uploaded on
+ *   A's own pattern.
+ *   Definition.  flags selects T: SPMV_TRSV_LOWER the entries with column < row, SPMV_TRSV_UPPER those with column > row, plus the
+ *   diagonal; entries of the other triangle are ignored, not refused.  Duplicates of the diagonal entry are summed; every other
+ *   stored entry, duplicates and stored zeros included, is a term of its own; columns may be unsorted and the order inside a row is
+ *   kept.  SPMV_TRSV_UNIT: the diagonal is 1 and stored diagonal entries are ignored.  SPMV_TRSV_TRANSPOSE: op(T) = T^T, solved
+ *   from a transposed working copy whose rows hold their entries in ascending column index (duplicates in stored order).
+ *   spmv_trsv_setup: a working copy of the selected triangle, its dependency levels, rows by level and the launch schedule
+ *   (tri_levels.hpp, as spmv_ilu0_setup's triangles).  Synchronous, idempotent.  A handle holds one analysis per (uplo, transpose)
+ *   pair, up to four; UNIT and non-UNIT solves share it.  Without UNIT: a diagonal entry that is missing, zero or not finite is
+ *   SPMV_ERR_INVALID, the message names the smallest such row, and the call leaves nothing in the handle that was not there before
+ *   (the same handle still solves with UNIT).  SPMV_ERR_UNSUPPORTED if a dependency chain exceeds 2^18 rows.  Re-analysis after the
+ *   values of a wrapped handle changed is not offered.
+ *   spmv_trsv_solve: x = op(T)^-1 b, asynchronous; sets the handle up on first use although it is passed as const.  b and x may be
+ *   the SAME vector (a row reads b at its own index only, before it writes x there); otherwise they must not overlap.  1, 4 or 16
+ *   lanes share a row (by the triangle's entries per row) and their partial sums meet in a fixed tree: two solves give the same bits.
+ *   spmv_trsv_solve_multi: the same for k right-hand sides, 1 <= k <= 64, B and X row-major n x k (the layout of spmv_apply_multi),
+ *   in the launches of ONE solve: a group of T lanes owns a row (T the next power of two >= min(k, 16)), lane t its column t of every
+ *   tile of 16 columns.  Order contract: for every column a row's sum runs left to right over the working copy's entries from 0.0 with
+ *   fma, then x = b - acc (UNIT) or (b - acc) / d.  Column c of a k-column solve is therefore bit-identical to a k = 1 solve of that
+ *   column, for every k, and to spmv_trsv_solve wherever spmv_trsv_info reports 1 lane.  B and X may be the same vector.
+ *   spmv_trsv_info: levels, lanes per row and launches per spmv_trsv_solve of the analysis `flags` selects, and its device bytes;
+ *   any output may be null; SPMV_ERR_INVALID where that analysis is not there.
+ *   Refused on the host, before any device use: a handle that is not CSR (SPMV_ERR_UNSUPPORTED); a shard or a non-square matrix, a
+ *   handle whose arrays were released (panel_keep_csr 0), null pointers, unknown flag bits, vectors of other than nrow (nrow * k)
+ *   entries, k outside 1 .. 64, vectors that overlap in part, another context's handle (SPMV_ERR_INVALID).  nrow = 0: SPMV_OK,
+ *   nothing is launched.
+ *   The state lives in the handle (spmv_mat_get_param "trsv_ready": bit (upper ? 1 : 0) | (transpose ? 2 : 0) of every analysis
+ *   present; "trsv_bytes"; "trsv_multi_launches" and "trsv_multi_level_launches": the launches of the last spmv_trsv_solve_multi,
+ *   all of them and those that were a level of their own), is counted in device_bytes and freed with the handle; the forward kernel,
+ *   the copies, the plan and the symgs, ILU(0) and transposed states stay as they were. */
+#define SPMV_TRSV_LOWER     0u
+#define SPMV_TRSV_UPPER     1u
+#define SPMV_TRSV_UNIT      2u /* the diagonal is 1; stored diagonal entries are ignored */
+#define SPMV_TRSV_TRANSPOSE 4u /* solve with the transpose of the selected triangle */
+int spmv_trsv_setup(spmv_ctx* ctx, spmv_mat* A, uint32_t flags);
+int spmv_trsv_solve(spmv_ctx* ctx, const spmv_mat* A, uint32_t flags, const spmv_vec* b, spmv_vec* x);
+int spmv_trsv_solve_multi(spmv_ctx* ctx, const spmv_mat* A, uint32_t flags, int32_t k, const spmv_vec* B, spmv_vec* X);
+int spmv_trsv_info(const spmv_mat* A, uint32_t flags, int32_t* levels, int32_t* lanes, int32_t* launches, int64_t* bytes);
 
 /* The Chebyshev polynomial preconditioner / smoother, and the Lanczos estimate of a symmetric handle's extreme eigenvalues
  * (chebyshev.hip).  A: a handle of any format that holds the whole square matrix (a shard that starts behind row 0:
