@@ -45,7 +45,7 @@ class Operator:
         row, col = row.astype(np.int64), col.astype(np.int64)
         m, n = shape
         assert len(row) == 0 or (row.min() >= 0 and row.max() < m and col.min() >= 0 and col.max() < n)
-        self.shape, self.kind = (m, n), kind
+        self.shape, self.kind, self.row_order = (m, n), kind, row_order
         v = _conv(val, kind)
         idx = np.arange(len(row))
         if row_order == "reversed":

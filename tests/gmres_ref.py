@@ -19,8 +19,10 @@ as csrc/solver_gmres.hip states it:
         and if the solve goes on, r = b - A x again
 
 x_k is the GMRES iterate formed from the columns that stand after k iterations (what spmv_gmres leaves at max_iter = k,
-rel_tol = 0), its residual |g_{j+1}| / ||b||.  M = I, or diag(A) (duplicates summed) for precond = "jacobi", or any callable (the
-ILU(0) application of tests/ilu0_ref.py, float64 only).  v_{j+1} is formed when the next iteration asks for it, so the last
+rel_tol = 0), its residual |g_{j+1}| / ||b||.  M = I, or diag(A) (duplicates summed) for precond = "jacobi", or an operator of
+tests/precond_ops.py (FSAI, ILU(0), Chebyshev as the engine applies them by launches: every arithmetic, every twin its own variant), or
+any callable (the ILU(0) application of tests/ilu0_ref.py, float64 only).
+v_{j+1} is formed when the next iteration asks for it, so the last
 iteration of a 1 x 1 .. 3 x 3 system divides nothing by a norm that is rounding noise.  The engine lets an iteration that starts
 with |g_j| <= 1e-14 ||b|| pass quietly and the reference does not: bicgstab_ref's drop rule takes such k off a problem's list.
 
@@ -37,6 +39,7 @@ from __future__ import annotations
 import numpy as np
 
 import bicgstab_ref as br
+import precond_ops
 from bicgstab_ref import DROP_BELOW, MAX_DROPPED, PROBLEMS, inverse_diagonal, kept, true_residual  # noqa: F401
 from cgls_ref import ROW_ORDERS, Operator, csr_arrays  # noqa: F401
 from solver_ref import DOT_ORDERS, F, FLOOR, _conv, _dot, _hp_kind, _sqrt, _xdev, available  # noqa: F401
@@ -46,8 +49,11 @@ RESTARTS = (4, 30)  # m = 4 puts restarts inside 13 iterations, m = 30 puts none
 # the wide basis: every tile edge of the dots kernel, a full basis, the restart behind it; and m = 1, a restart behind every iteration
 WIDE_KS = {64: (16, 17, 33, 64, 65, 66), 8: (8, 9, 16, 17), 1: (1, 2, 3)}
 MUTATIONS = ("rot", "g", "last_col", "keep_vm", "left", "no_minv", "tail")
+# those that only a preconditioner applied by launches makes possible (precond: an operator of tests/precond_ops.py)
+LAUNCHED_MUTATIONS = ("stale_z", "no_minv", "tail")
 # the worst leave-one-out ratios seen here (asserted <= F in tests/test_gmres_ref.py, which prints them)
 OBSERVED_LEAVE_ONE_OUT = {"x": 1.49, "residual": 2.60}
+OBSERVED_LEAVE_ONE_OUT_LAUNCHED = {"x": 1.35, "residual": 3.83}  # the same under the preconditioners applied by launches
 
 
 def _gmres(mv, minv, b, x0, kind, m, ks, dot_order="pairwise", mutate=None, rel_tol=None, max_iter=None):
@@ -78,7 +84,7 @@ def _gmres(mv, minv, b, x0, kind, m, ks, dot_order="pairwise", mutate=None, rel_
         g, g_plain = [beta], [beta]
         for j in range(m):
             V.append(pending[0] / pending[1])
-            w = mv(minv(V[j]))
+            w = mv(minv(V[j - 1] if mutate == "stale_z" and j else V[j]))
             h = [zero] * (j + 2)
             for _ in range(2):
                 c = [dot(V[i], w) for i in range(j + 1)]  # all against the same w
@@ -137,10 +143,13 @@ def _gmres(mv, minv, b, x0, kind, m, ks, dot_order="pairwise", mutate=None, rel_
     return (x, k) if to_tol else (out, hist)
 
 
-def _sides(Op, precond, mutate):
-    """(mv, M^-1, scale of b) of one Operator: precond None, "jacobi" or a callable; the mutation "left" moves Jacobi to the other side"""
+def _sides(Op, precond, mutate, dot_order="pairwise"):
+    """(mv, M^-1, scale of b) of one Operator: precond None, "jacobi", an operator of tests/precond_ops.py (any arithmetic; the twin's
+    variant from its row and dot order) or a callable (float64); the mutation "left" moves Jacobi to the other side"""
     if precond is None:
         return Op.mv, (lambda u: u), None
+    if precond_ops.is_op(precond):
+        return Op.mv, precond_ops.bound(precond, Op.kind, Op.row_order, dot_order), None
     if callable(precond):
         assert Op.kind == "f64"
         return Op.mv, precond, None
@@ -155,8 +164,9 @@ def run_gmres(Op: Operator, b, x0, ks, m, precond=None, dot_order="pairwise", mu
     """({k: (x_k, |g_{j+1}| / ||b||)}, the residual history for every k up to max(ks)).  mutate (the mutation check): "rot" the old
     rotations not applied to the new column; "g" y from the unrotated g = (beta, 0, ...); "last_col" the last column left out of
     x where the cycle is not full; "keep_vm" a restart that keeps v_m and |g_m| instead of recomputing r; "left" M^-1 on the left
-    (of A and of b); "no_minv" x += V y without M^-1; "tail" the last element of x never updated"""
-    mv, minv, scale = _sides(Op, precond, mutate)
+    (of A and of b); "no_minv" x += V y without M^-1; "tail" the last element of x never updated; "stale_z" from a cycle's second column
+    on M^-1 is applied to the basis vector before (z is not refreshed)"""
+    mv, minv, scale = _sides(Op, precond, mutate, dot_order)
     bb = _conv(b, Op.kind)
     return _gmres(mv, minv, bb * scale if scale is not None else bb, x0, Op.kind, m, ks, dot_order, mutate)
 

@@ -13,7 +13,16 @@ Problems: 1 x 1, 2 x 2, 3 x 3 dense; 33 x 33 and 4097 x 4097 random with a domin
 and one whose size is odd and beyond two sweeps of the vector kernels' largest grid (csrc/common.hpp: 2 * kMaxGrid * kBlock).  CSR
 under AUTO, plain and with Jacobi, and forced VECTOR, SCALAR and PANEL; COO (entries shuffled), CSC, ELL and DIA handles of the
 band; x and b 256-byte aligned (the 16-byte kernels) and 8 bytes past a 16-byte boundary (the 8-byte kernels); a random start and
-x0 = 0.  Then convergence to 1e-10 against the true residual, the stopping rules and special cases, refusals, reproducibility bit
+x0 = 0.
+
+The preconditioners applied by launches - FSAI, ILU(0) in row order, Chebyshev with given bounds - are stepped through in the same
+way (tests/precond_ops.py: BICGSTAB_CASES): the factor is read back from the handle, and the reference and its six twins apply that
+factor as a fixed linear operator in their own arithmetic, so a deviation belongs to the solver - phat and shat as buffers of their own,
+the two applications per iteration, the half, update and direction kernels reading them.  1 x 1 .. 3 x 3, the 33 x 33 Laplacian
+(n = 1089), upwind convection-diffusion on 45 x 45 (n = 2025) and the large odd size; both alignments, both starts.  AMG alone stays
+at convergence only (tests/test_gpu_amg.py): its cycle has no fixed factor to read back.
+
+Then convergence to 1e-10 against the true residual, the stopping rules and special cases, refusals, reproducibility bit
 for bit, the handle's state and the device memory before and after, and the torch operator.  test_every_case_ran asserts at the
 end that all of it ran; with SPMV_BICGSTAB_RATIOS=<file> it also writes the largest GPU deviation over twin envelope per problem
 (profiles/bicgstab_steps_gpu_vs_twin_envelope.txt).
@@ -28,10 +37,12 @@ import pytest
 
 import bicgstab_ref as br
 import oracle_lib as ol
+import precond_ops as po
 
 pytestmark = pytest.mark.gpu
 AUTO, VECTOR, SCALAR, PANEL = 0, 1, 3, 4
-NONE, JACOBI, SYMGS = 0, 1, 2
+NONE, JACOBI, SYMGS, ILU0, CHEBYSHEV, AMG, FSAI = 0, 1, 2, 3, 4, 5, 6
+LAUNCHED_ID = {"ilu0": ILU0, "chebyshev": CHEBYSHEV, "fsai": FSAI}
 INVALID, UNSUPPORTED = -1, -5
 CHECK_EVERY = (1, 4)
 PRECOND_NAME = {NONE: None, JACOBI: "jacobi"}
@@ -39,6 +50,7 @@ RUNS = collections.Counter()
 RATIO = {}  # problem -> {"x" | "residual": (largest deviation / twin envelope, where)}
 _MAT = {}
 _ENV = {}
+_OP = {}  # (problem, spec) -> (the engine's factor, the operator of tests/precond_ops.py over it)
 
 
 def _grid_constants():
@@ -96,14 +108,69 @@ def _device_vector(ctx, host, aligned):
 
 def _note(name, kind, ratio, where):
     old = RATIO.setdefault(name, {})
-    if ratio > old.get(kind, (0.0, ""))[0]:
+    if kind not in old or ratio > old[kind][0]:  # (a ratio of 0 - an exact iterate - is a record too)
         old[kind] = (ratio, where)
 
 
-def _steps(ctx, A, name, precond, aligned, what, zero_start=False):
-    """every k the problem keeps with check_every 1 and 4: iters, x_k and the residual against the reference"""
-    n, ent, b, x0, _, _ = _problem(name)
-    env = _envelope(name, precond, zero_start)
+# ---- the preconditioners applied by launches: the engine's own factor, and the references over it ---------------------------------
+def _engine_factor(ctx, M, spec):
+    """sets the handle M up as `spec` says and reads back what defines M^-1: G, the ILU(0) values in row order, or the Chebyshev state"""
+    if spec.kind == "fsai":
+        ctx.fsai_setup(M, spec.level)
+        return ctx.fsai_factor(M)
+    if spec.kind == "ilu0":
+        M.set_param("ilu0_order", 0)
+        ctx.ilu0_setup(M)
+        assert np.array_equal(ctx.ilu0_order(M), np.arange(M.info.nrow))
+        return ctx.ilu0_factors(M)
+    ctx.chebyshev_setup(M, degree=spec.degree, scaled=spec.scaled, lmin=spec.lmin, lmax=spec.lmax)
+    return ctx.chebyshev_info(M)
+
+
+def _same_factor(a, c):
+    return all(np.array_equal(u, v) for u, v in zip(a, c)) if isinstance(a, tuple) else np.array_equal(a, c)
+
+
+def _launched_problem(name):
+    if ("launched", name) not in _MAT:
+        n, ent, b, x0, ks = po.nonsym_problem(name, _big_n() if name == "big" else None)
+        _MAT["launched", name] = (n, ent, b, x0, ks, br.csr_arrays(n, *ent))
+    return _MAT["launched", name]
+
+
+def _launched_handle(ctx, name, spec):
+    """a CSR handle of the problem set up as `spec` says; the operator over the engine's factor is built once per (problem, spec), and
+    every later handle must hold the same factor bit for bit"""
+    n, ent, _, _, _, (rp, cc, cv) = _launched_problem(name)
+    A = ctx.csr(n, n, rp, cc, cv)
+    factor = _engine_factor(ctx, A, spec)
+    if (name, spec) not in _OP:
+        _OP[name, spec] = (factor, po.build(spec, n, ent, factor))
+    assert _same_factor(factor, _OP[name, spec][0]), f"{po.label(name, spec)}: two set-ups of the same matrix differ"
+    return A
+
+
+def _launched_envelope(name, spec, zero_start):
+    key = ("launched", name, spec, zero_start)
+    if key not in _ENV:
+        n, ent, b, x0, ks, _ = _launched_problem(name)
+        why = br.available(n)
+        if why:
+            pytest.skip(why)
+        _ENV[key] = br.Envelope(ent, n, b, np.zeros_like(x0) if zero_start else x0, ks, _OP[name, spec][1])
+    return _ENV[key]
+
+
+def _steps(ctx, A, name, precond, aligned, what, zero_start=False, spec=None):
+    """every k the problem keeps with check_every 1 and 4: iters, x_k and the residual against the reference.  spec: the problem is
+    precond_ops', the preconditioner the launched one that A was set up with (_launched_handle), the reference runs over its factor"""
+    if spec is None:
+        n, ent, b, x0, _, _ = _problem(name)
+        env = _envelope(name, precond, zero_start)
+    else:
+        n, ent, b, x0, _, _ = _launched_problem(name)
+        env = _launched_envelope(name, spec, zero_start)
+        precond, name = LAUNCHED_ID[spec.kind], po.label(name, spec)
     start = np.zeros_like(x0) if zero_start else x0
     db, keep_b = _device_vector(ctx, b, aligned)
     misses = []
@@ -155,6 +222,23 @@ def test_bicgstab_iterates_from_a_zero_start(ctx, pkg, name):
         misses += _steps(ctx, A, name, precond, aligned, "csr auto", zero_start=True)
     assert not misses, "\n".join(misses)
     RUNS["zero start"] += 1
+
+
+# ---- 1b. FSAI, ILU(0), Chebyshev: phat and shat are buffers of their own, written by apply_preconditioner -------------------------
+LAUNCHED_CASES = po.BICGSTAB_CASES
+LAUNCHED_NAMES = tuple(po.label(name, spec) for name, spec in LAUNCHED_CASES)
+
+
+@pytest.mark.parametrize("name,spec", LAUNCHED_CASES, ids=lambda v: v if isinstance(v, str) else v.kind)
+def test_bicgstab_iterates_under_the_preconditioners_applied_by_launches(ctx, pkg, name, spec):
+    """the reference and its twins apply the factor read back from the handle, so a deviation is the solver's: the two applications
+    per iteration into phat and shat, the half, update and direction kernels reading them, 16-byte and 8-byte x and b, both starts"""
+    A = _launched_handle(ctx, name, spec)
+    misses = []
+    for aligned, zero_start in ((True, False), (False, False), (True, True), (False, True)) if name != "big" else ((False, False),):
+        misses += _steps(ctx, A, name, None, aligned, "csr auto", zero_start, spec)
+    assert not misses, "\n".join(misses)
+    RUNS["launched"] += 1
 
 
 # ---- 2. forced product kernels ---------------------------------------------------------------------------------------------------------
@@ -393,20 +477,21 @@ def test_torch_solve_is_the_engine_solve_bit_for_bit():
 def test_every_case_ran():
     """every problem, kernel and format of the cases above ran, and no ratio lies above the gate"""
     expect = {"csr": len(CSR_CASES), "zero start": 2, "kernels": len(KERNEL_CASES), "formats": len(FORMATS), "convergence": 2, "stopping": 1,
-              "refusals": 1, "bits": 2, "state": 1 + len(FORMATS), "memory": 1, "torch": 1}
+              "launched": len(LAUNCHED_CASES), "refusals": 1, "bits": 2, "state": 1 + len(FORMATS), "memory": 1, "torch": 1}
     if any(RUNS[f] != c for f, c in expect.items()):
         pytest.skip(f"the coverage check needs every test of this module (ran {dict(RUNS)}, expected {expect})")
-    assert set(RATIO) == set(br.PROBLEMS), sorted(set(br.PROBLEMS) - set(RATIO))
+    names = br.PROBLEMS + LAUNCHED_NAMES
+    assert set(RATIO) == set(names), sorted(set(names) ^ set(RATIO))
     lines = ["# spmv_bicgstab iterate by iterate (tests/test_gpu_bicgstab.py): the largest deviation of the GPU's x_k and of its ||r_k|| / ||b||",
              "# from the np.longdouble recurrence, in units of the float64 twins' own largest deviation at that k (the gate is 8).",
              "# problem | x ratio | residual ratio | where the x ratio was largest"]
-    for name in br.PROBLEMS:
+    for name in names:
         r = RATIO[name]
-        lines.append(f"{name:12s}  x {r['x'][0]:6.3f}  residual {r['residual'][0]:6.3f}  ({r['x'][1]})")
+        lines.append(f"{name:18s}  x {r['x'][0]:6.3f}  residual {r['residual'][0]:6.3f}  ({r['x'][1]})")
     print("\n".join(lines))
     out = os.environ.get("SPMV_BICGSTAB_RATIOS")
     if out:
         with open(out, "w") as f:
             f.write("\n".join(lines) + "\n")
-    for name in br.PROBLEMS:
+    for name in names:
         assert all(RATIO[name][kind][0] <= br.F for kind in RATIO[name]), (name, RATIO[name])

@@ -15,7 +15,16 @@ one whose size is odd and beyond two sweeps of the vector kernels' largest grid 
 wide basis, a 4099-row tridiagonal matrix far from converged after 66 iterations, at m = 64 (k = 16, 17, 33: the edges of the dots
 kernel's tiles of 8 vectors; 64, 65, 66: a full basis and the restart behind it), m = 8 and m = 1.  CSR under AUTO, plain and with
 Jacobi, and forced VECTOR, SCALAR and PANEL; COO (entries shuffled), CSC, ELL and DIA handles of the band; x and b 256-byte aligned
-(the 16-byte kernels) and 8 bytes past a 16-byte boundary (the 8-byte kernels); a random start and x0 = 0.  Then the rotation that
+(the 16-byte kernels) and 8 bytes past a 16-byte boundary (the 8-byte kernels); a random start and x0 = 0.
+
+The preconditioners applied by launches - FSAI, ILU(0) in row order, Chebyshev with given bounds - are stepped through in the same
+way (tests/precond_ops.py: GMRES_CASES): the factor is read back from the handle, and the reference and its six twins apply that factor
+as a fixed linear operator in their own arithmetic, so a deviation belongs to the solver - z = M^-1 v_j per column, V y into the work
+vector, M^-1 of it added to x by the 16-byte and the 8-byte kernel, the end of a cycle mid-solve under m = 4.  1 x 1 .. 3 x 3, the
+33 x 33 Laplacian (n = 1089), upwind convection-diffusion on 45 x 45 (n = 2025), the band (ILU(0)) and the large odd size; both
+alignments, both starts.  AMG alone stays at convergence only (tests/test_gpu_amg.py): its cycle has no fixed factor to read back.
+
+Then the rotation that
 breaks BiCGSTAB down, the stopping rules and special cases, refusals, convergence to 1e-10 against the true residual, ILU(0) in
 both orders against the twins' iteration counts, reproducibility bit for bit, the handle's state and the device memory before and
 after, and the torch operator.  test_every_case_ran asserts at the end that all of it ran; with SPMV_GMRES_RATIOS=<file> it also
@@ -32,10 +41,12 @@ import pytest
 import gmres_ref as gr
 import ilu0_ref as ir
 import oracle_lib as ol
+import precond_ops as po
 
 pytestmark = pytest.mark.gpu
 AUTO, VECTOR, SCALAR, PANEL = 0, 1, 3, 4
-NONE, JACOBI, SYMGS, ILU0 = 0, 1, 2, 3
+NONE, JACOBI, SYMGS, ILU0, CHEBYSHEV, AMG, FSAI = 0, 1, 2, 3, 4, 5, 6
+LAUNCHED_ID = {"ilu0": ILU0, "chebyshev": CHEBYSHEV, "fsai": FSAI}
 INVALID, UNSUPPORTED = -1, -5
 CHECK_EVERY = (1, 4)
 PRECOND_NAME = {NONE: None, JACOBI: "jacobi"}
@@ -44,6 +55,7 @@ RUNS = collections.Counter()
 RATIO = {}  # problem -> {"x" | "residual": (largest deviation / twin envelope, where)}
 _MAT = {}
 _ENV = {}
+_OP = {}  # (problem, spec) -> (the engine's factor, the operator of tests/precond_ops.py over it)
 
 
 def _grid_constants():
@@ -112,10 +124,65 @@ def _note(name, kind, ratio, where):
         old[kind] = (ratio, where)
 
 
-def _steps(ctx, A, name, m, precond, aligned, what, zero_start=False):
-    """every k the problem keeps with check_every 1 and 4: iters, x_k and the residual against the reference"""
-    n, ent, b, x0, _, _ = _problem(name)
-    env = _envelope(name, m, precond, zero_start)
+# ---- the preconditioners applied by launches: the engine's own factor, and the references over it ---------------------------------
+def _engine_factor(ctx, M, spec):
+    """sets the handle M up as `spec` says and reads back what defines M^-1: G, the ILU(0) values in row order, or the Chebyshev state"""
+    if spec.kind == "fsai":
+        ctx.fsai_setup(M, spec.level)
+        return ctx.fsai_factor(M)
+    if spec.kind == "ilu0":
+        M.set_param("ilu0_order", 0)
+        ctx.ilu0_setup(M)
+        assert np.array_equal(ctx.ilu0_order(M), np.arange(M.info.nrow))
+        return ctx.ilu0_factors(M)
+    ctx.chebyshev_setup(M, degree=spec.degree, scaled=spec.scaled, lmin=spec.lmin, lmax=spec.lmax)
+    return ctx.chebyshev_info(M)
+
+
+def _same_factor(a, c):
+    return all(np.array_equal(u, v) for u, v in zip(a, c)) if isinstance(a, tuple) else np.array_equal(a, c)
+
+
+def _launched_problem(name):
+    if ("launched", name) not in _MAT:
+        n, ent, b, x0, ks = po.nonsym_problem(name, _big_n() if name == "big" else None)
+        _MAT["launched", name] = (n, ent, b, x0, ks, gr.csr_arrays(n, *ent))
+    return _MAT["launched", name]
+
+
+def _launched_handle(ctx, name, spec):
+    """a CSR handle of the problem set up as `spec` says; the operator over the engine's factor is built once per (problem, spec), and
+    every later handle must hold the same factor bit for bit"""
+    n, ent, _, _, _, (rp, cc, cv) = _launched_problem(name)
+    A = ctx.csr(n, n, rp, cc, cv)
+    factor = _engine_factor(ctx, A, spec)
+    if (name, spec) not in _OP:
+        _OP[name, spec] = (factor, po.build(spec, n, ent, factor))
+    assert _same_factor(factor, _OP[name, spec][0]), f"{po.label(name, spec)}: two set-ups of the same matrix differ"
+    return A
+
+
+def _launched_envelope(name, m, spec, zero_start):
+    key = ("launched", name, m, spec, zero_start)
+    if key not in _ENV:
+        n, ent, b, x0, ks, _ = _launched_problem(name)
+        why = gr.available(n)
+        if why:
+            pytest.skip(why)
+        _ENV[key] = gr.Envelope(ent, n, b, np.zeros_like(x0) if zero_start else x0, ks, m, _OP[name, spec][1])
+    return _ENV[key]
+
+
+def _steps(ctx, A, name, m, precond, aligned, what, zero_start=False, spec=None):
+    """every k the problem keeps with check_every 1 and 4: iters, x_k and the residual against the reference.  spec: the problem is
+    precond_ops', the preconditioner the launched one that A was set up with (_launched_handle), the reference runs over its factor"""
+    if spec is None:
+        n, ent, b, x0, _, _ = _problem(name)
+        env = _envelope(name, m, precond, zero_start)
+    else:
+        n, ent, b, x0, _, _ = _launched_problem(name)
+        env = _launched_envelope(name, m, spec, zero_start)
+        precond, name = LAUNCHED_ID[spec.kind], po.label(name, spec)
     start = np.zeros_like(x0) if zero_start else x0
     db, keep_b = _device_vector(ctx, b, aligned)
     misses = []
@@ -161,6 +228,23 @@ def test_gmres_iterates_match_the_extended_precision_recurrence(ctx, pkg, name, 
                 misses += _steps(ctx, A, name, m, precond, aligned, "csr auto", zero_start)
     assert not misses, "\n".join(misses)
     RUNS["csr"] += 1
+
+
+# ---- 1b. FSAI, ILU(0), Chebyshev: z = M^-1 v_j per column, w = V y and x += M^-1 w at the end of a cycle ----------------------------
+LAUNCHED_CASES = [(name, spec, m) for name, spec in po.GMRES_CASES for m in (gr.RESTARTS if name != "big" else (4,))]
+LAUNCHED_NAMES = tuple(po.label(name, spec) for name, spec in po.GMRES_CASES)
+
+
+@pytest.mark.parametrize("name,spec,m", LAUNCHED_CASES, ids=lambda v: v if isinstance(v, str) else v.kind if isinstance(v, tuple) else str(v))
+def test_gmres_iterates_under_the_preconditioners_applied_by_launches(ctx, pkg, name, spec, m):
+    """the reference and its twins apply the factor read back from the handle, so a deviation is the solver's: the application per
+    column, the x update through the work vector with its 16-byte and 8-byte add kernels, the end of a cycle mid-solve under m = 4"""
+    A = _launched_handle(ctx, name, spec)
+    misses = []
+    for aligned, zero_start in ((True, False), (False, False), (True, True), (False, True)) if name != "big" else ((False, False),):
+        misses += _steps(ctx, A, name, m, None, aligned, "csr auto", zero_start, spec)
+    assert not misses, "\n".join(misses)
+    RUNS["launched"] += 1
 
 
 # ---- 2. the wide basis ------------------------------------------------------------------------------------------------------------------
@@ -507,21 +591,22 @@ def test_torch_solve_is_the_engine_solve_bit_for_bit():
 # ---- 9. coverage ---------------------------------------------------------------------------------------------------------------------------
 def test_every_case_ran():
     """every problem, kernel and format of the cases above ran, and no ratio lies above the gate"""
-    expect = {"csr": len(CSR_CASES), "wide": len(gr.WIDE_KS), "kernels": len(KERNEL_CASES), "formats": len(FORMATS), "rotation": 1, "stopping": 1,
+    expect = {"csr": len(CSR_CASES), "launched": len(LAUNCHED_CASES), "wide": len(gr.WIDE_KS), "kernels": len(KERNEL_CASES), "formats": len(FORMATS), "rotation": 1, "stopping": 1,
               "refusals": 1, "convergence": 2, "ilu0": 2, "exact": 1, "bits": 2, "state": 1 + len(FORMATS), "memory": 1, "torch": 1}
     if any(RUNS[f] != c for f, c in expect.items()):
         pytest.skip(f"the coverage check needs every test of this module (ran {dict(RUNS)}, expected {expect})")
-    assert set(RATIO) == set(ALL_PROBLEMS), sorted(set(ALL_PROBLEMS) - set(RATIO))
+    names = ALL_PROBLEMS + LAUNCHED_NAMES
+    assert set(RATIO) == set(names), sorted(set(names) ^ set(RATIO))
     lines = ["# spmv_gmres iterate by iterate (tests/test_gpu_gmres.py): the largest deviation of the GPU's x_k and of its |g| / ||b||",
              "# from the np.longdouble recurrence, in units of the float64 twins' own largest deviation at that k (the gate is 8).",
              "# problem | x ratio | residual ratio | where the x ratio was largest"]
-    for name in ALL_PROBLEMS:
+    for name in names:
         r = RATIO[name]
-        lines.append(f"{name:12s}  x {r['x'][0]:6.3f}  residual {r['residual'][0]:6.3f}  ({r['x'][1]})")
+        lines.append(f"{name:18s}  x {r['x'][0]:6.3f}  residual {r['residual'][0]:6.3f}  ({r['x'][1]})")
     print("\n".join(lines))
     out = os.environ.get("SPMV_GMRES_RATIOS")
     if out:
         with open(out, "w") as f:
             f.write("\n".join(lines) + "\n")
-    for name in ALL_PROBLEMS:
+    for name in names:
         assert all(RATIO[name][kind][0] <= gr.F for kind in RATIO[name]), (name, RATIO[name])

@@ -17,11 +17,16 @@ Laplacian itself; and the band at a size that is odd and beyond two sweeps of th
 SCALAR and PANEL; COO (entries shuffled), CSC, ELL and DIA handles of the band; x and b 256-byte aligned (the 16-byte kernels) and
 8 bytes past a 16-byte boundary (the 8-byte kernels); a random start and x0 = 0.
 
-The preconditioners applied by launches (Chebyshev on the saddle point's P, FSAI and AMG on the Laplacian) have no twin here -
-tests/test_gpu_gmres.py states none for them either - so those cases are held to CONVERGENCE ONLY: the solve ends within the
-tolerance it reports, and the true 2-norm residual computed on the host in np.longdouble is within F sqrt(cond(P)) of it (the
-M^-1 norm the solver stops on and the 2-norm differ by at most the root of M's condition number, and M^-1 stands between a multiple
-of I and P^-1).
+FSAI and Chebyshev (given bounds) of a separate positive definite handle P are stepped through in the same way (tests/precond_ops.py:
+SYM_CASES): the factor is read back from P, and the reference and its six twins apply that factor as a fixed linear operator in their
+own arithmetic, so a deviation belongs to the solver - b.M^-1 b and r1.y of the set-up, launch 3 without y, the application, r2.y
+with the rotation, the pointers rotating around a y of its own.  1 x 1 .. 3 x 3 with the 1-D Laplacian as P, the shifted Laplacian,
+the saddle point, and the large odd size; both alignments, both starts.  ILU(0) is refused by this solver.
+
+AMG has no fixed factor to read back and no twin here, so it - and, kept beside it, Chebyshev on the saddle point's P and FSAI on the
+Laplacian run to a tolerance with the default set-ups - is held to CONVERGENCE ONLY: the solve ends within the tolerance it reports,
+and the true 2-norm residual computed on the host in np.longdouble is within F sqrt(cond(P)) of it (the M^-1 norm the solver stops on
+and the 2-norm differ by at most the root of M's condition number, and M^-1 stands between a multiple of I and P^-1).
 
 Then convergence to 1e-10 against the true residual (with spmv_cg answering SPMV_ERR_INVALID on the same systems), the stopping rules
 and special cases, refusals, a preconditioner that is not positive definite, reproducibility bit for bit, the handles' state and the
@@ -39,6 +44,7 @@ import pytest
 
 import minres_ref as mr
 import oracle_lib as ol
+import precond_ops as po
 from cgls_ref import rect
 
 pytestmark = pytest.mark.gpu
@@ -47,10 +53,12 @@ NONE, JACOBI, SYMGS, ILU0, CHEBYSHEV, AMG, FSAI = 0, 1, 2, 3, 4, 5, 6
 INVALID, UNSUPPORTED = -1, -5
 CHECK_EVERY = (1, 4)
 PRECOND_NAME = {NONE: None, JACOBI: "jacobi"}
+LAUNCHED_ID = {"chebyshev": CHEBYSHEV, "fsai": FSAI}
 RUNS = collections.Counter()
 RATIO = {}  # problem -> {"x" | "residual": (largest deviation / twin envelope, where)}
 _MAT = {}
 _ENV = {}
+_OP = {}  # (problem, spec) -> (the engine's factor, the operator of tests/precond_ops.py over it)
 
 
 def _grid_constants():
@@ -107,7 +115,7 @@ def _device_vector(ctx, host, aligned):
 
 def _note(name, kind, ratio, where):
     old = RATIO.setdefault(name, {})
-    if ratio > old.get(kind, (0.0, ""))[0]:
+    if kind not in old or ratio > old[kind][0]:  # (a ratio of 0 - an exact iterate - is a record too)
         old[kind] = (ratio, where)
 
 
@@ -131,10 +139,66 @@ def _precond_handle(ctx, name, A):
     return A if p.p_entries is p.entries else ctx.csr(p.n, p.n, *_sorted_csr(p.n, p.p_entries))
 
 
-def _steps(ctx, A, P, name, precond, aligned, what, zero_start=False):
-    """every k the problem keeps with check_every 1 and 4: iters, x_k and the residual against the reference"""
-    p = _problem(name)
-    env = _envelope(name, precond, zero_start)
+# ---- the preconditioners applied by launches: the engine's own factor, and the references over it ---------------------------------
+def _engine_factor(ctx, M, spec):
+    """sets the handle M up as `spec` says and reads back what defines M^-1: G, the ILU(0) values in row order, or the Chebyshev state"""
+    if spec.kind == "fsai":
+        ctx.fsai_setup(M, spec.level)
+        return ctx.fsai_factor(M)
+    if spec.kind == "ilu0":
+        M.set_param("ilu0_order", 0)
+        ctx.ilu0_setup(M)
+        assert np.array_equal(ctx.ilu0_order(M), np.arange(M.info.nrow))
+        return ctx.ilu0_factors(M)
+    ctx.chebyshev_setup(M, degree=spec.degree, scaled=spec.scaled, lmin=spec.lmin, lmax=spec.lmax)
+    return ctx.chebyshev_info(M)
+
+
+def _same_factor(a, c):
+    return all(np.array_equal(u, v) for u, v in zip(a, c)) if isinstance(a, tuple) else np.array_equal(a, c)
+
+
+def _launched_problem(name):
+    if ("launched", name) not in _MAT:
+        _MAT["launched", name] = po.sym_problem(name, _big_n() if name == "big" else None)
+    return _MAT["launched", name]
+
+
+def _launched_handles(ctx, name, spec):
+    """(A, P): the system and, ALWAYS a handle of its own, the positive definite matrix the preconditioner is built from, set up as
+    `spec` says; the operator over the engine's factor is built once per (problem, spec), and every later P must hold the same
+    factor bit for bit"""
+    p = _launched_problem(name)
+    A = ctx.csr(p.n, p.n, *_sorted_csr(p.n, p.entries))
+    P = ctx.csr(p.n, p.n, *_sorted_csr(p.n, p.p_entries))
+    factor = _engine_factor(ctx, P, spec)
+    if (name, spec) not in _OP:
+        _OP[name, spec] = (factor, po.build(spec, p.n, p.p_entries, factor))
+    assert _same_factor(factor, _OP[name, spec][0]), f"{po.label(name, spec)}: two set-ups of the same matrix differ"
+    return A, P
+
+
+def _launched_envelope(name, spec, zero_start):
+    key = ("launched", name, spec, zero_start)
+    if key not in _ENV:
+        p = _launched_problem(name)
+        why = mr.available(p.n)
+        if why:
+            pytest.skip(why)
+        _ENV[key] = mr.Envelope(p.entries, p.n, p.b, np.zeros_like(p.x0) if zero_start else p.x0, p.ks, p.shift, _OP[name, spec][1])
+    return _ENV[key]
+
+
+def _steps(ctx, A, P, name, precond, aligned, what, zero_start=False, spec=None):
+    """every k the problem keeps with check_every 1 and 4: iters, x_k and the residual against the reference.  spec: the problem is
+    precond_ops', the preconditioner the launched one that P was set up with (_launched_handles), the reference runs over its factor"""
+    if spec is None:
+        p = _problem(name)
+        env = _envelope(name, precond, zero_start)
+    else:
+        p = _launched_problem(name)
+        env = _launched_envelope(name, spec, zero_start)
+        precond, name = LAUNCHED_ID[spec.kind], po.label(name, spec)
     start = np.zeros_like(p.x0) if zero_start else p.x0
     db, keep_b = _device_vector(ctx, p.b, aligned)
     misses = []
@@ -185,6 +249,23 @@ def test_minres_iterates_from_a_zero_start(ctx, pkg, name):
         misses += _steps(ctx, A, P, name, JACOBI, False, "csr auto", zero_start=True)
     assert not misses, "\n".join(misses)
     RUNS["zero start"] += 1
+
+
+# ---- 1b. FSAI and Chebyshev of a separate handle P: y is a buffer of its own, written by apply_preconditioner ----------------------
+LAUNCHED_CASES = po.SYM_CASES
+LAUNCHED_NAMES = tuple(po.label(name, spec) for name, spec in LAUNCHED_CASES)
+
+
+@pytest.mark.parametrize("name,spec", LAUNCHED_CASES, ids=lambda v: v if isinstance(v, str) else v.kind)
+def test_minres_iterates_under_the_preconditioners_applied_by_launches(ctx, pkg, name, spec):
+    """the reference and its twins apply the factor read back from P, so a deviation is the solver's: the set-up's b.M^-1 b and r1.y,
+    launch 3 without y, the application, r2.y with the rotation, the pointers rotating around y; 16-byte and 8-byte x and b, both starts"""
+    A, P = _launched_handles(ctx, name, spec)
+    misses = []
+    for aligned, zero_start in ((True, False), (False, False), (True, True), (False, True)) if name != "big" else ((False, False),):
+        misses += _steps(ctx, A, P, name, None, aligned, "csr auto", zero_start, spec)
+    assert not misses, "\n".join(misses)
+    RUNS["launched steps"] += 1
 
 
 # ---- 2. forced product kernels ---------------------------------------------------------------------------------------------------------
@@ -293,8 +374,8 @@ BY_LAUNCHES_CASES = [("saddle", CHEBYSHEV), ("shifted", FSAI), ("shifted", AMG)]
 
 @pytest.mark.parametrize("name,precond", BY_LAUNCHES_CASES, ids=lambda v: str(v))
 def test_minres_converges_under_the_preconditioners_applied_by_launches(ctx, pkg, name, precond):
-    """convergence only (the module's docstring says why): the separate handle P, set up on first use with the defaults; the solve
-    ends within the tolerance it reports, in fewer iterations than max_iter, from both alignments with the same count, and the true
+    """convergence only (AMG has no twin; the other two are stepped through above and run to a tolerance here): the separate handle
+    P, set up on first use with the defaults; the solve ends within the tolerance it reports, in fewer iterations than max_iter, from both alignments with the same count, and the true
     2-norm residual is within F sqrt(cond(P)) of the tolerance"""
     rel_tol, max_iter = 1e-10, 20000
     p = _problem(name)
@@ -548,21 +629,22 @@ def test_torch_solve_symmetric_is_the_engine_solve_bit_for_bit():
 def test_every_case_ran():
     """every problem, kernel and format of the cases above ran, and no ratio lies above the gate"""
     expect = {"csr": len(CSR_CASES), "zero start": 2, "kernels": len(KERNEL_CASES), "formats": len(FORMATS), "convergence": 3,
-              "by launches": len(BY_LAUNCHES_CASES), "stopping": 1, "refusals": 1, "not definite": 1, "bits": 2, "state": 1 + len(FORMATS), "memory": 1,
+              "by launches": len(BY_LAUNCHES_CASES), "launched steps": len(LAUNCHED_CASES), "stopping": 1, "refusals": 1, "not definite": 1, "bits": 2, "state": 1 + len(FORMATS), "memory": 1,
               "torch": 1}
     if any(RUNS[f] != c for f, c in expect.items()):
         pytest.skip(f"the coverage check needs every test of this module (ran {dict(RUNS)}, expected {expect})")
-    assert set(RATIO) == set(mr.PROBLEMS), sorted(set(mr.PROBLEMS) - set(RATIO))
+    names = mr.PROBLEMS + LAUNCHED_NAMES
+    assert set(RATIO) == set(names), sorted(set(names) ^ set(RATIO))
     lines = ["# spmv_minres iterate by iterate (tests/test_gpu_minres.py): the largest deviation of the GPU's x_k and of its phibar_k / beta_b",
              "# from the np.longdouble recurrence, in units of the float64 twins' own largest deviation at that k (the gate is 8).",
              "# problem | x ratio | residual ratio | where the x ratio was largest"]
-    for name in mr.PROBLEMS:
+    for name in names:
         r = RATIO[name]
-        lines.append(f"{name:12s}  x {r['x'][0]:6.3f}  residual {r['residual'][0]:6.3f}  ({r['x'][1]})")
+        lines.append(f"{name:18s}  x {r['x'][0]:6.3f}  residual {r['residual'][0]:6.3f}  ({r['x'][1]})")
     print("\n".join(lines))
     out = os.environ.get("SPMV_MINRES_RATIOS")
     if out:
         with open(out, "w") as f:
             f.write("\n".join(lines) + "\n")
-    for name in mr.PROBLEMS:
+    for name in names:
         assert all(RATIO[name][kind][0] <= mr.F for kind in RATIO[name]), (name, RATIO[name])

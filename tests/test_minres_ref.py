@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import minres_ref as mr
+import precond_ops as po
 
 SMALL = ("n1", "n2", "n3")
 MID = ("r33", "r4097", "band4099", "saddle", "shifted")
@@ -176,3 +177,71 @@ def test_the_mpmath_fallback_is_the_same_reference():
         for k in p.ks:
             assert max(abs(float(a) - float(c)) for a, c in zip(runs["mp"][k][0], runs["ld"][k][0])) <= 1e-15 * max(1.0, float(np.max(np.abs(runs["ld"][k][0]))))
             assert abs(runs["mp"][k][1] - runs["ld"][k][1]) <= 1e-15
+
+
+# ---- the preconditioners applied by launches (tests/precond_ops.py): FSAI and Chebyshev of a separate positive definite P ----------
+LAUNCHED = [(name, spec) for name, spec in po.SYM_CASES if name != "big"]  # (big: a million rows in np.longdouble, the GPU file's)
+
+
+@pytest.fixture(scope="module")
+def launched():
+    cache = {}
+
+    def get(name, spec, zero_start=False):
+        key = (name, spec, zero_start)
+        if key not in cache:
+            p = po.sym_problem(name)
+            op = cache.setdefault((name, spec), po.build(spec, p.n, p.p_entries))
+            cache[key] = mr.Envelope(p.entries, p.n, p.b, np.zeros_like(p.x0) if zero_start else p.x0, p.ks, p.shift, op)
+        return cache[key], cache[name, spec]
+
+    return get
+
+
+@pytest.mark.parametrize("name,spec", LAUNCHED, ids=lambda v: v if isinstance(v, str) else v.kind)
+@pytest.mark.parametrize("zero_start", (False, True))
+def test_every_twin_lies_inside_the_gate_of_the_other_five_under_a_launched_preconditioner(launched, name, spec, zero_start):
+    p = po.sym_problem(name)
+    _skip_unless_available(p.n)
+    env, op = launched(name, spec, zero_start)
+    assert len(env.dropped) <= (mr.MAX_DROPPED if p.n > 3 else 0) and env.ks == p.ks[: len(env.ks)] and env.ks, (name, spec, env.dropped)
+    for k in env.ks:
+        assert len(env.twin_dev[k]) == len(mr.DOT_ORDERS) * len(mr.ROW_ORDERS)
+    worst = [max(env.leave_one_out(k, what) for k in env.ks) for what in (0, 1)]
+    spread = [(min(env.envelope(k, what) for k in env.ks), max(env.envelope(k, what) for k in env.ks)) for what in (0, 1)]
+    # the reference's x at the largest kept k has the residual its recurrence reports: phibar is the M^-1 norm of the true residual
+    k = env.ks[-1]
+    kind = mr._hp_kind(p.n)
+    b = mr._conv(p.b, kind)
+    r = b - (mr.Operator(p.entries, (p.n, p.n), kind).mv(env.ref_x[k]) - mr._conv(np.array([p.shift]), kind)[0] * env.ref_x[k])
+    true = float(mr._sqrt(mr._dot(r, op.apply(r, kind)) / mr._dot(b, op.apply(b, kind)), kind))
+    print(f"{po.label(name, spec)} {'x0=0' if zero_start else 'random start'}: kept {env.ks}, dropped {env.dropped}, phibar / beta_b before the last "
+          f"k {env.resid_hist[k - 1]:.2e}; twin envelope x {spread[0][0]:.1e} .. {spread[0][1]:.1e}, residual {spread[1][0]:.1e} .. "
+          f"{spread[1][1]:.1e}; leave-one-out x {worst[0]:.2f}, residual {worst[1]:.2f}; true residual at k = {k} {true:.3e}, reported {env.ref_resid[k]:.3e}")
+    assert worst[0] <= mr.F and worst[1] <= mr.F, (name, spec, worst)
+    assert worst[0] <= mr.OBSERVED_LEAVE_ONE_OUT_LAUNCHED["x"] * 2 and worst[1] <= mr.OBSERVED_LEAVE_ONE_OUT_LAUNCHED["residual"] * 2, "the recorded figures moved"
+    assert abs(true - env.ref_resid[k]) <= 1e-12 * max(env.resid_hist[0], 1.0), (name, spec, k, true, env.ref_resid[k])
+
+
+LAUNCHED_MUTATION_CASES = [("shifted", po.FSAI2), ("saddle", po.CHEB4)]
+
+
+@pytest.mark.parametrize("name,spec", LAUNCHED_MUTATION_CASES, ids=lambda v: v if isinstance(v, str) else v.kind)
+@pytest.mark.parametrize("mutate", mr.LAUNCHED_MUTATIONS)
+def test_the_gate_is_below_what_a_wrong_launch_sequence_does(launched, name, spec, mutate):
+    """the mutations that need a y of its own: each leaves a gate at some kept k by a factor above 1000 - x's, but for beta_b from b.b,
+    which moves the returned residual alone"""
+    p = po.sym_problem(name)
+    _skip_unless_available(p.n)
+    env, op = launched(name, spec)
+    with np.errstate(invalid="ignore"):  # (a stale y makes r2.y negative in the end: the iterates behind it are NaN and count as unseen)
+        out, _ = mr.run_minres(mr.Operator(p.entries, (p.n, p.n), "f64"), p.b, p.x0, env.ks, p.shift, op, mutate=mutate)
+    if mutate == "beta_b_bb":
+        assert all(env.x_dev(k, out[k][0]) <= env.gate(k) for k in env.ks), "beta_b does not enter x"
+        ratio = {k: env.resid_dev(k, out[k][1]) / env.gate_resid(k) for k in env.ks}
+    else:
+        ratio = {k: env.x_dev(k, out[k][0]) / env.gate(k) for k in env.ks}
+    seen = [k for k in env.ks if ratio[k] > 1]
+    print(f"mutation {mutate:9s} on {po.label(name, spec)}: first seen at k = {seen[0] if seen else None}, deviation / gate there "
+          f"{ratio[seen[0]] if seen else 0:.1e}")
+    assert seen and ratio[seen[0]] > 1000, (mutate, ratio)
