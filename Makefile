@@ -18,7 +18,7 @@ all: engine host oracle
 
 engine: $(LIBDIR)/libspmv_hip.so
 
-$(OBJDIR)/%.o: $(CSRC)/%.hip $(CSRC)/common.hpp $(CSRC)/wave.hpp $(CSRC)/solver_common.hpp $(CSRC)/solver_host.hpp $(CSRC)/precond.hpp $(CSRC)/placement_math.hpp $(CSRC)/panel_groups.hpp $(CSRC)/panel_settings.hpp $(CSRC)/ell_settings.hpp $(CSRC)/split_rows.hpp $(CSRC)/tri_levels.hpp $(CSRC)/sorted_runs.hpp $(CSRC)/spgemm_settings.hpp $(CSRC)/reorder_settings.hpp $(CSRC)/amg_sa_settings.hpp $(CSRC)/small_dense.hpp $(CSRC)/bsr_settings.hpp $(CSRC)/fsai_settings.hpp $(CSRC)/csr_f32_settings.hpp include/spmv_abi.h
+$(OBJDIR)/%.o: $(CSRC)/%.hip $(CSRC)/common.hpp $(CSRC)/wave.hpp $(CSRC)/solver_common.hpp $(CSRC)/solver_host.hpp $(CSRC)/precond.hpp $(CSRC)/placement_math.hpp $(CSRC)/panel_groups.hpp $(CSRC)/panel_settings.hpp $(CSRC)/ell_settings.hpp $(CSRC)/split_rows.hpp $(CSRC)/tri_levels.hpp $(CSRC)/sorted_runs.hpp $(CSRC)/spgemm_settings.hpp $(CSRC)/reorder_settings.hpp $(CSRC)/amg_sa_settings.hpp $(CSRC)/small_dense.hpp $(CSRC)/bsr_settings.hpp $(CSRC)/fsai_settings.hpp $(CSRC)/csr_f32_settings.hpp $(CSRC)/sddmm_settings.hpp include/spmv_abi.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -100,6 +100,9 @@ SIGNATURES = {
     "spmv_apply_timed": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _f64p]),
     "spmv_apply_multi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32]),
     "spmv_apply_multi_timed": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _f64p]),
+    "spmv_sddmm": (C.c_int, [_vp, _vp, C.c_int32, C.c_double, _vp, _vp, C.c_double, _vp]),
+    "spmv_sddmm_timed": (C.c_int, [_vp, _vp, C.c_int32, C.c_double, _vp, _vp, C.c_double, _vp, C.c_int32, _f64p]),
+    "spmv_csr_with_values": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "spmv_apply_transpose": (C.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_apply_transpose_timed": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _f64p]),
     "spmv_mat_transpose_setup": (C.c_int, [_vp]),
@@ -478,6 +481,27 @@ class Context:
         ms = C.c_double(0.0)
         _check(self._lib.spmv_apply_multi_timed(self.h, A.h, k, X.h, Y.h, 1 if overwrite else 0, reps, C.byref(ms)))
         return ms.value
+
+    def sddmm(self, A: "Matrix", U: "Vector", V: "Vector", k: int, out: "Vector", alpha: float = 1.0, beta: float = 0.0) -> None:
+        """out[e] = alpha * U[row(e), :] . V[col(e), :] + beta * out[e] for every stored entry e of the CSR handle A (spmv_sddmm),
+        asynchronous.  A gives the pattern only; U and V are row-major (nrow, k) and (ncol, k) as apply_multi's, out has nnz entries
+        in A's entry order.  beta = 0: out is not read"""
+        _check(self._lib.spmv_sddmm(self.h, A.h, k, alpha, U.h, V.h, beta, out.h))
+
+    def sddmm_timed(self, A: "Matrix", U: "Vector", V: "Vector", k: int, out: "Vector", reps: int, alpha: float = 1.0, beta: float = 0.0) -> float:
+        """`reps` back-to-back sddmm between two device events; mean milliseconds per call"""
+        ms = C.c_double(0.0)
+        _check(self._lib.spmv_sddmm_timed(self.h, A.h, k, alpha, U.h, V.h, beta, out.h, reps, C.byref(ms)))
+        return ms.value
+
+    def csr_with_values(self, A: "Matrix", values: "Vector") -> "Matrix":
+        """a CSR handle over A's row_ptr / col_ind and `values`' storage (spmv_csr_with_values): nothing is copied, A and the vector
+        are kept alive by the new handle's Python object"""
+        h = _vp()
+        _check(self._lib.spmv_csr_with_values(self.h, A.h, values.h, C.byref(h)))
+        m = Matrix(self, h)
+        m._keep = (A, values)
+        return m
 
     def apply_transpose(self, A: "Matrix", x: "Vector", y: "Vector") -> None:
         """y += A^T x, asynchronous: x has nrow entries (a shard: its rows), y ncol.  The first call builds the handle's transposed

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "sddmm_settings.hpp"
 #include "solver_host.hpp"
 
 namespace spmv
@@ -1226,6 +1227,63 @@ int spmv_apply_multi_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const sp
     SPMV_TRY(time_launches(ctx, reps, [&] { return spmm_apply(ctx, A, k, X->d, Y->d, overwrite != 0); }, &ms));
     *ms_per_apply = ms;
     return SPMV_OK;
+}
+
+// ---- dense products sampled on a CSR pattern: out = alpha * (U V^T)|pattern + beta * out (kernels_sddmm.hip) ------------------
+// Every check is made before the device is touched, so that they hold (and are tested) on a machine without one.
+static bool vec_overlap(const spmv_vec* p, const spmv_vec* q)
+{
+    return p->n > 0 && q->n > 0 && !(p->d + p->n <= q->d || q->d + q->n <= p->d);
+}
+
+static int check_sddmm_args(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* U, const spmv_vec* V, spmv_vec* out)
+{
+    SPMV_REQUIRE(ctx && A && U && V && out, "spmv_sddmm: null argument");
+    SPMV_REQUIRE(k >= 1 && k <= kSddmmMaxK, "spmv_sddmm: k = %d, must be in [1, %d]", k, kSddmmMaxK);
+    if (A->format != SPMV_FMT_CSR) SPMV_FAIL(SPMV_ERR_UNSUPPORTED, "spmv_sddmm: CSR patterns only (format %d)", A->format);
+    SPMV_REQUIRE(U->n == (int64_t)A->nrow * k, "spmv_sddmm: U has %lld entries, nrow * k = %d * %d", (long long)U->n, A->nrow, k);
+    SPMV_REQUIRE(V->n == (int64_t)A->ncol * k, "spmv_sddmm: V has %lld entries, ncol * k = %d * %d", (long long)V->n, A->ncol, k);
+    SPMV_REQUIRE(out->n == A->nnz, "spmv_sddmm: out has %lld entries, the pattern %lld", (long long)out->n, (long long)A->nnz);
+    SPMV_REQUIRE(!vec_overlap(out, U) && !vec_overlap(out, V), "spmv_sddmm: out must not overlap U or V");
+    SPMV_REQUIRE(A->a && (A->nnz == 0 || A->b), "spmv_sddmm: this handle gave up its CSR arrays (panel_keep_csr = 0)");
+    return SPMV_OK;
+}
+
+int spmv_sddmm(spmv_ctx* ctx, const spmv_mat* A, int32_t k, double alpha, const spmv_vec* U, const spmv_vec* V, double beta,
+               spmv_vec* out)
+{
+    SPMV_TRY(check_sddmm_args(ctx, A, k, U, V, out));
+    SPMV_TRY(use_device(ctx));
+    return sddmm_apply(ctx, A, k, alpha, U->d, V->d, beta, out->d);
+}
+
+int spmv_sddmm_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t k, double alpha, const spmv_vec* U, const spmv_vec* V, double beta,
+                     spmv_vec* out, int32_t reps, double* ms_per_call)
+{
+    SPMV_TRY(check_sddmm_args(ctx, A, k, U, V, out));
+    SPMV_REQUIRE(reps > 0 && ms_per_call, "spmv_sddmm_timed: reps=%d", reps);
+    SPMV_TRY(use_device(ctx));
+    float ms = 0.f;
+    SPMV_TRY(time_launches(ctx, reps, [&] { return sddmm_apply(ctx, A, k, alpha, U->d, V->d, beta, out->d); }, &ms));
+    *ms_per_call = ms;
+    return SPMV_OK;
+}
+
+// a CSR handle over A's own row_ptr / col_ind and the vector's storage as its values: spmv_csr_wrap_device over pointers the engine
+// already holds (a shard stays a shard); analysed like any wrapped handle
+int spmv_csr_with_values(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* values, spmv_mat** out)
+{
+    SPMV_REQUIRE(ctx && A && values && out, "spmv_csr_with_values: null argument");
+    SPMV_REQUIRE(A->format == SPMV_FMT_CSR && A->a && (A->nnz == 0 || A->b),
+                 "spmv_csr_with_values: A is not a CSR handle with its arrays (format %d; panel_keep_csr = 0 released them?)", A->format);
+    SPMV_REQUIRE(values->n == A->nnz, "spmv_csr_with_values: values has %lld entries, the pattern %lld", (long long)values->n,
+                 (long long)A->nnz);
+    SPMV_TRY(use_device(ctx));
+    plan_arm arm(ctx);
+    spmv_mat* m = nullptr;
+    SPMV_TRY(wrap(ctx, SPMV_FMT_CSR, A->nrow, A->ncol, A->nnz, 0, A->a, A->b, values->d, &m));
+    m->row_begin = A->row_begin;
+    return finish(m, out);
 }
 
 // ---- the reference's own call shape: host vectors in, host vector out ---------------------------------------------------------

@@ -577,6 +577,8 @@ int  csr_split_threshold(const spmv_mat* m);
 int  csr_split_long_rows_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 // kernels_spmm.hip: Y += A*X (Y = A*X) for k row-major vectors, CSR and ELL handles, over the handle's own arrays
 int spmm_apply(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const double* X, double* Y, bool overwrite);
+// kernels_sddmm.hip: out = alpha * (U V^T sampled on A's CSR pattern) + beta * out; U nrow x k, V ncol x k row-major, out nnz entries
+int sddmm_apply(spmv_ctx* ctx, const spmv_mat* A, int32_t k, double alpha, const double* U, const double* V, double beta, double* out);
 // kernels_misc.hip (CSC, DIA, BLAS-1, fill)
 int csc_apply(spmv_ctx* ctx, const spmv_mat* A, const double* x, double* y);
 int csc_analyse(spmv_mat* m);

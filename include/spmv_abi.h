@@ -449,6 +449,40 @@ int spmv_apply_multi(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec
 int spmv_apply_multi_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t k, const spmv_vec* X, spmv_vec* Y, int32_t overwrite,
                            int32_t reps, double* ms_per_apply);
 
+/* ---- dense products sampled on a CSR pattern (SDDMM), and a handle over their result ---------------------------------------------
+ * spmv_sddmm:   out[e] = alpha * sum_{c < k} U[row(e), c] * V[col(e), c] + beta * out[e]   for every stored entry e of A.
+ * A supplies the PATTERN only: its values are never read.  CSR handles (uploaded, wrapped, row shards: U then has the shard's rows);
+ * every other format: SPMV_ERR_UNSUPPORTED, the message naming the format.  U holds nrow*k entries and V ncol*k, both ROW-MAJOR as
+ * X and Y of spmv_apply_multi (a C-contiguous torch (n, k) tensor wraps directly); out holds info.nnz entries in the handle's CSR
+ * entry order: out[row_ptr[i] + t] belongs to the t-th stored entry of row i.  1 <= k <= 64.  Index arithmetic on U and V is 64-bit.
+ * beta == 0.0: out is NOT READ (NaN in it does not propagate); alpha == 0.0 has no special case.  U and V may be the same vector
+ * (nrow == ncol).  nnz = 0, nrow = 0 or ncol = 0 succeed and launch nothing.  Asynchronous on the context's stream.
+ * Every argument is checked on the host before the device is touched: a null pointer, k out of range, U, V or out of another
+ * length, out overlapping U or V, a CSR handle that released its arrays (panel_keep_csr = 0): SPMV_ERR_INVALID with a message, out
+ * untouched.
+ * This is the adjoint of the products in the matrix values: for y = A x, dL/da_e = g[row(e)] * x[col(e)] (k = 1); for Y = A X,
+ * dL/da_e = G[row(e), :] . X[col(e), :].
+ * Order of the additions (the contract): every product U[i, c] * V[j, c] is rounded on its own (no fma).  With L the next power of
+ * two >= k and p_c = 0.0 for k <= c < L, the L terms are summed as a balanced pairwise tree: p_c + p_(c xor 1), then the pair sums
+ * at distance 2, 4, ..., L / 2 (k = 3: (p0 + p1) + (p2 + 0.0)).  Then out = alpha * s where beta == 0.0, else
+ * fma(alpha, s, beta * out).  The order depends on k alone, never on the entry's position, its row's length or the launch: the call is
+ * deterministic, and the same entries stored as one long row or as many short ones give the same bits.
+ * The call reads row_ptr and col_ind of the handle only and changes nothing in it: plan, kernel, copies and device_bytes stay.
+ * Kernel (kernels_sddmm.hip, sddmm_settings.hpp): work is divided by entries, not rows - a wavefront takes a run of 512 entries
+ * wherever they lie and finds its rows by searching row_ptr, so one row of 1M entries is spread like any other 1M entries. */
+int spmv_sddmm(spmv_ctx* ctx, const spmv_mat* A, int32_t k, double alpha, const spmv_vec* U, const spmv_vec* V, double beta,
+               spmv_vec* out);
+/* `reps` back-to-back spmv_sddmm between two HIP events on the context's stream; the mean milliseconds per call.  Synchronous. */
+int spmv_sddmm_timed(spmv_ctx* ctx, const spmv_mat* A, int32_t k, double alpha, const spmv_vec* U, const spmv_vec* V, double beta,
+                     spmv_vec* out, int32_t reps, double* ms_per_call);
+/* A new CSR handle that BORROWS A's device row_ptr / col_ind and the storage of `values` as its values: spmv_csr_wrap_device over
+ * pointers the engine already holds, so that an spmv_sddmm result becomes a matrix every product and solver accepts without a round
+ * trip through the host.  A row shard gives a row shard.  The new handle is validated and analysed like any wrapped handle
+ * (synchronous); A is not changed.  The caller keeps A and the vector alive for as long as the new handle lives, and destroys the
+ * new handle with spmv_mat_destroy.  Refused (SPMV_ERR_INVALID): null arguments, `values` with other than nnz entries, A not a CSR
+ * handle with its arrays. */
+int spmv_csr_with_values(spmv_ctx* ctx, const spmv_mat* A, const spmv_vec* values, spmv_mat** out);
+
 /* y += A^T x.  x has nrow entries (the shard's rows), y has ncol entries.  Asynchronous.  Every format: CSR (uploaded, wrapped,
  * shard), CSC and COO run on an internal companion handle that borrows A's arrays read the other way round (CSR -> CSC, CSC ->
  * CSR, COO -> COO with rows and columns swapped) and picks its own kernel; ELL runs as a COO companion that borrows col_ind and
